@@ -38,6 +38,12 @@ Prints ONE JSON line (rank 0): metric/value/unit per BASELINE.json, plus
   config.secondary -- BASELINE configs[1] (minifam x 1000 synthetic 3 kb reads), same engine
   config.large_db -- the cost pass over a database of 5000 profiles (5.3 GB file, 6 GB of tables) x 100 reads
                   (--large-db P; 0 skips it)
+
+--dump-outputs DIR writes what the last timed step computed -- the viterbi_null and viterbi_cost scores of every
+staged window, the arrays Engine.cost returns for that window list -- as DIR/null_cost.npy and DIR/alt_cost.npy
+(float32, in window order; with N ranks, DIR/<name>_rank<i>.npy).  The inputs depend on the arguments alone, so two
+builds run with the same arguments can be compared output for output.  Above 64 MB in all, the same seeded sample of
+windows is written on every run (config.dumped.sampled).
 """
 import argparse
 import hashlib
@@ -61,6 +67,7 @@ HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 VALU_ISSUE_PEAK = 256 * 4 * 2.4 / 2.0  # G wave64-VALU instr/s: 256 CUs x 4 SIMD-32s, 2.4 GHz, 2 cycles each
 VALU_MEASURED_PEAK = 848.0  # best sustained stream on this GPU: 2 v_add_f32 per v_min3_f32, 8 waves per SIMD
 BYTES_PER_CELL = 20.0  # five fp32 match-emission operands per DP cell (cost pass)
+DUMP_LIMIT_BYTES = 64_000_000  # --dump-outputs: all files of all ranks together, .npy headers included
 SEED = 20250310
 SEED_DB = os.path.join(ROOT, "tests", "golden", "minifam.dcp")  # the reference's committed fixture (data)
 
@@ -334,6 +341,23 @@ def large_db(args, device, tmp):
             "value": cells * args.large_db_steps / (ms * 1e-3) / 1e9, "unit": "GCUPS", "steps": args.large_db_steps}
 
 
+def dump_outputs(out_dir, arrays, rank, world):
+    """--dump-outputs: float32 arrays of one value per window, written as out_dir/<name>.npy (<name>_rank<i>.npy with
+    several ranks).  Beyond DUMP_LIMIT_BYTES in all, every rank writes the same seeded, sorted sample of its windows."""
+    n = len(next(iter(arrays.values())))
+    limit = (DUMP_LIMIT_BYTES // world - 256 * len(arrays)) // (len(arrays) * 4)  # windows per rank
+    keep = None
+    if n > limit:
+        keep = np.sort(np.random.default_rng(SEED).choice(n, size=limit, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if world == 1 else f"_rank{rank}"
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a if keep is None else a[keep])
+    return {"dir": os.path.abspath(out_dir), "arrays": sorted(arrays), "windows": n,
+            "written": n if keep is None else int(len(keep)), "sampled": keep is not None}
+
+
 def measured_counters(workload_key):
     """PMC summary of this workload on this kernel source (scripts/profile_bench.sh -> profiles/*_traffic.json:
     FETCH_SIZE / WRITE_SIZE / SQ_INSTS_* from separate --pmc passes).  None when no summary matches."""
@@ -385,9 +409,13 @@ def main():
     ap.add_argument("--large-db-steps", type=int, default=2)
     ap.add_argument("--profile", action="store_true",
                     help="only warmup + timed launches (for rocprofv3: every dispatch is one step's)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the scores of the last timed step as DIR/null_cost.npy, DIR/alt_cost.npy (float32)")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be at least 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.reads is None:
         args.reads = 500 if args.workload == "pfam" else 1000
     if args.read_len is None:
@@ -466,6 +494,10 @@ def run(args, torch, deciphon_amd, ddist, dist, rank, local_rank, world, dev, de
     ms, cells = eng.run_staged(args.steps)  # returns when the last launch has finished
     barrier()
     wall = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs:  # the last timed step's scores, before anything else runs on this engine
+        nul, alt = eng.fetch_staged()
+        dumped = dump_outputs(args.dump_outputs, {"null_cost": nul, "alt_cost": alt}, rank, world)
 
     t = torch.tensor([wall], dtype=torch.float64, device=dev_coll)
     c = torch.tensor([cells], dtype=torch.float64, device=dev_coll)
@@ -543,6 +575,8 @@ def run(args, torch, deciphon_amd, ddist, dist, rank, local_rank, world, dev, de
                        "rccl_ranks": rccl_ranks, "world_size": dist.get_world_size()}},
         "roofline": roof,
     }
+    if dumped is not None:
+        out["config"]["dumped"] = dumped
     if db is not None:
         out["config"]["database"] = {k: v for k, v in db.items() if k != "path"}
         out["config"]["database"]["ingest_GBps"] = db["file_bytes"] / db["ingest_s"] / 1e9

@@ -145,6 +145,51 @@ def reflib():
     return RefLib() if RefLib.available() else None
 
 
+def ref_pins_lib(r):
+    """The CDLL of reflib() with the prototypes of the non-DP functions it also holds: c-core/partition_size.c,
+    state.c, disambiguate.c, uppercase.c, error.c."""
+    L = r.lib
+    L.partition_size.argtypes = [C.c_long, C.c_long, C.c_long]
+    L.partition_size.restype = C.c_long
+    L.state_name.argtypes = [C.c_int, C.c_char_p]
+    for f in ("state_is_mute", "state_is_core", "state_is_start", "state_is_end"):
+        getattr(L, f).argtypes = [C.c_int]
+        getattr(L, f).restype = C.c_bool
+    for f in ("state_make_match_id", "state_make_insert_id", "state_make_delete_id", "state_core_idx"):
+        getattr(L, f).argtypes = [C.c_int]
+        getattr(L, f).restype = C.c_int
+    L.state_make_end.restype = C.c_int
+    L.disambiguate.argtypes = [C.c_int, C.c_char_p]
+    L.uppercase.argtypes = [C.c_size_t, C.c_char_p]
+    L.dcp_error_string.argtypes = [C.c_int]
+    L.dcp_error_string.restype = C.c_char_p
+    return L
+
+
+def ref_state_name(L, sid) -> str:
+    buf = C.create_string_buffer(16)
+    assert L.state_name(int(sid), buf) == 0
+    return buf.value.decode()
+
+
+def ref_encode(L, text):
+    """sequence_setup's first steps (c-core/sequence.c:20-24): uppercase, then disambiguate -> (rc, text).
+    error() logs at the raise site (c-core/error.c:102-121): stderr is muted around the call."""
+    raw = text.encode("latin-1")
+    buf = C.create_string_buffer(raw, len(raw) + 1)
+    devnull = os.open(os.devnull, os.O_WRONLY)
+    saved = os.dup(2)
+    os.dup2(devnull, 2)
+    try:
+        L.uppercase(len(raw), buf)
+        rc = L.disambiguate(len(raw), buf)
+    finally:
+        os.dup2(saved, 2)
+        os.close(devnull)
+        os.close(saved)
+    return rc, buf.raw[: len(raw)].decode("latin-1")
+
+
 def bits(x) -> int:
     return int(np.float32(x).view(np.uint32))
 

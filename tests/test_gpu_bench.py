@@ -147,3 +147,48 @@ def test_two_ranks_line():
     whole = _line(one.stdout)["config"]["cells_per_step_per_gpu"]
     assert abs(d["value"] * d["ms_per_step"] * 1e6 - whole) <= 1e-6 * whole
     assert d["config"]["hits_gathered"] >= 1
+
+
+def test_dump_outputs_are_the_step_scores(orc, tmp_path):
+    """--dump-outputs: the last timed step's null/alt scores of every window, in window order, float32; the same bits on
+    a second run with the same arguments, and a sample of them bit for bit the oracle's on the windows bench.py
+    builds."""
+    import types
+
+    import numpy as np
+
+    from deciphon_amd import synth
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    argv = ["--steps", "3", "--warmup", "1", "--profiles", "60", "--reads", "40", "--no-cpu-baseline", "--no-secondary",
+            "--no-end-to-end", "--large-db", "0"]
+    got = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *argv, "--dump-outputs", str(tmp_path / run)],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr
+        d = _line(r.stdout)
+        assert d["steps"] == 3 and d["ms_per_step"] > 0
+        dumped = d["config"]["dumped"]
+        assert dumped["sampled"] is False and dumped["written"] == dumped["windows"] == d["config"]["windows_per_gpu"]
+        got.append({k: np.load(tmp_path / run / f"{k}.npy") for k in ("null_cost", "alt_cost")})
+    assert sorted(os.listdir(tmp_path / "a")) == ["alt_cost.npy", "null_cost.npy"]
+    for k in ("null_cost", "alt_cost"):
+        assert got[0][k].dtype == np.float32 and got[0][k].shape == (dumped["windows"],)
+        assert np.array_equal(got[0][k].view(np.uint32), got[1][k].view(np.uint32)), k
+    nul, alt = got[0]["null_cost"], got[0]["alt_cost"]
+    Ks = synth.pfam_like_lengths(60, bench.SEED)
+    seeds = synth.load_seeds(bench.SEED_DB)
+    reads = bench.pfam_reads(seeds, Ks, 40, 10000)
+    wins = bench.all_windows(Ks, len(reads), 10000)
+    assert len(wins) == len(nul)
+    for i in np.random.default_rng(5).choice(len(wins), size=24, replace=False):
+        p, r, a, b = (int(v) for v in wins[i])
+        prot = synth.pfam_like_database(seeds, 1, bench.SEED, first=p, lengths=Ks[p : p + 1])[0]
+        prof = orc.setup_profile(types.SimpleNamespace(**prot))
+        seq = np.ascontiguousarray(reads[r][a:b])
+        xt = orc.xtrans(max(len(seq) // 3, 1), True, False)
+        assert bits(nul[i]) == bits(orc.null(prof, xt, seq)), (p, r, a, b)
+        assert bits(alt[i]) == bits(orc.cost(prof, xt, seq)), (p, r, a, b)

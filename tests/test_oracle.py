@@ -1,6 +1,6 @@
 """CPU: the oracle restatement (oracle/dcp_oracle.c) against every golden the reference
-holds for this path, and -- where oracle/_ref exists -- against the reference's own
-viterbi.c run live.  This is what pins the oracle."""
+holds for this path and the reference's own viterbi.c's answers recorded under tests/golden/,
+and -- where oracle/_ref exists -- against that viterbi.c run live.  This is what pins the oracle."""
 import os
 import sys
 import zlib
@@ -11,7 +11,7 @@ import pytest
 from dcp_testlib import GOLDEN, bits, random_seq, read_fasta, reflib, synth_profile
 
 sys.path.insert(0, GOLDEN)
-from make_golden import MODES, synth_case_params, synth_xt  # noqa: E402
+from make_golden import LEAK_CASES, MODES, live_cases, synth_case_params, synth_xt  # noqa: E402
 from oracle.dcp_reader import read_dcp  # noqa: E402
 
 
@@ -202,48 +202,64 @@ def test_products_tsv_golden(orc, minifam, reads):
 
 
 def test_live_against_reference_viterbi(orc):
-    """Where oracle/_ref is present: fresh random tie-rich cases against the reference itself."""
+    """Fresh random tie-rich cases (make_golden.live_cases) against the reference's viterbi.c: its score bits and
+    trellis CRC32s as tests/golden/reference_pins.npz recorded them, and -- where oracle/_ref is present -- the
+    reference itself, run live."""
+    g = np.load(os.path.join(GOLDEN, "reference_pins.npz"))
     ref = reflib()
-    if ref is None:
-        pytest.skip("oracle/_ref not built (needs /root/reference)")
-    rng = np.random.default_rng(4242)
-    for it in range(330):
-        # the last cases: sizes of every multi-wave kernel class and of the strip class
-        K = int(rng.choice([2, 3, 5, 8, 9, 17, 33, 64, 100, 173])) if it < 300 else \
-            int(rng.choice([257, 385, 600, 1000, 1537, 2049, 3000, 4097, 6000, 9000]))
-        quant = [None, 1.0, 4.0][it % 3]
-        prof = synth_profile(rng, K, quant, [0.0, 0.2][it % 2])
-        seq = random_seq(rng, int(rng.integers(1, 80)))
-        xt = synth_xt(orc, len(seq), it % 2, (it // 2) % 2, quant)
-        ref.setup(prof)
-        assert bits(orc.null(prof, xt, seq)) == bits(ref.null(xt, seq))
-        assert bits(orc.cost(prof, xt, seq)) == bits(ref.cost(xt, seq))
-        _, xn, nd = orc.path(prof, xt, seq)
-        rx, rn = ref.path(xt, seq)
-        assert np.array_equal(xn, rx) and np.array_equal(nd, rn), (it, K)
+    n = 0
+    for it, (prof, seq, xt) in enumerate(live_cases(orc)):
+        K = prof.K
+        assert (K, len(seq)) == (int(g["live_K"][it]), int(g["live_L"][it]))
+        nul, (alt, xn, nd) = orc.null(prof, xt, seq), orc.path(prof, xt, seq)
+        assert bits(nul) == int(g["live_null_bits"][it]), (it, K)
+        assert bits(orc.cost(prof, xt, seq)) == bits(alt) == int(g["live_cost_bits"][it]), (it, K)
+        assert zlib.crc32(xn.tobytes()) == int(g["live_xnodes_crc"][it]), (it, K)
+        assert zlib.crc32(nd.tobytes()) == int(g["live_nodes_crc"][it]), (it, K)
+        if ref is not None:
+            ref.setup(prof)
+            assert bits(nul) == bits(ref.null(xt, seq))
+            assert bits(alt) == bits(ref.cost(xt, seq))
+            rx, rn = ref.path(xt, seq)
+            assert np.array_equal(xn, rx) and np.array_equal(nd, rn), (it, K)
+        n += 1
+    assert n == len(g["live_K"]) == 330
 
 
 def test_reference_row0_leak_is_off_path(orc, minifam, reads):
     """The reference never clears DP row 0 between runs (c-core/viterbi.c:471-473 only sets S
     and B), so viterbi_path after viterbi_cost on the same struct sees the previous run's last
     row as row 0.  On the goldens that changes trellis words off the optimal path only: scores
-    and unzipped paths equal the history-free run this repository defines parity on."""
+    and unzipped paths equal the history-free run this repository defines parity on.  The
+    reference's runs are those recorded in tests/golden/reference_pins.npz, and where oracle/_ref
+    is present they are made again live and must match the record."""
+    g = np.load(os.path.join(GOLDEN, "reference_pins.npz"))
     ref = reflib()
-    if ref is None:
-        pytest.skip("oracle/_ref not built (needs /root/reference)")
     _, profs = minifam
+    assert [tuple(int(v) for v in c) for c in g["leak_cases"]] == list(LEAK_CASES)
     differs = 0
-    for pi, ri in ((0, 0), (1, 1), (2, 2), (0, 3), (0, 7)):
+    for j, (pi, ri) in enumerate(LEAK_CASES):
         prof, x = profs[pi], reads[ri][2]
         xt = orc.xtrans(max(len(x) // 3, 1), True, False)
-        ref.setup(prof)
-        c_fresh = ref.cost(xt, x, fresh=True)
-        xn1, nd1 = ref.path(xt, x, fresh=False)  # the reference's real call sequence
-        xn0, nd0 = ref.path(xt, x, fresh=True)
-        differs += int(not (np.array_equal(xn0, xn1) and np.array_equal(nd0, nd1)))
-        assert bits(c_fresh) == bits(orc.cost(prof, xt, x))
-        a, b = orc.unzip(prof.K, len(x), xn0, nd0), orc.unzip(prof.K, len(x), xn1, nd1)
-        assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+        crc0 = (int(g["leak_fresh_xcrc"][j]), int(g["leak_fresh_ncrc"][j]))  # history-free
+        crc1 = (int(g["leak_xcrc"][j]), int(g["leak_ncrc"][j]))  # the reference's real call sequence
+        a, b = int(g["leak_path_off"][j]), int(g["leak_path_off"][j + 1])
+        leaky = (g["leak_path_ids"][a:b], g["leak_path_sizes"][a:b])  # the unzip of the latter's trellis
+        if ref is not None:
+            ref.setup(prof)
+            assert bits(ref.cost(xt, x, fresh=True)) == int(g["leak_cost_bits"][j])
+            xn1, nd1 = ref.path(xt, x, fresh=False)
+            xn0, nd0 = ref.path(xt, x, fresh=True)
+            assert (zlib.crc32(xn0.tobytes()), zlib.crc32(nd0.tobytes())) == crc0
+            assert (zlib.crc32(xn1.tobytes()), zlib.crc32(nd1.tobytes())) == crc1
+            ids1, sizes1 = orc.unzip(prof.K, len(x), xn1, nd1)
+            assert np.array_equal(ids1, leaky[0]) and np.array_equal(sizes1, leaky[1])
+        differs += int(crc0 != crc1)
+        assert int(g["leak_cost_bits"][j]) == bits(orc.cost(prof, xt, x))
+        _, xn, nd = orc.path(prof, xt, x)
+        assert (zlib.crc32(xn.tobytes()), zlib.crc32(nd.tobytes())) == crc0
+        ids, sizes = orc.unzip(prof.K, len(x), xn, nd)
+        assert np.array_equal(ids, leaky[0]) and np.array_equal(sizes, leaky[1])
     assert differs > 0  # the leak is real
 
 
