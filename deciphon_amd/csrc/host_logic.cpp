@@ -1,8 +1,11 @@
 // host_logic.cpp -- see host_logic.h
 #include "host_logic.h"
+#include "../../include/deciphon_host.h"
 #include "dcp_errors.h"
 
+#include <algorithm>
 #include <initializer_list>
+#include <limits.h>
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
@@ -366,6 +369,102 @@ void dcp_partition_bounds(int n, int32_t const *core_sizes, int nparts, bool bal
     first[p] = j;
   }
   first[nparts] = n;
+}
+
+// DcpWindow::next without hits: window 0 is [0, min(span, L)); while a window's stop is not cut at L, the next one
+// starts max(1, span + 1 - 4 K) after it (its start + 1, or its stop + 1 - 4 K), and the chain ends with the first
+// window that reaches L.  In int64: the walk's start + span is int arithmetic, this is not.
+extern "C" int64_t dcp_window_count(int64_t seq_size, int core_size)
+{
+  if (seq_size <= 0 || core_size < 1) return 0;
+  int64_t const span = std::min<int64_t>((int64_t)core_size * 50, 100000);
+  int64_t const step = std::max<int64_t>(1, span + 1 - 4 * (int64_t)core_size);
+  return seq_size <= span ? 1 : 1 + (seq_size - span + step - 1) / step;
+}
+
+std::vector<DcpChunk> dcp_plan_chunks(int nprof, int32_t const *core_sizes, int nreads, int32_t const *read_lengths,
+                                      double first_cells, double later_cells, int64_t max_pairs, int64_t max_windows)
+{
+  std::vector<DcpChunk> out;
+  // the windows of a profile against all reads, over the distinct read lengths
+  std::vector<std::pair<int32_t, int64_t>> lengths; // (length, reads of that length)
+  double read_nt = 0;
+  {
+    std::vector<int32_t> sorted(read_lengths, read_lengths + std::max(nreads, 0));
+    std::sort(sorted.begin(), sorted.end());
+    for (int32_t len : sorted)
+    {
+      read_nt += (double)len;
+      if (lengths.empty() || lengths.back().first != len) lengths.emplace_back(len, 0);
+      ++lengths.back().second;
+    }
+  }
+  auto profile_windows = [&](int p) {
+    int64_t n = 0;
+    for (std::pair<int32_t, int64_t> const &l : lengths) n += l.second * dcp_window_count(l.first, core_sizes[p]);
+    return n;
+  };
+  int64_t const by_pairs = nreads > 0 ? std::max<int64_t>(1, max_pairs / nreads) : std::max(nprof, 1);
+  int64_t next_windows = nprof > 0 ? profile_windows(0) : 0; // of profile p0 below
+  for (int p0 = 0; p0 < nprof;)
+  {
+    if (next_windows > max_windows || nreads > max_pairs)
+    {
+      // one profile against all reads is more than a chunk: ranges of reads, a single pair above the cap alone
+      for (int s0 = 0; s0 < nreads;)
+      {
+        int s1 = s0;
+        int64_t w = 0;
+        while (s1 < nreads && s1 - s0 < max_pairs)
+        {
+          int64_t const ws = dcp_window_count(read_lengths[s1], core_sizes[p0]);
+          if (s1 > s0 && w + ws > max_windows) break;
+          w += ws;
+          ++s1;
+        }
+        out.push_back(DcpChunk{p0, p0 + 1, s0, s1, w});
+        s0 = s1;
+      }
+      ++p0;
+      next_windows = p0 < nprof ? profile_windows(p0) : 0;
+      continue;
+    }
+    double const limit = out.empty() ? first_cells : later_cells;
+    int p1 = p0;
+    double cells = 0;
+    int64_t w = 0;
+    while (p1 < nprof && p1 - p0 < by_pairs && (p1 == p0 || (cells < limit && w + next_windows <= max_windows)))
+    {
+      cells += read_nt * (double)core_sizes[p1];
+      w += next_windows;
+      ++p1;
+      next_windows = p1 < nprof ? profile_windows(p1) : 0;
+    }
+    out.push_back(DcpChunk{p0, p1, 0, std::max(nreads, 0), w});
+    p0 = p1;
+  }
+  return out;
+}
+
+extern "C" int dcp_scan_plan_chunks(int nprof, int32_t const *core_sizes, int nreads, int32_t const *read_lengths,
+                                    double first_cells, double later_cells, int64_t max_pairs, int64_t max_windows,
+                                    int cap, int32_t *chunks, int64_t *windows, int *nchunks)
+{
+  if (nprof < 0 || nreads < 0 || (nprof > 0 && !core_sizes) || (nreads > 0 && !read_lengths) || !nchunks ||
+      max_pairs < 1 || max_windows < 1 || cap < 0 || (cap > 0 && (!chunks || !windows)))
+    return DCP_EFUNCUSE;
+  std::vector<DcpChunk> const plan =
+      dcp_plan_chunks(nprof, core_sizes, nreads, read_lengths, first_cells, later_cells, max_pairs, max_windows);
+  if (plan.size() > (size_t)INT_MAX) return DCP_ENOMEM;
+  *nchunks = (int)plan.size();
+  if (plan.size() > (size_t)cap) return DCP_ENOMEM;
+  for (size_t i = 0; i < plan.size(); ++i)
+  {
+    int32_t const c[4] = {plan[i].p0, plan[i].p1, plan[i].s0, plan[i].s1};
+    memcpy(chunks + 4 * i, c, sizeof c);
+    windows[i] = plan[i].windows;
+  }
+  return 0;
 }
 
 // ---- quasi-codon decoding (see host_logic.h) ----

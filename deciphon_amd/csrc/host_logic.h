@@ -61,6 +61,23 @@ inline float dcp_lrt(float null_loglik, float alt_loglik) { return -2 * (null_lo
 // number of profiles.
 void dcp_partition_bounds(int n, int32_t const *core_sizes, int nparts, bool balanced, int32_t *first);
 
+// The chunks dcp_scan_run scores speculatively, one cost batch each: profiles [p0, p1) x reads [s0, s1), and the
+// number of windows of the no-hit chains of those pairs (dcp_window_count, include/deciphon_host.h).  The chunks tile
+// profiles x reads in (profile, read) order.  Whole profiles are taken while a chunk holds fewer than
+// max(1, max_pairs / nreads) profiles, its cells (K x all reads' nucleotides, summed) are below first_cells (the
+// first chunk) or later_cells (every other one) -- the profile that crosses it is still taken -- and the next
+// profile keeps the chunk at or below max_windows.  A profile that alone is over max_windows (or over max_pairs
+// pairs) is split by reads: chunks of that one profile, each at or below both caps.  The only chunk above
+// max_windows is a single pair whose own chain is longer: a pair's chain is never split (its speculated
+// scores must all be at hand when it hits, dcp_scan_run's kept_lrt).
+struct DcpChunk
+{
+  int p0, p1, s0, s1;
+  int64_t windows;
+};
+std::vector<DcpChunk> dcp_plan_chunks(int nprof, int32_t const *core_sizes, int nreads, int32_t const *read_lengths,
+                                      double first_cells, double later_cells, int64_t max_pairs, int64_t max_windows);
+
 // ---- quasi-codon decoding: decoder_decode (c-core/decoder.c:38-58) + imm_gencode_decode ----
 // The arithmetic is third-party imm's imm_frame_cond_decode (absent here; unpinned HEAD in the reference's CI).
 // Restated from the published quasi-codon model, whose marginal form the pressed tables themselves confirm

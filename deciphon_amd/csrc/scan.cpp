@@ -15,6 +15,7 @@
 // in the reference's order (profile, then read, then window) whatever the order of work.
 #include "../../include/deciphon.h"
 #include "../../include/deciphon_hip.h"
+#include "../../include/deciphon_host.h"
 #include "dcp_db.h"
 #include "dcp_errors.h"
 #include "host_logic.h"
@@ -23,6 +24,7 @@
 #include <atomic>
 #include <chrono>
 #include <errno.h>
+#include <limits.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -417,31 +419,45 @@ int dcp_scan_run(struct dcp_scan *x, struct dcp_batch *batch, char const *produc
   // (length, core size) pairs of a Pfam-sized scan of 1e4 reads of 1e4 lengths would hold 2e8 chains.
   std::map<int, Chain> chains_of_profile;
   std::deque<Chain> kept_chains; // the chains of the pairs that hit: they walk them again (PairState::spec)
-  // chunks of profiles: small enough for the window table of a chunk (2^21 pairs); the first one is kept short
-  // (~1e10 DP cells, a dozen milliseconds of cost pass) so that the GPU starts early and the host builds and sorts
-  // the window list of the second chunk meanwhile (14 ms for the headline's 416 k windows; 4e10 cells while the upload
-  // of that list still waited for the device, profiles/r03_exp_register_policy.txt: 0.497-0.499 -> 0.493-0.495 s).
+  // chunks (dcp_plan_chunks: profiles [p0, p1) x reads [s0, s1)): small enough for the window table of a chunk (2^21
+  // pairs; DECIPHON_HIP_CHUNK_WINDOWS windows, 4 Mi by default -- a chunk holds every window of its pairs' no-hit
+  // chains, and the host keeps its list, the pinned copy and per-window results for two chunks in flight); the first
+  // one is kept short (~1e10 DP cells, a dozen milliseconds of cost pass) so that the GPU starts early and the host
+  // builds the window list of the second chunk meanwhile (14 ms for the headline's 416 k windows; 4e10 cells while the
+  // upload of that list still waited for the device, profiles/r03_exp_register_policy.txt: 0.497-0.499 -> 0.493-0.495 s).
   // DECIPHON_HIP_CHUNK_CELLS: cells per chunk (experiments).
-  std::vector<std::pair<int, int>> chunks;
+  std::vector<DcpChunk> chunks;
   {
-    double read_nt = 0;
-    for (dcp_batch::Seq const &sq : batch->seqs) read_nt += (double)sq.nt.size();
-    size_t const max_pairs = 1u << 21;
-    int const by_pairs = nseq > 0 ? (int)std::max<size_t>(1, max_pairs / (size_t)nseq) : std::max(nprof, 1);
+    std::vector<int32_t> K((size_t)std::max(nprof, 0)), len((size_t)nseq);
+    for (int p = 0; p < nprof; ++p) K[(size_t)p] = dcp_hip_profile_core_size(x->eng, p);
+    for (int s = 0; s < nseq; ++s)
+    {
+      if (batch->seqs[(size_t)s].nt.size() > (size_t)INT_MAX) return raise(DCP_EFUNCUSE, __func__, "a read is longer than INT_MAX");
+      len[(size_t)s] = (int32_t)batch->seqs[(size_t)s].nt.size();
+    }
     char const *cells_env = getenv("DECIPHON_HIP_CHUNK_CELLS");
     double const chunk_cells = cells_env ? atof(cells_env) : 0.0;
-    double const first_cells = 1.0e10;
-    for (int p0 = 0; p0 < nprof;)
-    {
-      int p1 = p0;
-      double cells = 0;
-      double const limit = chunk_cells > 0 ? chunk_cells : p0 == 0 ? first_cells : 1.0e300;
-      while (p1 < nprof && p1 - p0 < by_pairs && (p1 == p0 || cells < limit))
-        cells += read_nt * (double)dcp_hip_profile_core_size(x->eng, p1++);
-      chunks.emplace_back(p0, p1);
-      p0 = p1;
-    }
+    char const *windows_env = getenv("DECIPHON_HIP_CHUNK_WINDOWS");
+    double const chunk_windows = windows_env ? atof(windows_env) : 0.0;
+    chunks = dcp_plan_chunks(nprof, K.data(), nseq, len.data(), chunk_cells > 0 ? chunk_cells : DCP_SCAN_FIRST_CHUNK_CELLS,
+                             chunk_cells > 0 ? chunk_cells : HUGE_VAL, DCP_SCAN_CHUNK_PAIRS,
+                             chunk_windows >= 1 ? (int64_t)std::min(chunk_windows, 1.0e18) : DCP_SCAN_CHUNK_WINDOWS);
+    // the engine takes a window list's length as int (only a single pair's chain is beyond the cap, and no read of
+    // fewer than 2^31 nucleotides makes 2^31 windows, but DECIPHON_HIP_CHUNK_WINDOWS may raise the cap that far)
+    for (DcpChunk const &c : chunks)
+      if (c.windows > (int64_t)INT_MAX)
+        return raise(DCP_EFUNCUSE, __func__, "a chunk holds more than INT_MAX windows: lower DECIPHON_HIP_CHUNK_WINDOWS");
   }
+  // Path passes run once no cost batch is in flight.  When more than DECIPHON_HIP_PATH_DRAIN_HITS windows wait for
+  // one, no new chunk is begun: the batches in flight end, the path passes run, the decoders of the profiles that
+  // are through are released, and then the chunks go on.  Without that every hit would wait for the last chunk, and
+  // the decoders of all profiles with hits would be held at once.  (The chains and speculated scores of the pairs
+  // that hit, kept_chains / kept_lrt, stay for the whole scan either way.)  The default, 32768, is above the
+  // headline's ~2300 hits and the 13 k of the stress scan: those run their path passes at the end, as before.
+  char const *drain_env = getenv("DECIPHON_HIP_PATH_DRAIN_HITS");
+  size_t const drain_hits = drain_env ? (size_t)std::max(atol(drain_env), 0L) : (size_t)32768;
+  int chunks_begun = 0, path_batches = 0;
+  int64_t largest_chunk = 0;
   struct PairState
   {
     int profile, seq;
@@ -529,6 +545,8 @@ int dcp_scan_run(struct dcp_scan *x, struct dcp_batch *batch, char const *produc
     ph.windows += ph.lap();
     if (steps_copied.valid()) steps_copied.wait(); // the previous batch's formatters still read the engine's step buffers
     steps_copied = std::shared_future<void>();
+    if (hits.size() > (size_t)INT_MAX) return raise(DCP_ENOMEM, __func__, "more than INT_MAX windows for one path pass");
+    ++path_batches;
     int prc = dcp_hip_path(x->eng, (int)hits.size(), hits.data());
     if (prc) return raise(prc, __func__, dcp_hip_strerror(x->eng));
     ph.path += ph.lap();
@@ -643,6 +661,7 @@ int dcp_scan_run(struct dcp_scan *x, struct dcp_batch *batch, char const *produc
     int nh = 0;
     ++rounds;
     ph.windows += ph.lap();
+    if (wins.size() > (size_t)INT_MAX) return raise(DCP_ENOMEM, __func__, "more than INT_MAX windows to score again");
     int crc = dcp_hip_cost_hits(x->eng, (int)wins.size(), wins.data(), &nh, hit_index.data(), lrts.data());
     if (crc) return raise(crc, __func__, dcp_hip_strerror(x->eng));
     ph.cost += ph.lap();
@@ -665,7 +684,7 @@ int dcp_scan_run(struct dcp_scan *x, struct dcp_batch *batch, char const *produc
     {
       int chunk;
       std::vector<dcp_hip_window> wins;
-      std::vector<size_t> base; // first window of pair (p - p0) * nseq + s
+      std::vector<size_t> base; // first window of pair (p - p0) * (s1 - s0) + (s - s0)
     };
     std::deque<InFlight> flight;
     // whatever happens, no batch stays outstanding on the engine
@@ -685,52 +704,50 @@ int dcp_scan_run(struct dcp_scan *x, struct dcp_batch *batch, char const *produc
       }
     } drain{x->eng, &flight};
     auto begin_chunk = [&](int c) -> int {
-      int const p0 = chunks[(size_t)c].first, p1 = chunks[(size_t)c].second;
+      DcpChunk const &chunk = chunks[(size_t)c];
       InFlight f;
       f.chunk = c;
-      f.base.reserve((size_t)(p1 - p0) * (size_t)nseq + 1);
-      for (int pass = 0; pass < 2; ++pass) // count, then fill
+      f.base.reserve((size_t)(chunk.p1 - chunk.p0) * (size_t)(chunk.s1 - chunk.s0) + 1);
+      f.wins.resize((size_t)chunk.windows); // (dcp_plan_chunks counted them)
+      size_t n = 0;
+      for (int p = chunk.p0; p < chunk.p1; ++p)
       {
-        size_t n = 0;
-        for (int p = p0; p < p1; ++p)
+        int const K = dcp_hip_profile_core_size(x->eng, p);
+        int last_len = -1;
+        Chain const *ch = nullptr; // reads of one length follow each other more often than not
+        chains_of_profile.clear();
+        for (int s = chunk.s0; s < chunk.s1; ++s)
         {
-          int const K = dcp_hip_profile_core_size(x->eng, p);
-          int last_len = -1;
-          Chain const *ch = nullptr; // reads of one length follow each other more often than not
-          chains_of_profile.clear();
-          for (int s = 0; s < nseq; ++s)
+          int const len = (int)batch->seqs[(size_t)s].nt.size();
+          if (len != last_len)
           {
-            int const len = (int)batch->seqs[(size_t)s].nt.size();
-            if (len != last_len)
+            ch = nullptr;
+            if (len > 0)
             {
-              ch = nullptr;
-              if (len > 0)
+              auto it = chains_of_profile.find(len);
+              if (it == chains_of_profile.end())
               {
-                auto it = chains_of_profile.find(len);
-                if (it == chains_of_profile.end())
-                {
-                  it = chains_of_profile.emplace(len, Chain()).first;
-                  make_chain(len, K, it->second);
-                }
-                ch = &it->second;
+                it = chains_of_profile.emplace(len, Chain()).first;
+                make_chain(len, K, it->second);
               }
-              last_len = len;
+              ch = &it->second;
             }
-            if (pass == 1)
-            {
-              f.base.push_back(n);
-              if (ch)
-              {
-                dcp_hip_window *w = f.wins.data() + n;
-                for (std::pair<int, int> const &r : *ch) *w++ = dcp_hip_window{p, s, r.first, r.second};
-              }
-            }
-            n += ch ? ch->size() : 0;
+            last_len = len;
+          }
+          f.base.push_back(n);
+          if (ch)
+          {
+            if (ch->size() > f.wins.size() - n) return raise(DCP_EFUNCUSE, __func__, "chunk plan and window chains disagree");
+            dcp_hip_window *w = f.wins.data() + n;
+            for (std::pair<int, int> const &r : *ch) *w++ = dcp_hip_window{p, s, r.first, r.second};
+            n += ch->size();
           }
         }
-        if (pass == 0) f.wins.resize(n);
       }
-      f.base.push_back(f.wins.size());
+      if (n != f.wins.size()) return raise(DCP_EFUNCUSE, __func__, "chunk plan and window chains disagree");
+      f.base.push_back(n);
+      ++chunks_begun;
+      largest_chunk = std::max(largest_chunk, (int64_t)n);
       ph.windows += ph.lap();
       ++rounds;
       int brc = dcp_hip_cost_hits_begin(x->eng, (int)f.wins.size(), f.wins.data());
@@ -746,13 +763,19 @@ int dcp_scan_run(struct dcp_scan *x, struct dcp_batch *batch, char const *produc
     };
     int next = 0;
     int const nchunks = (int)chunks.size();
-    while (next < nchunks && flight.size() < 2 && !x->interrupted)
-      if ((rc = begin_chunk(next++))) return rc;
+    int released = 0; // the decoders of profiles [0, released) are gone
+    auto refill = [&]() -> int {
+      while (next < nchunks && flight.size() < 2 && need_path.size() <= drain_hits && !x->interrupted)
+        if (int const brc = begin_chunk(next++)) return brc;
+      return 0;
+    };
+    if ((rc = refill())) return rc;
     while (!flight.empty())
     {
       InFlight f = std::move(flight.front());
       flight.pop_front();
-      int const p0 = chunks[(size_t)f.chunk].first, p1 = chunks[(size_t)f.chunk].second;
+      DcpChunk const &chunk = chunks[(size_t)f.chunk];
+      int const p0 = chunk.p0, s0 = chunk.s0, ns = chunk.s1 - chunk.s0;
       std::vector<int32_t> hit_index(f.wins.size() + 1);
       std::vector<float> lrts(f.wins.size() + 1);
       int nh = 0;
@@ -760,7 +783,7 @@ int dcp_scan_run(struct dcp_scan *x, struct dcp_batch *batch, char const *produc
         return raise(rc, __func__, dcp_hip_strerror(x->eng));
       ph.cost += ph.lap();
       if (x->interrupted) continue; // (the batches still in flight are ended and dropped)
-      if (next < nchunks && (rc = begin_chunk(next++))) return rc;
+      if (next < nchunks && need_path.size() <= drain_hits && (rc = begin_chunk(next++))) return rc;
       size_t speculated_of_hit_pairs = 0, first_new = st.size();
       size_t last_pi = (size_t)-1;
       for (int h = 0; h < nh; ++h) // hit_index ascends: the hits of a pair are neighbours
@@ -770,7 +793,7 @@ int dcp_scan_run(struct dcp_scan *x, struct dcp_batch *batch, char const *produc
         if (pi != last_pi) // a pair's first hit: its chain and the (so far hit-less) scores of the chain's windows
         {
           last_pi = pi;
-          int const p = p0 + (int)(pi / (size_t)nseq), sq = (int)(pi % (size_t)nseq);
+          int const p = p0 + (int)(pi / (size_t)ns), sq = s0 + (int)(pi % (size_t)ns);
           int const len = (int)batch->seqs[(size_t)sq].nt.size(), K = dcp_hip_profile_core_size(x->eng, p);
           kept_chains.emplace_back();
           make_chain(len, K, kept_chains.back());
@@ -783,17 +806,25 @@ int dcp_scan_run(struct dcp_scan *x, struct dcp_batch *batch, char const *produc
       nwindows += f.wins.size() - speculated_of_hit_pairs; // the windows of the pairs without a hit are final
       for (size_t i = first_new; i < st.size(); ++i) advance(i);
       ph.windows += ph.lap();
-      // The path passes of the hits so far -- once no batch is in flight: beside a cost pass the path kernels, few
-      // wavefronts bound by memory latency, take several times as long and hold the cost kernels up for as long
-      // (whichever priority their streams have: profiles/r03_scan_pipeline.txt), so the scan gains nothing from the
-      // overlap and a short one loses.  What needs scoring again waits for the end as well.
+      // The path passes of the hits so far -- once no batch is in flight (at the end, or after a drain): beside a
+      // cost pass the path kernels, few wavefronts bound by memory latency, take several times as long and hold the
+      // cost kernels up for as long (whichever priority their streams have: profiles/r03_scan_pipeline.txt), so the
+      // scan gains nothing from the overlap and a short one loses.  What needs scoring again waits for the end.
       while ((flight.empty() || path_beside) && !need_path.empty() && !x->interrupted)
         if ((rc = run_path_batch())) return rc;
-      // the decoders of this chunk's profiles go with the chunk once its rows are under way (a memo of (K + 3) * 1364
-      // bytes each; the formatter jobs hold their own references): a Pfam-sized database with hits on most profiles
-      // would pin gigabytes.  (A pair of this chunk that hits again in the final rounds makes a new one.)
-      for (int p = p0; p < p1; ++p) x->decoders[(size_t)p].reset();
-      x->done_proteins += p1 - p0;
+      // a profile is through at its last chunk of reads
+      int const through = chunk.s1 == nseq ? chunk.p1 : chunk.p0;
+      x->done_proteins += through - p0;
+      // Once the path passes have caught up, the decoders of the profiles that are through go (a memo of (K + 3) *
+      // 1364 bytes each, made by run_path_batch; the formatter jobs hold their own references): a Pfam-sized database
+      // with hits on most profiles would pin gigabytes by the end of the scan.  (A pair of such a profile that hits
+      // again in the final rounds makes a new one.)
+      if (need_path.empty())
+      {
+        for (int p = released; p < through; ++p) x->decoders[(size_t)p].reset();
+        released = std::max(released, through);
+      }
+      if ((rc = refill())) return rc;
     }
   }
   else
@@ -841,14 +872,17 @@ int dcp_scan_run(struct dcp_scan *x, struct dcp_batch *batch, char const *produc
   {
     // (the progress callbacks of a batch are made while the GPU scores it: they count as cost pass)
     double const t[DCP_SCAN_TIMING_VALUES] = {ph.total(), ph.reads, ph.windows, ph.cost + ph.callbacks, ph.path, ph.rows, ph.write,
-                                              (double)rounds, (double)nwindows, (double)nhits};
+                                              (double)rounds, (double)nwindows, (double)nhits, (double)chunks_begun,
+                                              (double)largest_chunk, (double)path_batches};
     memcpy(x->timing, t, sizeof t);
   }
   if (getenv("DECIPHON_HIP_TIMING"))
     fprintf(stderr,
-            "dcp_scan_run: %d rounds, %zu windows, %zu path passes; windows %.3f s, cost pass %.3f s, path pass %.3f s, "
-            "rows %.3f s, products.tsv %.3f s; of the cost pass %.3f s in progress callbacks\n",
-            rounds, nwindows, nhits, ph.windows, ph.cost + ph.callbacks, ph.path, ph.rows, ph.write, ph.callbacks);
+            "dcp_scan_run: %d rounds, %zu windows, %zu path passes in %d batches, %d chunks of at most %lld windows; "
+            "windows %.3f s, cost pass %.3f s, path pass %.3f s, rows %.3f s, products.tsv %.3f s; of the cost pass "
+            "%.3f s in progress callbacks\n",
+            rounds, nwindows, nhits, path_batches, chunks_begun, (long long)largest_chunk, ph.windows,
+            ph.cost + ph.callbacks, ph.path, ph.rows, ph.write, ph.callbacks);
   return 0;
 }
 

@@ -42,6 +42,10 @@ def _lib():
     L.dcp_partition_bounds_of.argtypes = [i32, vp, i32, i32, vp]
     L.dcp_partition_size.argtypes = [C.c_long, C.c_long, C.c_long]
     L.dcp_partition_size.restype = C.c_long
+    L.dcp_window_count.argtypes = [C.c_int64, i32]
+    L.dcp_window_count.restype = C.c_int64
+    L.dcp_scan_plan_chunks.argtypes = [i32, vp, i32, vp, C.c_double, C.c_double, C.c_int64, C.c_int64, i32, vp, vp,
+                                       C.POINTER(i32)]
     L.dcp_window_setup.argtypes = [C.POINTER(_Window), i32, i32]
     L.dcp_window_setup.restype = None
     L.dcp_window_next.argtypes = [C.POINTER(_Window)]
@@ -168,6 +172,33 @@ class WindowIter:
 
     def set_last_hit_position(self, pos: int) -> None:
         self.w.last_hit_pos = pos
+
+
+def window_count(seq_size: int, core_size: int) -> int:
+    """Windows of the no-hit chain of one (read, profile) pair (what WindowIter walks when nothing hits)."""
+    return int(_lib().dcp_window_count(int(seq_size), int(core_size)))
+
+
+def plan_chunks(core_sizes, read_lengths, first_cells: float, later_cells: float, max_pairs: int, max_windows: int):
+    """dcp_scan_run's cost batches: (chunks int32[n][4] = (p0, p1, s0, s1), windows int64[n]) -- profiles [p0, p1)
+    x reads [s0, s1) -- for profiles and reads of these sizes (csrc/host_logic.h dcp_plan_chunks)."""
+    L = _lib()
+    K = np.ascontiguousarray(core_sizes, np.int32)
+    R = np.ascontiguousarray(read_lengths, np.int32)
+    cap = 64
+    while True:
+        chunks = np.zeros((cap, 4), np.int32)
+        windows = np.zeros(cap, np.int64)
+        n = C.c_int(0)
+        rc = L.dcp_scan_plan_chunks(len(K), K.ctypes.data_as(C.c_void_p), len(R), R.ctypes.data_as(C.c_void_p),
+                                    float(first_cells), float(later_cells), int(max_pairs), int(max_windows), cap,
+                                    chunks.ctypes.data_as(C.c_void_p), windows.ctypes.data_as(C.c_void_p), C.byref(n))
+        if rc == 20 and n.value > cap:  # DCP_ENOMEM: more chunks than room, their number is known now
+            cap = n.value
+            continue
+        if rc:
+            raise HipError(rc)
+        return chunks[: n.value].copy(), windows[: n.value].copy()
 
 
 def unzip(K: int, L: int, xnodes: np.ndarray, nodes: np.ndarray):

@@ -135,7 +135,8 @@ class Scan:
     def last_timing(self) -> dict:
         """Where the wall time of the last run went (dcp_scan_last_timing): seconds per phase and counts."""
         keys = ("total_s", "reads_h2d_encode_s", "window_bookkeeping_s", "cost_pass_s", "path_pass_s", "rows_decode_s",
-                "products_tsv_s", "rounds", "windows", "path_passes")
+                "products_tsv_s", "rounds", "windows", "path_passes", "chunks", "largest_chunk_windows",
+                "path_batches")
         buf = (C.c_double * len(keys))()
         n = self._lib.dcp_scan_last_timing(self._cscan, buf, len(keys))
         assert n == len(keys)

@@ -160,9 +160,10 @@ char const *dcp_scan_product(struct dcp_scan const *, long i);
 /* Where the wall time of the last dcp_scan_run went (measurement only; SURVEY 8d's wall definition: first H2D of the
  * reads to the last product row on the host).  Fills out[0..n) with, in order: total seconds, reads H2D + encode,
  * window bookkeeping, cost pass + LRT filter, path pass + unzip (the part the cost pass did not cover), row
- * formatting + decoding, products.tsv, then the counts of rounds, windows scored and path passes.  Returns how many
- * values exist (DCP_SCAN_TIMING_VALUES). */
-#define DCP_SCAN_TIMING_VALUES 10
+ * formatting + decoding, products.tsv, then the counts of rounds, windows scored and path passes, and of the chunks
+ * of speculated windows (cost batches begun ahead of the hits), the most windows one of them held and the path
+ * batches.  Returns how many values exist (DCP_SCAN_TIMING_VALUES). */
+#define DCP_SCAN_TIMING_VALUES 13
 int dcp_scan_last_timing(struct dcp_scan const *, double *out, int n);
 
 #ifdef __cplusplus

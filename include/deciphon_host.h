@@ -53,6 +53,25 @@ int dcp_db_partition_bounds(struct dcp_db const *, int nparts, int balanced, int
 /* the same rule on a plain array of n core sizes (core_sizes may be NULL when balanced = 0) */
 int dcp_partition_bounds_of(int n, int32_t const *core_sizes, int nparts, int balanced, int32_t *first);
 
+/* Windows of the chain of one (read, profile) pair that never hits: what dcp_window_setup / dcp_window_next
+ * walk for a read of seq_size nucleotides and a profile of core_size nodes, counted in O(1) (0 for an empty
+ * read or core_size < 1).  Returns the count. */
+int64_t dcp_window_count(int64_t seq_size, int core_size);
+/* How dcp_scan_run cuts profiles x reads into cost batches (csrc/host_logic.h dcp_plan_chunks: the rules).
+ * dcp_scan_run plans with first_cells = DCP_SCAN_FIRST_CHUNK_CELLS, later_cells = unlimited (both
+ * DECIPHON_HIP_CHUNK_CELLS when that is set), max_pairs = DCP_SCAN_CHUNK_PAIRS and max_windows =
+ * DCP_SCAN_CHUNK_WINDOWS (or DECIPHON_HIP_CHUNK_WINDOWS).
+ * Chunk i covers profiles [chunks[4i], chunks[4i+1]) x reads [chunks[4i+2], chunks[4i+3]) and holds windows[i]
+ * windows.  *nchunks receives the number of chunks; with more than cap of them nothing is written and
+ * DCP_ENOMEM is returned.  first_cells / later_cells: the DP-cell limits of the first / every later chunk;
+ * max_pairs, max_windows >= 1. */
+int dcp_scan_plan_chunks(int nprof, int32_t const *core_sizes, int nreads, int32_t const *read_lengths,
+                         double first_cells, double later_cells, int64_t max_pairs, int64_t max_windows, int cap,
+                         int32_t *chunks, int64_t *windows, int *nchunks);
+#define DCP_SCAN_FIRST_CHUNK_CELLS 1.0e10
+#define DCP_SCAN_CHUNK_PAIRS (1 << 21)
+#define DCP_SCAN_CHUNK_WINDOWS (4 << 20)
+
 /* ---- window iteration: window_setup / window_next / window_set_last_hit_position
  * (c-core/window.c:7-50) ---- */
 struct dcp_window

@@ -107,9 +107,10 @@ def test_a_table_beyond_a_strict_budget_is_a_clean_enomem(orc, monkeypatch):
 
 def test_scan_of_a_120_kb_read_cuts_windows_at_the_cap(tmp_path, orc):
     """The window chain of c-core/window.c on a read longer than the cap, through dcp_scan_run: K = 2048 (50 K = 102 400
-    > 100 000) against a 120 kb read whose first 100 000 nucleotides are the golden case's window.  Window 0 is
-    [0, 100000), the next starts where window.c:21-31 puts it after the hit; every row (window ranges, hit spans, lrt,
-    every step) equals the oracle-driven thread_run."""
+    > 100 000) against a 120 kb read whose first 100 000 nucleotides are the golden case's window and whose tail carries
+    the profile's back-translated consensus.  Window 0 is [0, 100000); window 1 starts where window.c:21-31 puts it
+    after window 0's hit and runs to the end of the read, and hits too; every row (window ranges, hit spans, lrt, every
+    step) equals the oracle-driven thread_run."""
     from dcp_testlib import oracle_scan
     from deciphon_amd import synth
     from deciphon_amd.scan import Batch, Scan, Sequence
@@ -119,6 +120,8 @@ def test_scan_of_a_120_kb_read_cuts_windows_at_the_cap(tmp_path, orc):
     _, seq, _ = build_case(c, orc)
     rng = np.random.default_rng(5)
     tail = rng.integers(0, 4, size=20000).astype(np.uint8)
+    dom = synth.back_translate(tiled_protein(c)["consensus"])
+    tail[3000 : 3000 + len(dom)] = dom  # 103 000 ... 109 144: in window 1 only
     text = "".join("ACGT"[v] for v in np.concatenate([seq, tail]))
     dcp = str(tmp_path / "k2048.dcp")
     synth.write_dcp(dcp, [tiled_protein(c)], 0.01, False, False)
@@ -134,4 +137,9 @@ def test_scan_of_a_120_kb_read_cuts_windows_at_the_cap(tmp_path, orc):
     g = np.load(os.path.join(GOLDEN, "window_cap.npz"))
     nul, alt = (np.array([g[k][0]], np.uint32).view(np.float32)[0] for k in ("null_bits", "alt_bits"))
     assert first[9] == f"{orc.lrt(-nul, -alt):.1f}"  # the reference viterbi.c's scores for that window
-    assert any(r.split("\t")[1] == "1" and int(r.split("\t")[3]) == 120000 for r in rows) or len(rows) >= 1
+    # window 1 (c-core/window.c:21-31): it starts at the later of one past window 0's last hit position (hit_stop - 1,
+    # c-core/thread.c:162) and 4 K - 1 before window 0's end, and stops at the end of the read
+    last_hit_pos = int(first[6]) - 1
+    second = [r.split("\t") for r in rows if r.split("\t")[1] == "1"]
+    assert len(rows) == len(second) + 1 == 2
+    assert second[0][2:4] == [str(max(1 + last_hit_pos, 100001 - 4 * c["K"])), "120000"]

@@ -228,3 +228,95 @@ def test_speculative_chains_with_hits_all_along_long_reads(tmp_path, orc):
         assert run_scan(str(tmp_path / "chunks"), reads, dbfile=dcp) == rows
     finally:
         del os.environ["DECIPHON_HIP_CHUNK_CELLS"]
+
+
+def long_read_case(tmp_path):
+    """Profiles tiled from minifam with K = 3 ... 173 (the K = 12 tile hits tandem copies of its consensus, the K = 3
+    one a few chance matches) and reads of 0.4 Mb carrying a planted domain every ~50 kb, with 10 kb reads of two other
+    lengths in between, so that the chains of one profile are made for one length, another, and the first again.
+    (0.4 Mb, not more: the oracle's scalar DP takes ~0.25 us a cell, and the K = 173 pair of one such read is ~20 s.)"""
+    from deciphon_amd import synth
+
+    seeds = synth.load_seeds(DCP)
+    tiles = ((30, 0), (3, 234), (173, 74), (12, 498), (124, 148), (60, 185))  # (K, offset in the ring of nodes)
+    prots = [synth.tile_protein(seeds, K, off, f"LR{K}") for K, off in tiles]
+    dcp = str(tmp_path / "long_reads.dcp")
+    synth.write_dcp(dcp, prots, 0.01, False, False)
+    rng = np.random.default_rng(1505)
+    reads = []
+    for sid, n in enumerate((400_000, 10_000, 400_000, 9_990, 380_000)):
+        x = rng.integers(0, 4, size=n).astype(np.uint8)
+        at = int(rng.integers(0, 20_000)) if n > 100_000 else n
+        while at < n - 3000:
+            p = prots[int(rng.integers(0, len(prots)))]
+            dom = synth.back_translate(p["consensus"])
+            # the K = 12 tile only hits runs of copies of its consensus
+            dom = np.concatenate([dom] * 20) if p["core_size"] < 30 else synth.mutate(dom, rng, 0.03, 0.01, 0.01)
+            dom = dom[: n - at]
+            x[at : at + len(dom)] = dom
+            at += len(dom) + int(rng.integers(40_000, 60_000))
+        reads.append((sid + 1, "".join("ACGT"[v] for v in x)))
+    return dcp, reads
+
+
+def oracle_scan_pairs(orc, db, reads, threads=16):
+    """dcp_testlib.oracle_scan with one task per (profile, read) pair, rows in the reference's order."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    tasks = [([prot], [read]) for prot in db.proteins for read in reads]
+    with ThreadPoolExecutor(max(1, min(threads, os.cpu_count() or 1))) as ex:
+        parts = list(ex.map(lambda t: dcp_testlib.oracle_scan(orc, t[0], t[1], True, False), tasks))
+    return [r for part in parts for r in part]
+
+
+def test_long_reads_split_into_capped_chunks_and_drained_path_passes(tmp_path, orc, monkeypatch):
+    """dcp_scan_run's chunk planner and path-pass drain at the sizes where they matter, scaled down by their knobs:
+    DECIPHON_HIP_CHUNK_WINDOWS = 1500 splits the K = 3 and K = 12 profiles by reads, and one K = 3 pair of a 0.4 Mb
+    read (2878 windows) is a chunk above the cap on its own; DECIPHON_HIP_PATH_DRAIN_HITS = 1 stops beginning chunks
+    whenever more than one hit waits, so the path passes run between chunks.  Every row equals the oracle-driven thread_run, the
+    scan with the default settings (one chunk, the path passes at the end) and the scan with nothing speculated."""
+    from deciphon_amd import host
+    from deciphon_amd.scan import Batch, Scan, Sequence
+
+    dcp, reads = long_read_case(tmp_path)
+    db = read_dcp(dcp)
+    batch = Batch()
+    for sid, text in reads:
+        batch.add(Sequence(sid, f"seq{sid}", text))
+
+    def scan(tag):
+        with Scan(dcp, 0, 1, True, False, False) as s:
+            s.run(str(tmp_path / tag), batch)
+            assert s.progress() == 100  # every profile counted once, at its last chunk of reads
+            rows = s.products()
+            timing = s.last_timing()
+        assert open(str(tmp_path / tag / "products.tsv")).read().splitlines()[1:] == rows
+        return rows, timing
+
+    monkeypatch.setenv("DECIPHON_HIP_CHUNK_WINDOWS", "1500")
+    monkeypatch.setenv("DECIPHON_HIP_PATH_DRAIN_HITS", "1")
+    rows, timing = scan("capped")
+    # the plan the scan ran: as dcp_scan_plan_chunks makes it, and with the cap broken by single pairs only
+    K = [p.core_size for p in db.proteins]
+    R = [len(t) for _, t in reads]
+    chunks, windows = host.plan_chunks(K, R, 1.0e10, float("inf"), 1 << 21, 1500)
+    assert timing["chunks"] == len(chunks) > 6
+    assert timing["largest_chunk_windows"] == int(windows.max()) == host.window_count(400_000, 3) > 1500
+    assert all(w <= 1500 or (c[1] - c[0] == 1 and c[3] - c[2] == 1) for c, w in zip(chunks.tolist(), windows))
+    assert sum(1 for c in chunks if c[1] - c[0] == 1 and c[3] - c[2] < len(reads)) >= 6  # K = 3 and 12 by reads
+    assert timing["path_passes"] >= len(rows)
+    want = oracle_scan_pairs(orc, db, reads)
+    assert rows == want
+    assert len(rows) >= 40 and len({r.split("\t")[7] for r in rows}) == 6
+    # hits of the profiles split by reads in chunks that start past read 0 (K = 3: reads 4..4, K = 12: 4..4) or
+    # hold several reads (K = 12: reads 0..3)
+    assert {("5", "LR3"), ("3", "LR12"), ("5", "LR12")} <= {(r.split("\t")[0], r.split("\t")[7]) for r in rows}
+    monkeypatch.delenv("DECIPHON_HIP_CHUNK_WINDOWS")
+    monkeypatch.delenv("DECIPHON_HIP_PATH_DRAIN_HITS")
+    default_rows, default_timing = scan("default")
+    assert default_rows == rows
+    assert default_timing["chunks"] == 1 and default_timing["largest_chunk_windows"] == int(windows.sum())
+    # the drained scan ran its path passes between chunks: in more batches than the one that ran them at the end
+    assert timing["path_batches"] > default_timing["path_batches"] >= 1
+    monkeypatch.setenv("DECIPHON_HIP_SPECULATE", "0")
+    assert run_scan(str(tmp_path / "rounds"), reads, dbfile=dcp) == rows
