@@ -278,6 +278,14 @@ struct dcp_hip
   int staged_pg_begin[DCP_NUM_PACK_SHAPES + 1] = {0};
   double staged_cells = 0;
   int staged_n = -1;
+  bool staged_ran = false; // a dcp_hip_run_staged with reps > 0 has filled d_out since the dcp_hip_stage
+
+  // Input generation: moves with every accepted change of the profiles, sequences, mode or xtrans override.  The
+  // staged list and the path results remember the generation they were made under; dcp_hip_run_staged /
+  // _fetch_staged and dcp_hip_path_trellis (which recomputes) refuse once it has moved.
+  uint64_t gen = 0;
+  uint64_t staged_gen = 0;
+  uint64_t path_gen = UINT64_MAX; // UINT64_MAX: the last dcp_hip_path failed or there was none
 };
 
 #define BK(x) ((x)->bank[(x)->cur])
@@ -585,7 +593,7 @@ int stage(dcp_hip *x, int n, dcp_hip_window const *w, ArenaKind arena_kind, Stag
     HIP_TRY(x, BK(x).d_ring.reserve((size_t)DCP_RING_SLOTS * DCP_RING_FLOATS), DCP_ENOMEM);
   int rc = ensure_xt(x, max_s + 1);
   if (rc) return rc;
-  x->staged_n = -1; // the device problem list is about to be replaced
+  if (x->cur != 2) x->staged_n = -1; // a cost bank's problem list and results are about to be replaced
   // every allocation first: after the first copy is enqueued nothing below can fail but a copy itself
   HIP_TRY(x, BK(x).d_problems.reserve((size_t)std::max(nu, 1)), DCP_ENOMEM);
   if (!st.packs.empty()) HIP_TRY(x, BK(x).d_packs.reserve(st.packs.size()), DCP_ENOMEM);
@@ -812,6 +820,11 @@ struct PathContext
 // batches begun and not ended
 int outstanding_batches(dcp_hip const *x) { return (x->outstanding[0] >= 0) + (x->outstanding[1] >= 0); }
 
+int refuse_outstanding(dcp_hip *x)
+{
+  return fail(x, DCP_EFUNCUSE, "cost batches are outstanding (dcp_hip_cost_hits_begin): end them first");
+}
+
 } // namespace
 
 extern "C" {
@@ -989,6 +1002,7 @@ static int push_profile(dcp_hip *x, HostProfile hp, std::vector<float> const &st
   x->pool_used += staged.size();
   if (index) *index = (int)x->profiles.size();
   x->profiles.push_back(hp);
+  ++x->gen;
   return 0;
 }
 
@@ -1062,7 +1076,11 @@ int dcp_hip_load_dcp(struct dcp_hip *x, char const *path, int first, int count)
   if (first < 0 || first > N) return fail(x, DCP_EINVALPART, "first protein out of range");
   int const last = count < 0 ? N : std::min(N, first + count);
   int const n = last - first;
-  if (n <= 0) return 0;
+  if (n <= 0)
+  {
+    ++x->gen; // nothing to read, but a successful load ends what was computed before it, as every other does
+    return 0;
+  }
 
   std::vector<HostProfile> hps((size_t)n);
   std::vector<size_t> off((size_t)n + 1, 0);
@@ -1175,6 +1193,7 @@ int dcp_hip_load_dcp(struct dcp_hip *x, char const *path, int first, int count)
     x->profiles.push_back(hps[(size_t)i]);
   }
   x->pool_used += off[(size_t)n];
+  ++x->gen;
   return 0;
 }
 
@@ -1201,6 +1220,7 @@ int dcp_hip_commit_profiles(struct dcp_hip *x)
   if (!x) return DCP_EFUNCUSE;
   if (outstanding_batches(x)) return fail(x, DCP_EFUNCUSE, "cost batches are outstanding (dcp_hip_cost_hits_begin): end them first");
   HIP_TRY(x, hipSetDevice(x->device), DCP_EFUNCUSE);
+  ++x->gen; // even when there is nothing new to publish (the header: every accepted commit)
   if (x->committed == x->profiles.size()) return 0;
   // the tables are already in HBM; what is published here are the profile descriptors
   HIP_TRY(x, hipStreamSynchronize(x->stream), DCP_EFUNCUSE);
@@ -1228,6 +1248,12 @@ int dcp_hip_commit_profiles(struct dcp_hip *x)
 void dcp_hip_clear_profiles(struct dcp_hip *x)
 {
   if (!x) return;
+  if (outstanding_batches(x))
+  {
+    (void)refuse_outstanding(x); // void in the ABI: the refusal shows in dcp_hip_strerror and num_profiles
+    return;
+  }
+  ++x->gen;
   x->pool_used = 0;
   x->profiles.clear();
   x->committed = 0;
@@ -1244,22 +1270,25 @@ int dcp_hip_set_sequences(struct dcp_hip *x, int nseq, uint8_t const *nt, int64_
   if (!x || nseq < 0 || !offsets || (nseq > 0 && !nt)) return DCP_EFUNCUSE;
   if (outstanding_batches(x)) return fail(x, DCP_EFUNCUSE, "cost batches are outstanding (dcp_hip_cost_hits_begin): end them first");
   HIP_TRY(x, hipSetDevice(x->device), DCP_EFUNCUSE);
-  x->seq_off.assign(offsets, offsets + nseq + 1);
-  x->row_off.resize((size_t)nseq + 1);
+  // everything is checked before anything is replaced: a refused call leaves the previous reads in force
+  std::vector<int64_t> row_off((size_t)nseq + 1);
   int64_t max_len = 0, rows = 0;
-  if (x->seq_off[0] != 0) return fail(x, DCP_EFUNCUSE, "offsets[0] must be 0");
+  if (offsets[0] != 0) return fail(x, DCP_EFUNCUSE, "offsets[0] must be 0");
   for (int i = 0; i < nseq; ++i)
   {
-    int64_t len = x->seq_off[(size_t)i + 1] - x->seq_off[(size_t)i];
+    int64_t len = offsets[i + 1] - offsets[i];
     if (len < 0) return fail(x, DCP_EFUNCUSE, "offsets must not decrease");
     max_len = std::max(max_len, len);
-    x->row_off[(size_t)i] = rows;
+    row_off[(size_t)i] = rows;
     rows += len + 1;
   }
-  x->row_off[(size_t)nseq] = rows;
-  int64_t const total = x->seq_off[(size_t)nseq];
+  row_off[(size_t)nseq] = rows;
+  int64_t const total = offsets[nseq];
   for (int64_t i = 0; i < total; ++i)
     if (nt[i] > 3) return fail(x, DCP_ESEQABC, "nucleotide index above 3");
+  ++x->gen;
+  x->seq_off.assign(offsets, offsets + nseq + 1);
+  x->row_off = std::move(row_off);
   HIP_TRY(x, hipStreamSynchronize(x->stream), DCP_EFUNCUSE);
   HIP_TRY(x, x->d_nt.reserve((size_t)std::max<int64_t>(total, 1)), DCP_ENOMEM);
   HIP_TRY(x, x->d_seq_off.reserve((size_t)nseq + 1), DCP_ENOMEM);
@@ -1284,6 +1313,7 @@ int dcp_hip_set_mode(struct dcp_hip *x, int multi_hits, int hmmer3_compat)
   if (!x) return DCP_EFUNCUSE;
   if (outstanding_batches(x)) return fail(x, DCP_EFUNCUSE, "cost batches are outstanding (dcp_hip_cost_hits_begin): end them first");
   bool mh = multi_hits != 0, h3 = hmmer3_compat != 0;
+  ++x->gen;
   if (x->mode_set && (mh != x->multi_hits || h3 != x->hmmer3_compat)) x->xt_rows = 0;
   x->multi_hits = mh;
   x->hmmer3_compat = h3;
@@ -1295,6 +1325,7 @@ int dcp_hip_set_xtrans_table(struct dcp_hip *x, int rows, float const *xt)
 {
   if (!x || rows < 0 || (rows > 0 && !xt)) return DCP_EFUNCUSE;
   if (outstanding_batches(x)) return fail(x, DCP_EFUNCUSE, "cost batches are outstanding (dcp_hip_cost_hits_begin): end them first");
+  ++x->gen;
   x->xt_override.assign((size_t)rows * DCP_XT_STRIDE, 0.0f);
   for (int r = 0; r < rows; ++r)
     memcpy(x->xt_override.data() + (size_t)r * DCP_XT_STRIDE, xt + (size_t)r * DCP_NUM_XTRANS,
@@ -1311,6 +1342,7 @@ void dcp_hip_xtrans(int seq_size, int multi_hits, int hmmer3_compat, float xt[DC
 int dcp_hip_cost(struct dcp_hip *x, int n, struct dcp_hip_window const *w, float *null_cost, float *alt_cost)
 {
   if (!x || (n > 0 && (!null_cost || !alt_cost))) return DCP_EFUNCUSE;
+  if (outstanding_batches(x)) return refuse_outstanding(x);
   HIP_TRY(x, hipSetDevice(x->device), DCP_EFUNCUSE);
   bool const timing = getenv("DECIPHON_HIP_TIMING") != nullptr && n > 1000;
   auto const t0 = std::chrono::steady_clock::now();
@@ -1440,6 +1472,7 @@ int dcp_hip_cost_bench(struct dcp_hip *x, int n, struct dcp_hip_window const *w,
                        double *cells, float *null_cost, float *alt_cost)
 {
   if (!x || n <= 0 || reps <= 0 || !ms || !cells) return DCP_EFUNCUSE;
+  if (outstanding_batches(x)) return refuse_outstanding(x);
   HIP_TRY(x, hipSetDevice(x->device), DCP_EFUNCUSE);
   Staged st;
   int rc = stage(x, n, w, ARENA_NONE, st);
@@ -1476,9 +1509,22 @@ int dcp_hip_cost_bench(struct dcp_hip *x, int n, struct dcp_hip_window const *w,
   return 0;
 }
 
+// what dcp_hip_run_staged and dcp_hip_fetch_staged need: no batch in flight, a list, and the inputs it was staged under
+static int check_staged(dcp_hip *x)
+{
+  if (outstanding_batches(x)) return refuse_outstanding(x);
+  if (x->staged_n <= 0) return fail(x, DCP_EFUNCUSE, "nothing staged (dcp_hip_stage; a cost call since replaces the list)");
+  if (x->staged_gen != x->gen)
+    return fail(x, DCP_EFUNCUSE, "the profiles, sequences, mode or xtrans table changed since dcp_hip_stage: stage again");
+  return 0;
+}
+
 int dcp_hip_stage(struct dcp_hip *x, int n, struct dcp_hip_window const *w)
 {
-  if (!x || n <= 0) return DCP_EFUNCUSE;
+  if (!x) return DCP_EFUNCUSE;
+  if (outstanding_batches(x)) return refuse_outstanding(x);
+  x->staged_n = -1; // a failed stage leaves no list behind
+  if (n <= 0) return fail(x, DCP_EFUNCUSE, "dcp_hip_stage needs at least one window");
   HIP_TRY(x, hipSetDevice(x->device), DCP_EFUNCUSE);
   Staged st;
   int rc = stage(x, n, w, ARENA_NONE, st);
@@ -1491,12 +1537,16 @@ int dcp_hip_stage(struct dcp_hip *x, int n, struct dcp_hip_window const *w)
   memcpy(x->staged_pg_begin, st.pg_begin, sizeof(st.pg_begin));
   x->staged_cells = st.cells;
   x->staged_n = n;
+  x->staged_ran = false;
+  x->staged_gen = x->gen;
   return 0;
 }
 
 int dcp_hip_run_staged(struct dcp_hip *x, int reps, float *ms, double *cells)
 {
-  if (!x || x->staged_n <= 0 || reps < 0) return DCP_EFUNCUSE;
+  if (!x || reps < 0) return DCP_EFUNCUSE;
+  int rc = check_staged(x);
+  if (rc) return rc;
   HIP_TRY(x, hipSetDevice(x->device), DCP_EFUNCUSE);
   Staged st;
   memcpy(st.c_begin, x->staged_c_begin, sizeof(st.c_begin));
@@ -1511,7 +1561,6 @@ int dcp_hip_run_staged(struct dcp_hip *x, int reps, float *ms, double *cells)
   // the batches of a scan do (dcp_hip_cost_hits_begin while another batch is in flight), kernel class by kernel class --
   // measured no faster on the bench's 0.4 s steps (profiles/r03_scan_pipeline.txt)
   char const *join_env = getenv("DECIPHON_HIP_STEP_JOIN");
-  int rc = 0;
   if (join_env && join_env[0] == '0' && reps > 0)
     rc = launch_cost_all(x, st, nullptr, reps);
   else
@@ -1525,12 +1574,16 @@ int dcp_hip_run_staged(struct dcp_hip *x, int reps, float *ms, double *cells)
   (void)hipEventDestroy(e1);
   if (ms) *ms = total;
   if (cells) *cells = x->staged_cells;
+  if (reps > 0) x->staged_ran = true;
   return 0;
 }
 
 int dcp_hip_fetch_staged(struct dcp_hip *x, float *null_cost, float *alt_cost)
 {
-  if (!x || x->staged_n <= 0 || !null_cost || !alt_cost) return DCP_EFUNCUSE;
+  if (!x || !null_cost || !alt_cost) return DCP_EFUNCUSE;
+  int rc = check_staged(x);
+  if (rc) return rc;
+  if (!x->staged_ran) return fail(x, DCP_EFUNCUSE, "dcp_hip_run_staged has not run the staged list yet");
   size_t const n = (size_t)x->staged_n;
   std::vector<float> out(2 * n);
   HIP_TRY(x, hipMemcpyAsync(out.data(), BK(x).d_out.p, out.size() * sizeof(float), hipMemcpyDeviceToHost, x->stream),
@@ -1912,18 +1965,15 @@ size_t path_budget(dcp_hip *x)
 
 extern "C" {
 
-int dcp_hip_path(struct dcp_hip *x, int n, struct dcp_hip_window const *w)
+} // extern "C"
+
+namespace
 {
-  if (!x || n < 0 || (n > 0 && !w)) return DCP_EFUNCUSE;
+
+int path_run(dcp_hip *x, int n, dcp_hip_window const *w)
+{
   HIP_TRY(x, hipSetDevice(x->device), DCP_EFUNCUSE);
   PathContext ctx(x); // its own window lists, result buffers and streams: cost batches may be in flight
-  x->h_steps_used = 0;
-  x->paths.clear();
-  x->path_wins.assign(w, w + n);
-  x->paths.resize((size_t)n);
-  x->host_trellis.assign((size_t)n, std::vector<unsigned char>());
-  if (n == 0) return 0;
-  std::vector<int> redo;
   // every window is checked here, whichever pass takes it (path_literal indexes x->profiles before stage() looks)
   int const nseq = (int)x->seq_off.size() - 1;
   for (int i = 0; i < n; ++i)
@@ -1933,6 +1983,11 @@ int dcp_hip_path(struct dcp_hip *x, int n, struct dcp_hip_window const *w)
     int64_t const len = x->seq_off[(size_t)w[i].seq + 1] - x->seq_off[(size_t)w[i].seq];
     if (w[i].start < 0 || w[i].stop < w[i].start || w[i].stop > len) return fail(x, DCP_EFUNCUSE, "bad window range");
   }
+  x->path_wins.assign(w, w + n);
+  x->paths.resize((size_t)n);
+  x->host_trellis.assign((size_t)n, std::vector<unsigned char>());
+  if (n == 0) return 0;
+  std::vector<int> redo;
   char const *mode = getenv("DECIPHON_HIP_PATH"); // "literal": skip the fast pass (tests, debugging)
   if (mode && strcmp(mode, "literal") == 0)
     for (int i = 0; i < n; ++i) redo.push_back(i);
@@ -2008,6 +2063,31 @@ int dcp_hip_path(struct dcp_hip *x, int n, struct dcp_hip_window const *w)
   return path_literal(x, redo);
 }
 
+} // namespace
+
+extern "C" {
+
+int dcp_hip_path(struct dcp_hip *x, int n, struct dcp_hip_window const *w)
+{
+  if (!x || n < 0 || (n > 0 && !w)) return DCP_EFUNCUSE;
+  // the previous results end here, whether or not this call succeeds; a failed call leaves none
+  x->path_gen = UINT64_MAX;
+  x->h_steps_used = 0;
+  x->paths.clear();
+  x->path_wins.clear();
+  x->host_trellis.clear();
+  int const rc = path_run(x, n, w);
+  if (rc)
+  {
+    x->paths.clear();
+    x->path_wins.clear();
+    x->host_trellis.clear();
+    return rc;
+  }
+  x->path_gen = x->gen;
+  return 0;
+}
+
 int dcp_hip_path_reserve(struct dcp_hip *x, int64_t bytes)
 {
   if (!x || bytes < 0) return DCP_EFUNCUSE;
@@ -2062,6 +2142,11 @@ int dcp_hip_path_trellis(struct dcp_hip const *cx, int i, uint32_t const **xnode
 {
   dcp_hip *x = const_cast<dcp_hip *>(cx);
   if (!x || i < 0 || i >= (int)x->paths.size() || !xnodes || !nodes) return DCP_EFUNCUSE;
+  // the trellis is (re)computed from the engine's inputs: they must still be those of the dcp_hip_path
+  if (x->path_gen != x->gen)
+    return fail(x, DCP_EFUNCUSE, x->path_gen == UINT64_MAX ? "the last dcp_hip_path failed"
+                                                            : "the profiles, sequences, mode or xtrans table changed since "
+                                                              "dcp_hip_path: call it again");
   HIP_TRY(x, hipSetDevice(x->device), DCP_EFUNCUSE);
   PathContext ctx(x);
   if (!x->paths[(size_t)i].has_trellis)

@@ -138,6 +138,8 @@ class Engine:
             raise HipError(8, f"no usable HIP device {device}; there is no CPU fallback")
         self.device = int(device)
         self._seq_lens = []
+        self._staged_n = 0
+        self._path_shape = []
 
     def close(self):
         if getattr(self, "h", None):
@@ -204,7 +206,11 @@ class Engine:
         self._check(self.lib.dcp_hip_commit_profiles(self.h))
 
     def clear_profiles(self) -> None:
+        """Drops every profile.  The C call returns no code: while cost batches are outstanding it does nothing, which
+        shows here as DCP_EFUNCUSE."""
         self.lib.dcp_hip_clear_profiles(self.h)
+        if getattr(self, "_pending", None) or self.num_profiles:
+            raise HipError(8, self.lib.dcp_hip_strerror(self.h).decode())
 
     # ---- sequences ------------------------------------------------------------
     def set_sequences(self, seqs) -> None:
@@ -286,8 +292,8 @@ class Engine:
     def stage(self, windows) -> None:
         """Copies the window list to HBM for run_staged() (measurement)."""
         n, arr = self._windows(windows)
-        self._staged_n = n
         self._check(self.lib.dcp_hip_stage(self.h, n, arr))
+        self._staged_n = n  # only once staged: fetch_staged sizes its buffers by it
 
     def run_staged(self, reps: int):
         """-> (HIP-event ms of `reps` cost-pass launches together, DP cells of one launch)."""
@@ -297,6 +303,7 @@ class Engine:
         return ms.value, cells.value
 
     def fetch_staged(self):
+        """-> (null_cost, alt_cost) of the last run_staged(reps > 0) over the staged list."""
         nul = np.zeros(self._staged_n, dtype=np.float32)
         alt = np.zeros(self._staged_n, dtype=np.float32)
         self._check(self.lib.dcp_hip_fetch_staged(self.h, _p(nul), _p(alt)))
@@ -319,7 +326,14 @@ class Engine:
         The steps are read first (they come from the fast pass); trellis=True then asks for the
         packed back-pointers too, which makes the library run the literal pass for the batch."""
         n, arr = self._windows(windows)
+        self._path_shape = []
         self._check(self.lib.dcp_hip_path(self.h, n, arr))
+        # (K, L) of every window now: path_trellis() sizes its arrays by them whatever has changed since
+        if isinstance(windows, np.ndarray):  # arr is then a bare pointer to the int32 [n][4] array
+            w4 = np.asarray(windows, dtype=np.int32).reshape(-1, 4)
+            self._path_shape = [(self.core_size(int(p)), int(b) - int(a)) for p, _, a, b in w4]
+        else:
+            self._path_shape = [(self.core_size(arr[i].profile), arr[i].stop - arr[i].start) for i in range(n)]
         self.path_redone = self.lib.dcp_hip_path_redone(self.h)
         out = []
         for i in range(n):
@@ -331,16 +345,7 @@ class Engine:
         if not trellis:
             return out
         for i in range(n):
-            xn, nd = C.c_void_p(), C.c_void_p()
-            self._check(self.lib.dcp_hip_path_trellis(self.h, i, C.byref(xn), C.byref(nd)))
-            if isinstance(windows, np.ndarray):  # arr is then a bare pointer to the int32 [n][4] array
-                prof, _, start, stop = (int(v) for v in np.asarray(windows, dtype=np.int32).reshape(-1, 4)[i])
-            else:
-                prof, start, stop = arr[i].profile, arr[i].start, arr[i].stop
-            L = stop - start
-            K = self.core_size(prof)
-            out[i]["xnodes"] = np.ctypeslib.as_array(C.cast(xn, C.POINTER(C.c_uint32)), shape=(L + 1,)).copy()
-            out[i]["nodes"] = np.ctypeslib.as_array(C.cast(nd, C.POINTER(C.c_uint16)), shape=((L + 1) * K,)).copy()
+            out[i]["xnodes"], out[i]["nodes"] = self.path_trellis(i)
             # the literal pass has replaced the steps: they must be the very same path
             ns = self.lib.dcp_hip_path_nsteps(self.h, i)
             ids = np.zeros(ns, dtype=np.int32)
@@ -349,3 +354,14 @@ class Engine:
             out[i]["literal_state_ids"], out[i]["literal_seqsizes"] = ids, sizes
             out[i]["literal_score"] = np.float32(self.lib.dcp_hip_path_score(self.h, i))
         return out
+
+    def path_trellis(self, i: int):
+        """-> (xnodes[L+1], nodes[(L+1)*K]) of window i of the last path(), copied; K and L as they were at that call.
+        Any time after path(..., trellis=False); the library refuses (DCP_EFUNCUSE) once the profiles, sequences, mode
+        or xtrans table have changed since."""
+        xn, nd = C.c_void_p(), C.c_void_p()
+        self._check(self.lib.dcp_hip_path_trellis(self.h, i, C.byref(xn), C.byref(nd)))
+        K, L = self._path_shape[i]
+        xnodes = np.ctypeslib.as_array(C.cast(xn, C.POINTER(C.c_uint32)), shape=(L + 1,)).copy()
+        nodes = np.ctypeslib.as_array(C.cast(nd, C.POINTER(C.c_uint16)), shape=((L + 1) * K,)).copy()
+        return xnodes, nodes

@@ -69,6 +69,8 @@ int dcp_hip_profile_core_size(struct dcp_hip const *, int index);
 char const *dcp_hip_profile_accession(struct dcp_hip const *, int index);
 /* Uploads everything added so far to HBM (idempotent). */
 int dcp_hip_commit_profiles(struct dcp_hip *);
+/* Drops every profile.  While cost batches are outstanding it does nothing (the profiles stay, num_profiles
+ * included) and leaves the reason in dcp_hip_strerror: the function returns no code. */
 void dcp_hip_clear_profiles(struct dcp_hip *);
 
 /* ---- sequences (replaces batch_encode -> sequence_encode, c-core/batch.c:60-70) ----
@@ -92,7 +94,15 @@ void dcp_hip_xtrans(int seq_size, int multi_hits, int hmmer3_compat, float xt[DC
 
 /* ---- the DP ---------------------------------------------------------------------------
  * A window is the half-open range [start, stop) of sequence `seq` scored against
- * `profile`, i.e. one process_window call (c-core/thread.c:98-128). */
+ * `profile`, i.e. one process_window call (c-core/thread.c:98-128).
+ *
+ * The inputs: every accepted call of dcp_hip_add_profile, _add_protein, _load_dcp, _commit_profiles,
+ * _clear_profiles, _set_sequences, _set_mode or _set_xtrans_table changes them, even one that sets what was
+ * there already (a call refused for outstanding batches or for its arguments changes nothing).  Two things
+ * outlive a call and are tied to the inputs they were made from: the staged window list (dcp_hip_stage) and the
+ * trellis of the last dcp_hip_path, which is computed only when asked for.  Once the inputs have changed,
+ * dcp_hip_run_staged, dcp_hip_fetch_staged and dcp_hip_path_trellis are DCP_EFUNCUSE until dcp_hip_stage /
+ * dcp_hip_path is called again. */
 struct dcp_hip_window
 {
   int32_t profile;
@@ -114,13 +124,17 @@ int dcp_hip_cost_hits(struct dcp_hip *, int n, struct dcp_hip_window const *, in
 /* The same in two halves: _begin stages the windows and enqueues the kernels and returns while the GPU works;
  * _end waits for the OLDEST batch begun and delivers what dcp_hip_cost_hits would have.  Two batches may be
  * outstanding per engine (the second queues behind the first, so the GPU does not drain between them); a third
- * _begin is a DCP_EFUNCUSE.  While batches are outstanding the engine accepts only _begin, _end, the read-only
- * queries and dcp_hip_path (which has buffers and streams of its own); everything else is a DCP_EFUNCUSE. */
+ * _begin is a DCP_EFUNCUSE.  While batches are outstanding -- in either buffer set, whichever began first -- the
+ * engine accepts only _begin, _end, the read-only queries, dcp_hip_path, dcp_hip_path_trellis and
+ * dcp_hip_path_reserve (the path pass has buffers and streams of its own); everything else is a DCP_EFUNCUSE, and
+ * dcp_hip_clear_profiles does nothing (see there). */
 int dcp_hip_cost_hits_begin(struct dcp_hip *, int n, struct dcp_hip_window const *);
 int dcp_hip_cost_hits_end(struct dcp_hip *, int *nhits, int32_t *hit_window, float *hit_lrt);
 
-/* viterbi_path + trellis_unzip for n windows (c-core/thread.c:124-126).  Results
- * stay valid until the next dcp_hip_path / dcp_hip_del.
+/* viterbi_path + trellis_unzip for n windows (c-core/thread.c:124-126).  The steps and scores
+ * (dcp_hip_path_nsteps, _steps, _steps_packed, _score) stay valid until the next dcp_hip_path /
+ * dcp_hip_del, whatever is called between: they are host copies.  A dcp_hip_path that fails leaves
+ * no results (nsteps -1, trellis DCP_EFUNCUSE).
  * The steps come from a fast pass (cost pass with the DP values kept in HBM + a traceback
  * that picks, at every visited state, the first candidate equal to the stored minimum --
  * the reference's strict-< rule); windows in which that meets an exact fp32 tie only the
@@ -145,7 +159,10 @@ int dcp_hip_path_steps(struct dcp_hip const *, int i, int32_t *state_ids, int32_
  * state id in the low 16 bits, emission length in the high -- valid until the next dcp_hip_path / dcp_hip_del
  * (what struct imm_step carries apart from the score, c-core/trellis.c:147-167). */
 int dcp_hip_path_steps_packed(struct dcp_hip const *, int i, uint32_t const **steps, int32_t *nsteps);
-/* the packed back-pointers themselves: xnodes[L+1], nodes[(L+1)*K] (c-core/trellis.h:12-21) */
+/* the packed back-pointers themselves: xnodes[L+1], nodes[(L+1)*K] (c-core/trellis.h:12-21), L and K of the
+ * window and its profile as they were at the dcp_hip_path.  DCP_EFUNCUSE, with the steps left as they are, once
+ * the inputs have changed since that dcp_hip_path (see "the inputs" above).  Allowed while cost batches are
+ * outstanding; the cost calls and the staged list do not touch it. */
 int dcp_hip_path_trellis(struct dcp_hip const *, int i, uint32_t const **xnodes, uint16_t const **nodes);
 /* score of the path pass's own DP (equals alt_cost of dcp_hip_cost) */
 float dcp_hip_path_score(struct dcp_hip const *, int i);
@@ -160,7 +177,12 @@ int dcp_hip_cost_bench(struct dcp_hip *, int n, struct dcp_hip_window const *, i
 /* The same in two steps: dcp_hip_stage copies the window list to HBM (untimed);
  * dcp_hip_run_staged launches the cost pass `reps` times over it and returns when the
  * last launch has finished; *ms = HIP-event time of all `reps` launches together,
- * *cells = DP cells of ONE launch.  dcp_hip_fetch_staged copies the scores back. */
+ * *cells = DP cells of ONE launch.  dcp_hip_fetch_staged copies back the scores of the last
+ * dcp_hip_run_staged with reps > 0 (DCP_EFUNCUSE before there is one).  Both may be called any
+ * number of times over one staged list.  The list ends with a dcp_hip_stage that fails, and with
+ * any dcp_hip_cost, _cost_hits, _cost_hits_begin or _cost_bench that gets past checking its
+ * windows (they reuse its buffers); dcp_hip_path and dcp_hip_path_trellis leave it.  After a change
+ * of the inputs (see "the inputs" above) both are DCP_EFUNCUSE until the list is staged again. */
 int dcp_hip_stage(struct dcp_hip *, int n, struct dcp_hip_window const *);
 int dcp_hip_run_staged(struct dcp_hip *, int reps, float *ms, double *cells);
 int dcp_hip_fetch_staged(struct dcp_hip *, float *null_cost, float *alt_cost);

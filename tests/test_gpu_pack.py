@@ -235,6 +235,9 @@ def test_two_cost_batches_in_flight_and_a_path_pass_between(orc):
         paths = eng.path([tuple(int(v) for v in small[3])], trellis=False)  # allowed: its own buffers and streams
         t0 = time.perf_counter()
         got_small = eng.cost_hits_end()
+        with pytest.raises(deciphon_amd.HipError) as e:
+            eng.cost(small)  # the second batch, in the other buffer set, is still outstanding: refused too
+        assert e.value.code == 8
         got_big = eng.cost_hits_end()
         waited = time.perf_counter() - t0
         with pytest.raises(deciphon_amd.HipError):
