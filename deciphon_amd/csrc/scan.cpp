@@ -80,11 +80,6 @@ struct dcp_scan
   std::vector<std::shared_ptr<LazyDecoder>> decoders; // by local profile
 };
 
-struct dcp_press
-{
-  int unused;
-};
-
 namespace
 {
 
@@ -945,15 +940,5 @@ void dcp_batch_reset(struct dcp_batch *x)
 {
   if (x) x->seqs.clear();
 }
-
-// ---- press: not provided (needs third-party imm + hmmer_reader) ----------------
-struct dcp_press *dcp_press_new(void) { return new (std::nothrow) dcp_press; }
-int dcp_press_setup(struct dcp_press *, int, float) { return raise(DCP_EFUNCUSE, __func__, "press is not part of this build"); }
-int dcp_press_open(struct dcp_press *, char const *, char const *) { return raise(DCP_EFUNCUSE, __func__, "press is not part of this build"); }
-long dcp_press_nproteins(struct dcp_press const *) { return 0; }
-int dcp_press_next(struct dcp_press *) { return raise(DCP_EFUNCUSE, __func__, "press is not part of this build"); }
-bool dcp_press_end(struct dcp_press const *) { return true; }
-int dcp_press_close(struct dcp_press *) { return 0; }
-void dcp_press_del(struct dcp_press const *x) { delete const_cast<dcp_press *>(x); }
 
 } // extern "C"

@@ -56,8 +56,77 @@ def _lib():
     L.dcp_state_is_mute_id.argtypes = [i32]
     L.dcp_lrt_of.argtypes = [C.c_float, C.c_float]
     L.dcp_lrt_of.restype = C.c_float
+    L.dcp_hmm_open.argtypes = [C.c_char_p, i32, C.POINTER(vp)]
+    L.dcp_hmm_close.argtypes = [vp]
+    L.dcp_hmm_close.restype = None
+    L.dcp_hmm_count.argtypes = [vp]
+    L.dcp_hmm_count.restype = C.c_long
+    L.dcp_hmm_next.argtypes = [vp]
+    L.dcp_hmm_end.argtypes = [vp]
+    L.dcp_hmm_core_size.argtypes = [vp]
+    L.dcp_hmm_has_ga.argtypes = [vp]
+    L.dcp_hmm_read.argtypes = [vp, vp, vp, vp, vp, C.c_char_p, C.c_char_p]
     L._host_ready = True
     return L
+
+
+class HmmFile:
+    """A HMMER3 text file read as press reads it (include/deciphon_host.h dcp_hmm_*): iterating yields one dict per
+    profile with accession, consensus, core_size, has_ga, trans[(K+1), 7], BMk[K], and nucltp[(K+3), 4] /
+    codonm[(K+3), 125] (0 = null, 1 = background, 2 + n = node n) -- the fields press writes, emission tables
+    aside.  Host code only: no GPU is needed."""
+
+    def __init__(self, path: str, gencode: int = 1):
+        self.lib = _lib()
+        h = C.c_void_p()
+        rc = self.lib.dcp_hmm_open(os.fsencode(path), int(gencode), C.byref(h))
+        if rc:
+            raise HipError(rc, path)
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.dcp_hmm_close(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *_):
+        self.close()
+
+    def __len__(self):
+        """press.c count_proteins: the HMMER3/f lines of the file."""
+        return int(self.lib.dcp_hmm_count(self.h))
+
+    def next(self):
+        """The next profile, or None at the end of the file; raises HipError on a malformed profile."""
+        if rc := self.lib.dcp_hmm_next(self.h):
+            raise HipError(rc)
+        if self.lib.dcp_hmm_end(self.h):
+            return None
+        K = self.lib.dcp_hmm_core_size(self.h)
+        trans = np.zeros((K + 1, 7), np.float32)
+        BMk = np.zeros(K, np.float32)
+        nucltp = np.zeros((K + 3, 4), np.float32)
+        codonm = np.zeros((K + 3, 125), np.float32)
+        acc = C.create_string_buffer(32)
+        cons = C.create_string_buffer(K + 1)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        if rc := self.lib.dcp_hmm_read(self.h, p(trans), p(BMk), p(nucltp), p(codonm), acc, cons):
+            raise HipError(rc)
+        return dict(accession=acc.value.decode(), consensus=cons.value.decode(), core_size=K,
+                    has_ga=bool(self.lib.dcp_hmm_has_ga(self.h)), trans=trans, BMk=BMk, nucltp=nucltp, codonm=codonm)
+
+    def __iter__(self):
+        while (p := self.next()) is not None:
+            yield p
 
 
 class Database:

@@ -286,3 +286,78 @@ def iter_pfam_like(seeds, n: int, seed: int, first: int = 0, lengths=None):
     for j, K in enumerate(Ks):
         i = first + j
         yield resample_protein(seeds, int(K), np.random.default_rng([seed, i]), f"SY{i:05d}.1")
+
+
+# ---- HMMER3 text (the input of press) --------------------------------------------------------
+
+_HMM_HEAD = ("HMM          A        C        D        E        F        G        H        I        K        L        M"
+             "        N        P        Q        R        S        T        V        W        Y   \n"
+             "            m->m     m->i     m->d     i->m     i->i     d->m     d->d\n")
+
+
+def load_hmm_seeds(path: str):
+    """The profiles of a HMMER3/f text file as text: per profile its COMPO block (3 lines) and, per node, the 20
+    match values, the annotation columns, the insert line and the transition line -- what the synthetic files below
+    are resampled from, value for value."""
+    profiles, cur, lines = [], None, open(path).read().splitlines()
+    i = 0
+    while i < len(lines):
+        t = lines[i].split()
+        if t and t[0] == "COMPO":
+            cur = dict(compo=lines[i : i + 3], nodes=[])
+            i += 3
+            continue
+        if cur is not None and t and t[0] == "//":
+            profiles.append(cur)
+            cur = None
+        elif cur is not None and t and t[0].isdigit() and len(t) >= 23:
+            cur["nodes"].append(dict(match=t[1:21], tail=t[21:], insert=lines[i + 1], trans=lines[i + 2]))
+            i += 3
+            continue
+        i += 1
+    return profiles
+
+
+def resample_hmm(seeds, K: int, rng, accession: str, mean_run: int = 30, ga: bool = True) -> dict:
+    """A profile of K nodes made of runs of consecutive interior nodes of the seed profiles; the last node's
+    transitions are those of a seed's last node (MD, DD impossible), as in any HMMER3 file."""
+    nodes = []
+    while len(nodes) < K:
+        s = seeds[int(rng.integers(0, len(seeds)))]["nodes"]
+        run = int(min(rng.geometric(1.0 / mean_run), K - len(nodes), max(len(s) - 2, 1)))
+        i0 = int(rng.integers(0, max(len(s) - 1 - run, 0) + 1))
+        nodes += [dict(n) for n in s[i0 : i0 + run]]
+    nodes[-1]["trans"] = seeds[0]["nodes"][-1]["trans"]
+    return dict(accession=accession, name=f"SYN_{accession}", compo=seeds[0]["compo"], nodes=nodes, ga=ga)
+
+
+def pfam_like_hmms(seeds, n: int, seed: int, lengths=None):
+    """n profiles with Pfam-shaped lengths (pfam_like_lengths), profile i depending on (seed, i) only."""
+    Ks = pfam_like_lengths(n, seed) if lengths is None else lengths
+    for i, K in enumerate(Ks):
+        yield resample_hmm(seeds, int(K), np.random.default_rng([seed, i]), f"SH{i:05d}.1")
+
+
+def hmm_text(p: dict) -> str:
+    """One HMMER3/f profile (the fields press reads; the other header lines of a real file are left out)."""
+    out = ["HMMER3/f [3.3 | Nov 2019]\n", f"NAME  {p['name']}\n", f"ACC   {p['accession']}\n",
+           f"LENG  {len(p['nodes'])}\n", "ALPH  amino\n"]
+    if p.get("ga", True):
+        out.append("GA    22.90 22.90\n")
+    out.append(_HMM_HEAD)
+    out += [ln + "\n" for ln in p["compo"]]
+    for k, nd in enumerate(p["nodes"], 1):
+        cols = " ".join(f"{v:>8}" for v in nd["match"])
+        out.append(f"{k:>7} {cols} {' '.join(nd['tail'])}\n{nd['insert']}\n{nd['trans']}\n")
+    out.append("//\n")
+    return "".join(out)
+
+
+def write_hmm(path: str, profiles) -> int:
+    """Writes the profiles one after the other (an iterable: one alive at a time); returns their number."""
+    n = 0
+    with open(path, "w") as f:
+        for p in profiles:
+            f.write(hmm_text(p))
+            n += 1
+    return n

@@ -13,8 +13,11 @@
  *  - the codon and amino fields of the `match` column come from a restatement of third-party
  *    imm's imm_frame_cond_decode (csrc/host_logic.h), pinned by the reference's committed
  *    products.tsv only.
- *  - dcp_press_* needs the absent third-party imm/hmmer_reader libraries; the
- *    symbols exist and fail with DCP_EFUNCUSE.
+ *  - dcp_press_* reads HMMER3 text and builds the model on the host (csrc/hmm_model.h: a restatement of
+ *    hmm_reader.c, the third-party hmr reader, model.c and the imm arithmetic it calls) and computes the
+ *    emission tables on the GPU (csrc/press_kernel.hip).  It writes the current encoding (f32 arrays as `bin`,
+ *    c-core/write.c:59-66).  dcp_press_open fails with DCP_EFUNCUSE, creating nothing, without a gfx950 at
+ *    DECIPHON_HIP_DEVICE (default 0).
  */
 #ifndef DECIPHON_AMD_DECIPHON_H
 #define DECIPHON_AMD_DECIPHON_H
@@ -44,7 +47,10 @@ void dcp_batch_del(struct dcp_batch *);
 int dcp_batch_add(struct dcp_batch *, long id, char const *name, char const *data);
 void dcp_batch_reset(struct dcp_batch *);
 
-/* press: c-core/press.c:43-204 -- not provided by this build, see above */
+/* press: c-core/press.c:43-204, see above.  Call order: setup (while no press is open), open, next until end()
+ * is true, close.  next before open, after end() or after a failed next is DCP_EFUNCUSE.  A parse error is returned
+ * by the next that reaches that protein.  close after a failed next removes the output and returns 0; close
+ * before end() writes the proteins pressed so far, as the reference does.  No call leaves a temporary file. */
 struct dcp_press *dcp_press_new(void);
 int dcp_press_setup(struct dcp_press *, int gencode_id, float epsilon);
 int dcp_press_open(struct dcp_press *, char const *hmm, char const *db);
@@ -165,6 +171,12 @@ char const *dcp_scan_product(struct dcp_scan const *, long i);
  * batches.  Returns how many values exist (DCP_SCAN_TIMING_VALUES). */
 #define DCP_SCAN_TIMING_VALUES 13
 int dcp_scan_last_timing(struct dcp_scan const *, double *out, int n);
+/* Where the time of the current (or last) press went, from open on (measurement only).  Fills out[0..n) with, in
+ * order: seconds of parsing + model building (host), of uploads, of the emission kernel and of copy-back (GPU, from
+ * HIP events), of the host waiting for the GPU, of writing (records + header at close), then the nodes written and
+ * the bytes written.  Returns how many values exist (DCP_PRESS_TIMING_VALUES). */
+#define DCP_PRESS_TIMING_VALUES 8
+int dcp_press_last_timing(struct dcp_press const *, double *out, int n);
 
 #ifdef __cplusplus
 }

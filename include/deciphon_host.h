@@ -42,6 +42,25 @@ int dcp_decode_quasi_codon(float epsilon, float const *nucltp4, float const *cod
                            uint8_t codon[3]);
 char dcp_gencode_amino_of(int gencode_id, uint8_t const codon[3]);
 
+/* ---- HMMER3 text reader and protein model of press (csrc/hmm_model.h): hmm_reader_next (c-core/hmm_reader.c:19-67),
+ * model.c and the node layout of protein_absorb (c-core/protein.c:66-121).  dcp_hmm_open: DCP_EGENCODEID for an
+ * unknown NCBI table, DCP_EFOPEN for an unreadable file; dcp_hmm_count: the HMMER3/f lines of the file.
+ * dcp_hmm_next reads one profile (0, or DCP_EREADHMMER3, DCP_EENDOFFILE, DCP_EENDOFNODES, DCP_ELARGEMODEL,
+ * DCP_ELONGACCESSION, DCP_EZEROMODEL); at the end of the file it returns 0 and dcp_hmm_end becomes 1.
+ * dcp_hmm_read of the profile just read: trans[(K+1)*7] (node i: the transitions out of model node min(i + 1, K)),
+ * BMk[K], nucltp[(K+3)*4] and codonm[(K+3)*125] (0 = null, 1 = background, 2 + n = node n, n = 0..K, as
+ * dcp_db_read_nuclt_dist), accession[32], consensus[K+1]; any pointer may be NULL. ---- */
+struct dcp_hmm;
+int dcp_hmm_open(char const *path, int gencode_id, struct dcp_hmm **out);
+void dcp_hmm_close(struct dcp_hmm *);
+long dcp_hmm_count(struct dcp_hmm const *);
+int dcp_hmm_next(struct dcp_hmm *);
+int dcp_hmm_end(struct dcp_hmm const *);
+int dcp_hmm_core_size(struct dcp_hmm const *);
+int dcp_hmm_has_ga(struct dcp_hmm const *);
+int dcp_hmm_read(struct dcp_hmm const *, float *trans, float *BMk, float *nucltp, float *codonm, char *accession,
+                 char *consensus);
+
 /* partition_size (c-core/partition_size.c:13-16): proteins of partition idx out of nparts */
 long dcp_partition_size(long nelems, long nparts, long idx);
 /* core sizes of all proteins (read from the protein heads; nothing else of a protein is touched) */
