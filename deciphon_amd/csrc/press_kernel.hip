@@ -8,9 +8,15 @@
 // reference's pressed tables (tests/test_decoder.py).
 //
 // One workgroup per entry (a node, or the null or background model): its 129 inputs are exponentiated once into
-// LDS, lanes stride over the codes and each row of 1364 floats is stored coalesced.  Sums are taken in probability
-// space -- every term is a product of probabilities, so nothing cancels -- and the log is the accurate logf.  With
-// e = 0 every term of a code of length != 3 is 0 * (a finite probability) = 0, and logf(0) = -inf exactly.
+// LDS, lanes stride over the codes and each row of 1364 floats is stored coalesced.
+//
+// Every code length's P(z) is a sum of at most three terms c e^a f^b poly(p, M), f = 1 - e, a + b <= 4.  In fp32
+// probability space these products underflow long before log P(z) leaves its range: e^2 at e < 1e-19 (log P is
+// still about -100 at e = 1e-22), and p p M of an almost one-hot emission at any e.  So each term is taken as its
+// log, ln c + a ln e + b ln f + ln poly, in double, and the terms are combined by a max-shifted sum.  The
+// polynomials are sums of products of at most three probabilities, in double from the fp32 log inputs.  A zero power is left out of its term, never written as 0 * ln 0: with e = 0 or
+// e = 1 the terms that vanish are -inf (a positive multiple of -inf, or ln 0), nothing is NaN, and a code whose
+// terms all vanish is -inf exactly.  No term is ever +inf.  The result is rounded to fp32 once, at the end.
 #include "press_kernel.h"
 
 #include <hip/hip_runtime.h>
@@ -23,34 +29,47 @@ constexpr int THREADS = 256;
 
 struct State
 {
-  float const *p; // [4]
-  float const *M; // [125]
-  __device__ float m(int a, int b, int c) const { return M[a * 25 + b * 5 + c]; }
-  __device__ float del1(int a, int b) const { return m(ANY, a, b) + m(a, ANY, b) + m(a, b, ANY); }
-  __device__ float one(int a) const { return m(a, ANY, ANY) + m(ANY, a, ANY) + m(ANY, ANY, a); }
+  double const *p; // [4]
+  double const *M; // [125]
+  __device__ double m(int a, int b, int c) const { return M[a * 25 + b * 5 + c]; }
+  __device__ double del1(int a, int b) const { return m(ANY, a, b) + m(a, ANY, b) + m(a, b, ANY); }
+  __device__ double one(int a) const { return m(a, ANY, ANY) + m(ANY, a, ANY) + m(ANY, ANY, a); }
 };
 
-__device__ float emission_prob(State const &s, float e, int n, int const *z)
+// ln(exp(x) + exp(y)) and ln(exp(x) + exp(y) + exp(z)); -inf when every argument is
+__device__ double log_sum(double x, double y)
 {
-  float const f = 1.0f - e;
-  float const *p = s.p;
-  if (n == 1) return e * e * f * f / 3.0f * s.one(z[0]);
+  double const hi = fmax(x, y);
+  if (hi == -INFINITY) return hi;
+  return hi + log(exp(x - hi) + exp(y - hi));
+}
+
+__device__ double log_sum(double x, double y, double z)
+{
+  double const hi = fmax(fmax(x, y), z);
+  if (hi == -INFINITY) return hi;
+  return hi + log(exp(x - hi) + exp(y - hi) + exp(z - hi));
+}
+
+// ln P(z) for n = |z| nucleotides; le = ln e, lf = ln(1 - e)
+__device__ double emission_lprob(State const &s, double le, double lf, int n, int const *z)
+{
+  double const *p = s.p;
+  if (n == 1) return log(1.0 / 3.0) + 2.0 * le + 2.0 * lf + log(s.one(z[0]));
   if (n == 2)
-    return 2.0f * e * f * f * f / 3.0f * s.del1(z[0], z[1]) +
-           e * e * e * f / 3.0f * (p[z[0]] * s.one(z[1]) + p[z[1]] * s.one(z[0]));
+    return log_sum(log(2.0 / 3.0) + le + 3.0 * lf + log(s.del1(z[0], z[1])),
+                   log(1.0 / 3.0) + 3.0 * le + lf + log(p[z[0]] * s.one(z[1]) + p[z[1]] * s.one(z[0])));
   if (n == 3)
-  {
-    float v = f * f * f * f * s.m(z[0], z[1], z[2]);
-    v += 4.0f * e * e * f * f / 9.0f *
-         (p[z[0]] * s.del1(z[1], z[2]) + p[z[1]] * s.del1(z[0], z[2]) + p[z[2]] * s.del1(z[0], z[1]));
-    return v + e * e * e * e * p[z[0]] * p[z[1]] * p[z[2]];
-  }
+    return log_sum(4.0 * lf + log(s.m(z[0], z[1], z[2])),
+                   log(4.0 / 9.0) + 2.0 * le + 2.0 * lf +
+                       log(p[z[0]] * s.del1(z[1], z[2]) + p[z[1]] * s.del1(z[0], z[2]) + p[z[2]] * s.del1(z[0], z[1])),
+                   4.0 * le + log(p[z[0]] * p[z[1]] * p[z[2]]));
   if (n == 4)
   {
     // one base inserted (j) into a codon, or two inserted (i, j) into a codon with one base deleted
-    float a = p[z[0]] * s.m(z[1], z[2], z[3]) + p[z[1]] * s.m(z[0], z[2], z[3]) + p[z[2]] * s.m(z[0], z[1], z[3]) +
-              p[z[3]] * s.m(z[0], z[1], z[2]);
-    float b = 0.0f;
+    double a = p[z[0]] * s.m(z[1], z[2], z[3]) + p[z[1]] * s.m(z[0], z[2], z[3]) + p[z[2]] * s.m(z[0], z[1], z[3]) +
+               p[z[3]] * s.m(z[0], z[1], z[2]);
+    double b = 0.0;
     for (int i = 0; i < 4; ++i)
       for (int j = i + 1; j < 4; ++j)
       {
@@ -59,9 +78,9 @@ __device__ float emission_prob(State const &s, float e, int n, int const *z)
           if (t != i && t != j) r[k++] = z[t];
         b += p[z[i]] * p[z[j]] * s.del1(r[0], r[1]);
       }
-    return e * f * f * f / 2.0f * a + e * e * e * f / 9.0f * b;
+    return log_sum(log(1.0 / 2.0) + le + 3.0 * lf + log(a), log(1.0 / 9.0) + 3.0 * le + lf + log(b));
   }
-  float v = 0.0f; // n == 5: two bases inserted (i, j) into a codon
+  double v = 0.0; // n == 5: two bases inserted (i, j) into a codon
   for (int i = 0; i < 5; ++i)
     for (int j = i + 1; j < 5; ++j)
     {
@@ -70,18 +89,19 @@ __device__ float emission_prob(State const &s, float e, int n, int const *z)
         if (t != i && t != j) r[k++] = z[t];
       v += p[z[i]] * p[z[j]] * s.m(r[0], r[1], r[2]);
     }
-  return e * e * f * f / 10.0f * v;
+  return log(1.0 / 10.0) + 2.0 * le + 2.0 * lf + log(v);
 }
 
 __global__ __launch_bounds__(THREADS) void emission_kernel(float const *__restrict__ in, float *__restrict__ out,
                                                            float epsilon)
 {
-  __shared__ float prob[DCP_PRESS_IN_STRIDE];
+  __shared__ double prob[DCP_PRESS_IN_STRIDE];
   int const tid = (int)threadIdx.x;
   size_t const entry = blockIdx.x;
-  if (tid < 4 + 125) prob[tid] = expf(in[entry * DCP_PRESS_IN_STRIDE + (size_t)tid]);
+  if (tid < 4 + 125) prob[tid] = exp((double)in[entry * DCP_PRESS_IN_STRIDE + (size_t)tid]);
   __syncthreads();
   State const s{prob, prob + 4};
+  double const le = log((double)epsilon), lf = log1p(-(double)epsilon);
   float *row = out + entry * DCP_PRESS_TABLE;
   for (int code = tid; code < DCP_PRESS_TABLE; code += THREADS)
   {
@@ -93,7 +113,7 @@ __global__ __launch_bounds__(THREADS) void emission_kernel(float const *__restri
     else n = 5, idx = code - 340;
     int z[5];
     for (int j = n - 1; j >= 0; --j, idx >>= 2) z[j] = idx & 3;
-    row[code] = logf(emission_prob(s, epsilon, n, z));
+    row[code] = (float)emission_lprob(s, le, lf, n, z);
   }
 }
 

@@ -3,6 +3,7 @@ of deciphon_amd/csrc/dcp_types.h restated in numpy, and loaders for the fixtures
 from __future__ import annotations
 
 import ctypes as C
+import itertools
 import os
 import subprocess
 import sys
@@ -67,6 +68,53 @@ def choose_qw(K: int, path: bool = False):
         if K <= 64 * Q * W:
             return Q, W
     raise ValueError("core size beyond 4096: the strip class (pack_profile(..., strips=))")
+
+
+def _code_digits():
+    """per length n = 1..5: int[4^n, n], the nucleotides of codes offset[n-1] .. offset[n-1] + 4^n - 1 (first
+    nucleotide most significant)"""
+    return [np.array(list(itertools.product(range(4), repeat=n)), np.int64).reshape(-1, n) for n in range(1, 6)]
+
+
+CODE_DIGITS = _code_digits()
+
+
+def emission_probs(e: float, nucltp, codonm) -> np.ndarray:
+    """oracle.pydecode.emission_prob over whole tables, in float64: nucltp[entries, 4] and codonm[entries, 125]
+    (log-probabilities, as pressed) -> P[entries, 1364], the probability (not log) of every quasi-codon code."""
+    p = np.exp(np.asarray(nucltp, np.float64)).reshape(-1, 4)
+    M = np.exp(np.asarray(codonm, np.float64)).reshape(-1, 5, 5, 5)
+    e = float(e)
+    f = 1.0 - e
+    A = 4  # ANY
+    one = M[:, :4, A, A] + M[:, A, :4, A] + M[:, A, A, :4]  # [E, a]: codons holding a, two bases deleted
+    del1 = M[:, A, :4, :4] + M[:, :4, A, :4] + M[:, :4, :4, A]  # [E, a, b]: codons reading (a, b), one deleted
+
+    def m3(r):  # M at the codons r[:, 0..2] -> [E, codes]
+        return M[:, r[:, 0], r[:, 1], r[:, 2]]
+
+    out = np.empty((len(p), TABLE_SIZE))
+    z = CODE_DIGITS[0]
+    out[:, 0:4] = e * e * f * f / 3 * one[:, z[:, 0]]
+    z0, z1 = CODE_DIGITS[1].T
+    out[:, 4:20] = 2 * e * f ** 3 / 3 * del1[:, z0, z1] + e ** 3 * f / 3 * (p[:, z0] * one[:, z1] + p[:, z1] * one[:, z0])
+    z0, z1, z2 = CODE_DIGITS[2].T
+    v = f ** 4 * M[:, z0, z1, z2]
+    v = v + 4 * e * e * f * f / 9 * (p[:, z0] * del1[:, z1, z2] + p[:, z1] * del1[:, z0, z2] + p[:, z2] * del1[:, z0, z1])
+    out[:, 20:84] = v + e ** 4 * p[:, z0] * p[:, z1] * p[:, z2]
+    z = CODE_DIGITS[3]
+    a = sum(p[:, z[:, j]] * m3(np.delete(z, j, axis=1)) for j in range(4))
+    b = 0.0
+    for i, j in itertools.combinations(range(4), 2):
+        r = np.delete(z, (i, j), axis=1)
+        b = b + p[:, z[:, i]] * p[:, z[:, j]] * del1[:, r[:, 0], r[:, 1]]
+    out[:, 84:340] = e * f ** 3 / 2 * a + e ** 3 * f / 9 * b
+    z = CODE_DIGITS[4]
+    v = 0.0
+    for i, j in itertools.combinations(range(5), 2):
+        v = v + p[:, z[:, i]] * p[:, z[:, j]] * m3(np.delete(z, (i, j), axis=1))
+    out[:, 340:] = e * e * f * f / 10 * v
+    return out
 
 
 def pack_profile(prof: Profile, Q: int | None = None, W: int | None = None, strips: int = 1):

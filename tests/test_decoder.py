@@ -95,3 +95,54 @@ def test_reference_products_triples(seeds):
             assert "".join("ACGT"[v] for v in got) == codon and host.gencode_amino(s["gencode"], got) == amino, cell
             n += 1
     assert n == 173 + 241 + 162
+
+
+@pytest.mark.parametrize("eps", [0.0, 1e-30, 0.01, 0.5, 1.0])
+def test_vectorised_model_equals_the_scalar_model(seeds, eps):
+    """dcp_testlib.emission_probs (the float64 reference the GPU press tests check every entry against) == the
+    scalar emission_prob above, every code of 60 random minifam entries -- null, background and nodes alike."""
+    from dcp_testlib import emission_probs
+
+    e = float(np.float32(eps))
+    rng = np.random.default_rng(int(eps * 1000) + 7)
+    for it in range(60):
+        s = seeds[it % 3]
+        entry = int(rng.integers(0, s["core_size"] + 3))
+        got = emission_probs(e, s["nucltp"][entry : entry + 1], s["codonm"][entry : entry + 1])[0]
+        p = np.exp(s["nucltp"][entry].astype(np.float64))
+        M = np.exp(s["codonm"][entry].astype(np.float64)).reshape(5, 5, 5)
+        for code, z in _codes():
+            want = pydecode.emission_prob(e, p, M, z)
+            assert abs(got[code] - want) <= 1e-12 * want, (eps, entry, z, got[code], want)
+            if eps in (0.0, 1.0) and len(z) != 3:
+                assert got[code] == 0.0
+
+
+@pytest.mark.parametrize("eps", [0.0, 1e-30, 0.5, 0.999])
+def test_product_decoder_equals_the_oracle_at_extreme_error_rates(seeds, eps):
+    """dcp_decode_codon == pydecode.decode away from the default error rate: random quasi-codons of every length, and
+    at epsilon = 0 (where only a whole codon has a probability) of 3 nucleotides.  Where no codon has a positive
+    probability (at epsilon = 0, a stop codon) both refuse."""
+    from deciphon_amd import HipError, host
+
+    e = float(np.float32(eps))
+    rng = np.random.default_rng(int(eps * 1000) + 11)
+    refused = 0
+    for it in range(300):
+        s = seeds[it % 3]
+        entry = int(rng.integers(0, s["core_size"] + 3))
+        n = 3 if eps == 0.0 else int(rng.integers(1, 6))
+        z = rng.integers(0, 4, size=n).astype(np.uint8)
+        if eps == 0.0 and it % 10 == 0:
+            z = np.array([3, 0, 2], np.uint8)  # TAG
+        try:
+            want = pydecode.decode(e, s["nucltp"][entry], s["codonm"][entry], z)
+        except ValueError:
+            with pytest.raises(HipError):
+                host.decode_quasi_codon(e, s["nucltp"][entry], s["codonm"][entry], z)
+            refused += 1
+            continue
+        codon = host.decode_quasi_codon(e, s["nucltp"][entry], s["codonm"][entry], z)
+        assert tuple(int(v) for v in codon) == want[0], (eps, entry, z)
+        assert host.gencode_amino(1, codon) == want[1]
+    assert (refused > 0) == (eps == 0.0)
