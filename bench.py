@@ -14,20 +14,27 @@ every window of every (profile, read) pair as c-core/window.c cuts them (window 
 overlap 4K - 1).  P and R are sized so that a step stays below a second.  With N ranks the
 PROFILES are sharded, as north_star says: the database has N x P profiles, rank i owns the i-th
 contiguous partition (boundaries balanced by core size), reads are replicated, there is no
-data-path collective; the hit records are gathered with RCCL after the timed region.  Per-GPU
-work is fixed as N grows: weak scaling.
+data-path collective; with --full the hit records are gathered with RCCL after the timed region.
+Per-GPU work is fixed as N grows: weak scaling.
 
 `python bench.py --gpus N` with N > 1 and no torchrun environment starts its own N ranks: a CHILD
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py ...` (before this process has
 imported torch or touched HIP), whose one JSON line and exit code it relays.
 
-Prints ONE JSON line (rank 0): metric/value/unit per BASELINE.json, plus
+A plain run does only what the headline needs: it builds and stages the workload, runs the warm-up and the timed
+steps, writes --dump-outputs if asked, and prints ONE JSON line (rank 0): metric/value/unit per BASELINE.json, plus
   roofline     -- the binding roofline of the cost kernels is VALU issue:
                   wave-level VALU instructions of one step (PMC pass of this same workload and
                   kernel source, profiles/*_traffic.json) / HIP-event time of one step, against
                   the chip's nominal VALU issue peak (`peak`, `frac`) and against the best
                   instruction stream measured on this GPU (`peak_measured`, `frac_of_measured`); HBM
                   figures (measured traffic, algorithmic bytes) ride along as secondary fields
+
+--full adds every leg that runs or times something of its own after the timed steps (each still switched off by its
+--no-... option or --large-db 0; --profile skips them all):
+  config.pcie_inclusive_gcups_per_gpu -- the same step once more through the host-buffer boundary (reads H2D +
+                  encode, window list H2D, kernels, scores D2H)
+  config.hits_gathered -- the windows whose LRT is >= 0, gathered from every rank (RCCL with N ranks)
   cpu_baseline -- the reference's own viterbi.c (oracle/_ref, kind "reference") or the oracle
                   restatement (kind "port") on a bounded sample of the same workload: a sweep over
                   thread counts up to what this process may use (affinity, cgroup quota); value = best
@@ -400,15 +407,19 @@ def main():
     ap.add_argument("--profiles", type=int, default=400, help="profiles per GPU (pfam workload)")
     ap.add_argument("--reads", type=int, default=None)
     ap.add_argument("--read-len", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
-    ap.add_argument("--no-end-to-end", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run and time the other legs too: PCIe-inclusive step, gathered hits, "
+                         "end to end scan, secondary config, large database, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the secondary config")
+    ap.add_argument("--no-end-to-end", action="store_true", help="--full without the end to end scan")
     ap.add_argument("--large-db", type=int, default=5000, metavar="P",
-                    help="also time the cost pass over a database of P profiles (5000 = 6 GB of tables; 0 = skip)")
+                    help="with --full, also time the cost pass over a database of P profiles (5000 = 6 GB of tables; "
+                         "0 = skip)")
     ap.add_argument("--large-db-reads", type=int, default=100)
     ap.add_argument("--large-db-steps", type=int, default=2)
     ap.add_argument("--profile", action="store_true",
-                    help="only warmup + timed launches (for rocprofv3: every dispatch is one step's)")
+                    help="only warmup + timed launches, even with --full (for rocprofv3: every dispatch is one step's)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the scores of the last timed step as DIR/null_cost.npy, DIR/alt_cost.npy (float32)")
     args = ap.parse_args()
@@ -506,9 +517,10 @@ def run(args, torch, deciphon_amd, ddist, dist, rank, local_rank, world, dev, de
         dist.all_reduce(c, op=dist.ReduceOp.SUM)
     t_max, total_cells = float(t.item()), float(c.item())
 
+    legs = args.full and not args.profile  # the legs that run or time something of their own
     host_gcups = None
     all_rows = []
-    if not args.profile:
+    if legs:
         # outside the timed region: the same step through the host-buffer boundary (reads H2D + encode,
         # window list H2D, kernels, scores D2H) -- the PCIe-inclusive rate DESIGN.md quotes
         t1 = time.perf_counter()
@@ -567,24 +579,26 @@ def run(args, torch, deciphon_amd, ddist, dist, rank, local_rank, world, dev, de
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
         "data": "synthetic",
         "config": {"workload": desc, "workload_key": workload_key, "kernel_source_hash": kernel_source_hash(),
-                   "windows_per_gpu": int(len(wins)), "cells_per_step_per_gpu": cells,
-                   "hits_gathered": len(all_rows), "pcie_inclusive_gcups_per_gpu": host_gcups,
+                   "windows_per_gpu": int(len(wins)), "cells_per_step_per_gpu": cells, "full": args.full,
                    "parallelism": parallelism,
                    "collective": None if dist is None else {
                        "backend": dist.get_backend(), "library": "gloo (rehearsal)" if dev_coll == "cpu" else "RCCL",
                        "rccl_ranks": rccl_ranks, "world_size": dist.get_world_size()}},
         "roofline": roof,
     }
+    if legs:
+        out["config"]["hits_gathered"] = len(all_rows)
+        out["config"]["pcie_inclusive_gcups_per_gpu"] = host_gcups
     if dumped is not None:
         out["config"]["dumped"] = dumped
     if db is not None:
         out["config"]["database"] = {k: v for k, v in db.items() if k != "path"}
         out["config"]["database"]["ingest_GBps"] = db["file_bytes"] / db["ingest_s"] / 1e9
-    if world == 1 and not args.profile and not args.no_end_to_end and args.workload == "pfam":
+    if world == 1 and legs and not args.no_end_to_end and args.workload == "pfam":
         eng.close()  # the scan owns its engines; the bench's tables go first
         out["config"]["end_to_end"] = end_to_end(db["path"], reads, cells, local_rank)
         out["config"]["end_to_end"]["frac_of_value"] = out["config"]["end_to_end"]["gcups"] / gcups
-    if world == 1 and not args.profile and not args.no_secondary and args.workload == "pfam":
+    if world == 1 and legs and not args.no_secondary and args.workload == "pfam":
         # BASELINE configs[1], same engine class, same entry points
         with deciphon_amd.Engine(local_rank) as e2:
             _, _, w2 = minifam_workload(e2, 1000, 3000)
@@ -595,14 +609,14 @@ def run(args, torch, deciphon_amd, ddist, dist, rank, local_rank, world, dev, de
                 "workload": "minifam.dcp (K=173,241,162) x 1000 synthetic 3000 nt reads, one window per pair "
                             "(BASELINE configs[1])",
                 "value": cells2 * 20 / (ms2 * 1e-3) / 1e9, "unit": "GCUPS", "ms_per_step": ms2 / 20}
-    if world == 1 and not args.profile and args.large_db > 0 and args.workload == "pfam":
+    if world == 1 and legs and args.large_db > 0 and args.workload == "pfam":
         eng.close()
         try:  # 5 GB of scratch file and 6 GB of HBM more than the line needs: a box that lacks them still gets its line
             out["config"]["large_db"] = large_db(args, local_rank, tmp)
             out["config"]["large_db"]["frac_of_value"] = out["config"]["large_db"]["value"] / gcups
         except (OSError, MemoryError, RuntimeError) as e:
             out["config"]["large_db"] = {"error": f"{type(e).__name__}: {e}"}
-    if not args.no_cpu_baseline and not args.profile and world == 1:
+    if not args.no_cpu_baseline and legs and world == 1:
         out["cpu_baseline"] = cpu_baseline(seeds, Ks_all, reads, args.read_len) if args.workload == "pfam" else None
         if out["cpu_baseline"]:
             out["config"]["vs_cpu_baseline"] = gcups / out["cpu_baseline"]["value"]

@@ -1,4 +1,4 @@
-"""GPU: bench.py's contract -- one JSON line with the agreed keys -- for one rank, and the multi-rank
+"""GPU: bench.py's contract -- one JSON line with the agreed keys -- for one rank, plain and with --full, and the multi-rank
 path (barriers, max-over-ranks time, whole-job cells, gathered hit records) rehearsed with two ranks
 that share this box's one GPU (DECIPHON_DIST_BACKEND=gloo; on a real node each rank has its own GPU
 and the collectives are RCCL)."""
@@ -6,6 +6,7 @@ import json
 import os
 import subprocess
 import sys
+import time
 
 import pytest
 
@@ -15,6 +16,8 @@ pytestmark = pytest.mark.gpu
 
 KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
         "vs_baseline", "dtype", "data", "config", "roofline"}
+# what --full adds to config: the legs that run or time something of their own after the timed steps
+LEGS = {"end_to_end", "secondary", "large_db", "vs_cpu_baseline", "hits_gathered", "pcie_inclusive_gcups_per_gpu"}
 
 
 def _line(out):
@@ -23,12 +26,29 @@ def _line(out):
     return json.loads(lines[0])
 
 
+def test_plain_run_is_the_headline_alone():
+    """Without --full the run sets up, warms up, times its steps and prints its line: no leg of its own after them,
+    and at most 30 s of the whole process's wall time outside the warm-up and timed steps."""
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1"],
+                       capture_output=True, text=True, timeout=600)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr
+    d = _line(r.stdout)
+    assert KEYS <= set(d) and "cpu_baseline" not in d and not LEGS & set(d["config"])
+    assert d["config"]["full"] is False and d["config"]["workload_key"] == "pfam:400x500x10000"
+    assert d["metric"] == "GCUPS (Viterbi DP cell updates/sec)" and d["unit"] == "GCUPS" and d["higher_is_better"]
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "f32" and 0.0 < d["ms_per_step"] < 1000.0
+    assert d["value"] > 0 and d["roofline"]["bound"] == "valu_issue"
+    assert wall - 4 * d["ms_per_step"] * 1e-3 < 30.0, (wall, d["ms_per_step"])
+
+
 def test_one_rank_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=1100)
     assert r.returncode == 0, r.stderr
     d = _line(r.stdout)
-    assert KEYS <= set(d) and "cpu_baseline" in d
+    assert KEYS <= set(d) and "cpu_baseline" in d and d["config"]["full"] is True
     assert d["n_gpus"] == 1 and d["steps"] == 5 and d["unit"] == "GCUPS" and d["dtype"] == "f32"
     assert d["config"]["workload"].startswith("Pfam-shaped") and d["config"]["workload_key"] == "pfam:400x500x10000"
     assert d["ms_per_step"] < 1000.0  # the workload is sized to keep a step below a second
@@ -133,7 +153,8 @@ def test_two_ranks_line():
     env = dict(os.environ, DECIPHON_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", "29545", os.path.join(ROOT, "bench.py"),
-                        "--gpus", "2", "--steps", "3", "--warmup", "1", "--profiles", "120", "--reads", "100"], env=env,
+                        "--gpus", "2", "--steps", "3", "--warmup", "1", "--profiles", "120", "--reads", "100", "--full"],
+                       env=env,
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     d = _line(r.stdout)
