@@ -33,6 +33,8 @@ struct DcpCodeRow
 //          { null[c], bg[c], 0, 0, match[c][0..Kp) } -- everything a DP row needs
 //          for one emission length sits behind ONE scalar offset c * stride
 //   trans: [8][Kp]
+//   cost_rows: the same rows in the order the cost kernel of shape cost_shape reads them (dcp_cost_order_col,
+//          host_logic.h), [1364][DCP_COST_ORDER_HDR + 64 Q' W']; offset 0 = no copy, every kernel reads `rows`
 struct DcpProfileDev
 {
   int32_t K;         // core size
@@ -41,8 +43,11 @@ struct DcpProfileDev
   int32_t W;         // waves per problem (1 for K <= 256)
   int64_t rows_off;  // [1364][DCP_ROW_HDR + Kp]
   int64_t trans_off; // [8][Kp]
-  int64_t pad0, pad1;
+  int64_t cost_rows_off; // 0 or [1364][dcp_cost_order_stride(Q', W')]
+  int64_t cost_shape;    // DCP_COST_SHAPE(Q', W') of the kernel the copy is for
 };
+#define DCP_COST_SHAPE(Q, W) ((Q) * 256 + (W))
+#define DCP_COST_ORDER_HDR 32 // floats in front of the columns of a cost-order row: { null, bg, 0, 0 }, +inf to 128 bytes
 
 // One (profile x sequence-window) DP problem.
 struct DcpProblem

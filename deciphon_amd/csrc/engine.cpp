@@ -161,6 +161,7 @@ struct HostProfile
   int K, Kp, Q, W, cls;
   int pack = -1; // shape of the packed cost kernel (several windows per wavefront), -1: none
   bool narrow = false; // fits its class with one position per lane less (dcp_class_narrow_limit)
+  int cQ = 0, cW = 0;  // shape of the cost kernel its cost-order copy of the rows is for (host_logic.h); 0: no copy
   int64_t pool_off; // floats
   std::string accession;
 };
@@ -945,10 +946,48 @@ char const *dcp_hip_strerror(struct dcp_hip const *x) { return x ? x->err.c_str(
 // A profile is laid out on the host in a staging buffer (rows | trans, +inf padded) and
 // copied behind the profiles already resident; nothing Pfam-sized is ever held twice.
 
-static size_t profile_floats(int Kp)
+// rows | trans, rounded up to 128 bytes: every profile, and the cost-order copy behind its tables, starts on a line
+static size_t canonical_floats(int Kp)
 {
   size_t const floats = (size_t)DCP_TABLE_SIZE * ((size_t)Kp + DCP_ROW_HDR) + (size_t)DCP_NUM_TRANS * (size_t)Kp;
-  return (floats + 3) & ~(size_t)3; // keep every profile 16-byte aligned for the dwordx4 row loads
+  return (floats + 31) & ~(size_t)31;
+}
+
+static size_t profile_floats(HostProfile const &hp)
+{
+  size_t const copy = hp.cQ ? (size_t)DCP_TABLE_SIZE * (size_t)dcp_cost_order_stride(hp.cQ, hp.cW) : 0;
+  return canonical_floats(hp.Kp) + copy;
+}
+
+// The cost-order copy (host_logic.h) of the staged rows, behind the profile's canonical tables, for the profiles whose
+// default cost kernel is a narrow one (dcp_launch_cost_narrow) that gains from it: (5,1) and (10,1), K = 257..320 and
+// 513..640.  Their tail chunks of one and two floats were the most strided loads; per class they run 7-10 % and 6-8 %
+// faster on the copy, while (6,1), (7,1), (8,1) and (6,2) do not move (profiles/r04_cost_order_ab.txt) -- no copy there.
+// Only dcp_cost_kernel<5,1> and <10,1> read it: every other kernel has a shape of its own (the checkpoint and block
+// kernels of the path pass run the class shape) and reads the canonical rows.
+// DECIPHON_HIP_COST_ORDER, read at ingest: 0 = no copies; "poison" = copies, and the canonical match columns of those
+// profiles staged as 0 (a test's proof that the narrow kernels read the copy: their scores stay the oracle's).
+static bool cost_order_pays(int Q, int W) { return W == 1 && (Q == 5 || Q == 10); }
+
+static void cost_order_shape(HostProfile &hp)
+{
+  hp.cQ = hp.cW = 0;
+  char const *e = getenv("DECIPHON_HIP_COST_ORDER");
+  if (!hp.narrow || (e && e[0] == '0')) return;
+  int const q = dcp_class_narrow_q(hp.cls);
+  if (!cost_order_pays(q, 1)) return;
+  hp.cQ = q;
+  hp.cW = 1;
+}
+
+static void stage_cost_order(HostProfile const &hp, float *staged)
+{
+  if (!hp.cQ) return;
+  dcp_cost_order_rows(hp.cQ, hp.cW, hp.K, hp.Kp, staged, staged + canonical_floats(hp.Kp));
+  char const *e = getenv("DECIPHON_HIP_COST_ORDER");
+  if (e && strcmp(e, "poison") == 0)
+    for (int c = 0; c < DCP_TABLE_SIZE; ++c)
+      memset(staged + (size_t)c * ((size_t)hp.Kp + DCP_ROW_HDR) + DCP_ROW_HDR, 0, sizeof(float) * (size_t)hp.K);
 }
 
 static int describe(dcp_hip *x, int K, char const *accession, HostProfile &hp)
@@ -964,6 +1003,7 @@ static int describe(dcp_hip *x, int K, char const *accession, HostProfile &hp)
   hp.pool_off = 0;
   hp.accession = accession ? accession : "";
   hp.narrow = K <= dcp_class_narrow_limit(cls);
+  cost_order_shape(hp);
   hp.pack = dcp_pack_shape_of(K);
   if (hp.pack >= 0)
   {
@@ -1027,7 +1067,7 @@ int dcp_hip_add_profile(struct dcp_hip *x, int K, float const *trans, float cons
   if (rc) return rc;
   int const Kp = hp.Kp;
   size_t const stride = (size_t)Kp + DCP_ROW_HDR;
-  std::vector<float> buf(profile_floats(Kp), INFINITY);
+  std::vector<float> buf(profile_floats(hp), INFINITY);
   float *r = buf.data();
   float *t = r + (size_t)DCP_TABLE_SIZE * stride;
   for (int id = 0; id < DCP_NUM_TRANS; ++id) memcpy(t + (size_t)id * Kp, trans + (size_t)id * K, sizeof(float) * K);
@@ -1040,6 +1080,7 @@ int dcp_hip_add_profile(struct dcp_hip *x, int K, float const *trans, float cons
     hdr[2] = hdr[3] = 0.0f;
     memcpy(hdr + DCP_ROW_HDR, match + (size_t)c * K, sizeof(float) * K);
   }
+  stage_cost_order(hp, r);
   return push_profile(x, hp, buf, index);
 }
 
@@ -1052,11 +1093,12 @@ int dcp_hip_add_protein(struct dcp_hip *x, int K, float const *node_trans, float
   HostProfile hp;
   int rc = describe(x, K, nullptr, hp);
   if (rc) return rc;
-  std::vector<float> buf(profile_floats(hp.Kp), INFINITY);
+  std::vector<float> buf(profile_floats(hp), INFINITY);
   float *r = buf.data();
   float *t = r + (size_t)DCP_TABLE_SIZE * ((size_t)hp.Kp + DCP_ROW_HDR);
   dcp_setup_profile(K, hp.Kp, node_trans, node_emission, BMk, null_lprob, bg_lprob, t, r);
   if (!delete_costs_ok(t, K, hp.Kp)) return fail(x, DCP_EFDATA, "positive (or NaN) delete log-probability in the protein");
+  stage_cost_order(hp, r);
   return push_profile(x, hp, buf, index);
 }
 
@@ -1090,13 +1132,13 @@ int dcp_hip_load_dcp(struct dcp_hip *x, char const *path, int first, int count)
     std::string acc;
     if ((rc = db.read_protein_head(first + i, K, acc))) return fail(x, rc, "cannot read protein");
     if ((rc = describe(x, K, acc.c_str(), hps[(size_t)i]))) return rc;
-    off[(size_t)i + 1] = off[(size_t)i] + profile_floats(hps[(size_t)i].Kp);
+    off[(size_t)i + 1] = off[(size_t)i] + profile_floats(hps[(size_t)i]);
   }
   if ((rc = ensure_pool(x, x->pool_used + off[(size_t)n]))) return rc;
 
   // staging chunks of 256 MiB; DECIPHON_HIP_STAGE_MB shrinks them (never below one profile of the largest
   // size present), which is how the tests drive a small database through many chunks
-  size_t chunk_floats = std::max<size_t>((size_t)64 << 20, profile_floats(DCP_MAX_CORE_SIZE));
+  size_t chunk_floats = std::max<size_t>((size_t)64 << 20, canonical_floats(DCP_MAX_CORE_SIZE));
   if (char const *e = getenv("DECIPHON_HIP_STAGE_MB"))
   {
     size_t largest = 0;
@@ -1158,6 +1200,7 @@ int dcp_hip_load_dcp(struct dcp_hip *x, char const *path, int first, int count)
           int expected = 0;
           bad.compare_exchange_strong(expected, DCP_EFDATA); // a positive delete log-probability
         }
+        stage_cost_order(hps[(size_t)i], rows);
       }
     };
     {
@@ -1234,7 +1277,8 @@ int dcp_hip_commit_profiles(struct dcp_hip *x)
     dev[i].W = hp.W;
     dev[i].rows_off = hp.pool_off;
     dev[i].trans_off = dev[i].rows_off + (int64_t)DCP_TABLE_SIZE * (hp.Kp + DCP_ROW_HDR);
-    dev[i].pad0 = dev[i].pad1 = 0;
+    dev[i].cost_rows_off = hp.cQ ? hp.pool_off + (int64_t)canonical_floats(hp.Kp) : 0;
+    dev[i].cost_shape = hp.cQ ? DCP_COST_SHAPE(hp.cQ, hp.cW) : 0;
   }
   HIP_TRY(x, x->d_profiles.reserve(dev.size()), DCP_ENOMEM);
   HIP_TRY(x, hipMemcpyAsync(x->d_profiles.p, dev.data(), dev.size() * sizeof(DcpProfileDev), hipMemcpyHostToDevice,

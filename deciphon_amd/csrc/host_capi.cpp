@@ -102,6 +102,13 @@ int dcp_decode_quasi_codon(float epsilon, float const *nucltp4, float const *cod
 
 char dcp_gencode_amino_of(int gencode_id, uint8_t const codon[3]) { return dcp_gencode_amino(gencode_id, codon); }
 
+int dcp_cost_order_map(int Q, int W, int32_t *cols)
+{
+  if (Q < 1 || W < 1 || Q * W > 64 || !cols) return 0;
+  for (int k = 0; k < 64 * Q * W; ++k) cols[k] = dcp_cost_order_col(Q, W, k);
+  return dcp_cost_order_stride(Q, W);
+}
+
 int dcp_partition_bounds_of(int n, int32_t const *core_sizes, int nparts, int balanced, int32_t *first)
 {
   if (n < 0 || !first || (balanced && n > 0 && !core_sizes)) return DCP_EFUNCUSE;

@@ -88,6 +88,32 @@ void dcp_setup_profile(int K, int Kp, float const *node_trans, float const *node
   }
 }
 
+int dcp_cost_order_col(int Q, int W, int k)
+{
+  (void)W;
+  int const g = k / Q, q = k % Q, w = g / 64, e = g % 64, c = q / 4;
+  int const wc = Q - 4 * c < 4 ? Q - 4 * c : 4;
+  return 64 * Q * w + 256 * c + e * wc + (q - 4 * c);
+}
+
+int dcp_cost_order_stride(int Q, int W) { return DCP_COST_ORDER_HDR + 64 * Q * W; }
+
+void dcp_cost_order_rows(int Q, int W, int K, int Kp, float const *rows, float *copy)
+{
+  int const Kc = 64 * Q * W, stride = dcp_cost_order_stride(Q, W);
+  std::vector<int> col((size_t)Kc);
+  for (int k = 0; k < Kc; ++k) col[(size_t)k] = dcp_cost_order_col(Q, W, k);
+  for (int c = 0; c < DCP_TABLE_SIZE; ++c)
+  {
+    float const *hdr = rows + (size_t)c * ((size_t)Kp + DCP_ROW_HDR);
+    float const *row = hdr + DCP_ROW_HDR;
+    float *out = copy + (size_t)c * stride;
+    for (int j = 0; j < DCP_ROW_HDR; ++j) out[j] = hdr[j];
+    for (int j = DCP_ROW_HDR; j < DCP_COST_ORDER_HDR; ++j) out[j] = INFINITY;
+    for (int k = 0; k < Kc; ++k) out[DCP_COST_ORDER_HDR + col[(size_t)k]] = k < K ? row[k] : INFINITY;
+  }
+}
+
 int dcp_encode_sequence(char const *data, int64_t n, uint8_t *out)
 {
   enum { A, C, G, T, U, NSYM };

@@ -16,6 +16,21 @@ void dcp_xtrans(int seq_size, bool multi_hits, bool hmmer3_compat, float xt[DCP_
 void dcp_setup_profile(int K, int Kp, float const *node_trans, float const *node_emission, float const *BMk,
                        float const *null_lprob, float const *bg_lprob, float *trans, float *rows);
 
+// ---- the cost-order copy of the emission rows (CostWave, viterbi_body.h) ----
+// The cost kernels of Q >= 5 positions per lane read a lane's Q floats of a row in chunks of four (b128, and a
+// narrower tail).  In the canonical rows lane e's floats sit at e*Q: every chunk load is strided by 4Q bytes over
+// the lanes and touches about the whole row.  The copy puts chunk c of every lane of wave w side by side: position
+// k (global lane g = k / Q, q = k % Q, w = g / 64, e = g % 64) goes to column 64*Q*w + 256*c + e*wc + (q - 4c),
+// c = q / 4, wc = min(4, Q - 4c) -- one contiguous 256*wc-byte span per load instruction of a wave.  A copy row is
+// { null, bg, 0, 0 } padded with +inf to 32 floats, then the Kp' = 64*Q*W columns: dcp_cost_order_stride = 32 + Kp'
+// floats, so every row and its column block start on a 128-byte line, and the header sits at the row's offset as in
+// the canonical rows (no extra scalar add per emission length).  Q <= 4 is the identity; no copy for those shapes.
+int dcp_cost_order_col(int Q, int W, int k);
+int dcp_cost_order_stride(int Q, int W);
+// copy[1364][dcp_cost_order_stride(Q, W)] from canonical rows[1364][DCP_ROW_HDR + Kp], Kp >= 64*Q*W; the columns
+// are +inf beyond position K
+void dcp_cost_order_rows(int Q, int W, int K, int Kp, float const *rows, float *copy);
+
 // c-core/sequence.c:15-45 (uppercase + disambiguate, c-core/disambiguate.c:37-86)
 // followed by the A,C,G,T/U -> 0..3 indexing imm_eseq applies.  0 or DCP_E*.
 int dcp_encode_sequence(char const *data, int64_t n, uint8_t *out);

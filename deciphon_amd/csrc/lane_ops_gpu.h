@@ -596,6 +596,54 @@ template <> DCP_FN void load_row_q<10>(RowSrc const &r, lu voff, uint32_t soff, 
   out[6] = __uint_as_float(b.z); out[7] = __uint_as_float(b.w); out[8] = __uint_as_float(c.x);
   out[9] = __uint_as_float(c.y);
 }
+
+// ---- the cost-order copy of the rows (dcp_types.h cost_rows_off, host_logic.h dcp_cost_order_col) ----
+// A lane's Q >= 5 floats come in chunks of four and a narrower tail, chunk c from its own lane offset voffc[c]
+// (computed once).  In the canonical rows chunk c of global lane g sits at 16 + 4Qg + 16c: every load of a wave is
+// strided by 4Q bytes and touches about the whole row.  In the copy it sits at 4 (64 Q w + 256 c + e wc) for lane e
+// of wave w, wc = min(4, Q - 4c), behind a 128-byte header: each load reads one contiguous span of 256 wc bytes.
+#define DCP_COST_ORDER 1
+template <int Q> struct DcpRowChunks
+{
+  static constexpr int N = (Q + 3) / 4;
+  static constexpr int width(int c) { return Q - 4 * c < 4 ? Q - 4 * c : 4; }
+};
+
+template <int Q, int W> DCP_FN void row_chunk_offsets(lu lane, bool ordered, lu (&v)[DcpRowChunks<Q>::N])
+{
+  lu const w = lane >> 6, e = lane & 63u;
+#pragma unroll
+  for (int c = 0; c < DcpRowChunks<Q>::N; ++c)
+    v[c] = ordered ? (uint32_t)(4 * DCP_COST_ORDER_HDR) + w * (uint32_t)(256 * Q) + (uint32_t)(1024 * c) +
+                         e * (uint32_t)(4 * DcpRowChunks<Q>::width(c))
+                   : row_lane_offset<Q>(lane) + (uint32_t)(16 * c);
+}
+
+template <int Q, int C = 0>
+DCP_FN void load_row_chunks(RowSrc const &r, lu const (&v)[DcpRowChunks<Q>::N], uint32_t soff, lf (&out)[Q])
+{
+  constexpr int WC = DcpRowChunks<Q>::width(C), q0 = 4 * C;
+  if constexpr (WC == 4)
+  {
+    dcp_u32x4 const a = __builtin_amdgcn_raw_buffer_load_b128(r.rsrc, v[C], soff, 0);
+    out[q0] = __uint_as_float(a.x); out[q0 + 1] = __uint_as_float(a.y);
+    out[q0 + 2] = __uint_as_float(a.z); out[q0 + 3] = __uint_as_float(a.w);
+  }
+  else if constexpr (WC == 3)
+  {
+    dcp_u32x3 const a = __builtin_amdgcn_raw_buffer_load_b96(r.rsrc, v[C], soff, 0);
+    out[q0] = __uint_as_float(a.x); out[q0 + 1] = __uint_as_float(a.y); out[q0 + 2] = __uint_as_float(a.z);
+  }
+  else if constexpr (WC == 2)
+  {
+    dcp_u32x2 const a = __builtin_amdgcn_raw_buffer_load_b64(r.rsrc, v[C], soff, 0);
+    out[q0] = __uint_as_float(a.x); out[q0 + 1] = __uint_as_float(a.y);
+  }
+  else
+    out[q0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r.rsrc, v[C], soff, 0));
+  if constexpr (C + 1 < DcpRowChunks<Q>::N) load_row_chunks<Q, C + 1>(r, v, soff, out);
+}
+
 // one DP-table row plane: the lane's Q values at row[lane*Q ..], rows padded to Kp.
 // Non-temporal stores: tables and checkpoints are written once and read once, by another kernel, 66 GB of them for the
 // headline scan's 2301 hits -- through the L2 they evicted the emission rows every wavefront of the path pass keeps

@@ -122,6 +122,12 @@ template <int Q, int W, bool STORE = false, int POLICY = DCP_SHAPE_POLICY(Q, W)>
   RowSrc rows;
   lu voff;
   uint32_t stride_bytes;
+#ifdef DCP_COST_ORDER
+  // Q >= 5 (not the table-writing kernels): the rows are read chunk by chunk, from the profile's cost-order copy
+  // when it was made for this very shape (dcp_types.h), else from the canonical rows -- the same loads either way
+  static constexpr bool ORDERED = !STORE && Q >= 5;
+  lu voffc[ORDERED ? DcpRowChunks<Q>::N : 1];
+#endif
   DcpCodeRow const *__restrict__ codes;
 
   DcpCodeRow cr; // codes of the next row to fetch, already resident in SGPRs
@@ -136,6 +142,14 @@ template <int Q, int W, bool STORE = false, int POLICY = DCP_SHAPE_POLICY(Q, W)>
     for (int t = 0; t < 5; ++t)
     {
       uint32_t const off = cr.c[t] * stride_bytes;
+#ifdef DCP_COST_ORDER
+      if constexpr (ORDERED)
+      {
+        load_row_hdr(rows, off, nil[t], bgv[t]);
+        load_row_chunks<Q>(rows, voffc, off, em[t]);
+        continue;
+      }
+#endif
       load_row_hdr(rows, off, nil[t], bgv[t]);
       load_row_q<Q>(rows, voff, off, em[t]);
     }
@@ -156,7 +170,20 @@ template <int Q, int W, bool STORE = false, int POLICY = DCP_SHAPE_POLICY(Q, W)>
     lu const lane = g.lane;
     int const Kp = pf.Kp;
     stride_bytes = (uint32_t)(Kp + DCP_ROW_HDR) * 4u;
-    rows = rowsrc_make(pool + pf.rows_off, (uint32_t)DCP_TABLE_SIZE * stride_bytes);
+    int64_t rows_off = pf.rows_off;
+#ifdef DCP_COST_ORDER
+    if constexpr (ORDERED)
+    {
+      bool const copy = pf.cost_rows_off != 0 && pf.cost_shape == DCP_COST_SHAPE(Q, W);
+      if (copy)
+      {
+        rows_off = pf.cost_rows_off;
+        stride_bytes = 4u * (uint32_t)(DCP_COST_ORDER_HDR + 64 * Q * W); // dcp_cost_order_stride
+      }
+      row_chunk_offsets<Q, W>(lane, copy, voffc);
+    }
+#endif
+    rows = rowsrc_make(pool + rows_off, (uint32_t)DCP_TABLE_SIZE * stride_bytes);
     voff = row_lane_offset<Q>(lane);
     codes = code_rows;
     float const *__restrict__ trans = pool + pf.trans_off;

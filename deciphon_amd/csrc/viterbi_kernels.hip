@@ -914,15 +914,16 @@ hipError_t dcp_launch_cost(int cls, DcpLaunch const &a)
 // and no exchange per row, 325 instead of 2 x 242 VALU instructions (K = 520 / 576 / 640: 530 / 585 / 651 -> 715 /
 // 810 / 857 GCUPS).  The engine sorts those windows to the front of their class.
 int dcp_class_narrow_limit(int cls) { return cls == 4 ? 320 : cls == 5 ? 448 : cls == 6 ? 640 : 0; }
+int dcp_class_narrow_q(int cls) { return cls == 4 ? 5 : cls == 5 ? 7 : cls == 6 ? 10 : 0; }
 
 hipError_t dcp_launch_cost_narrow(int cls, DcpLaunch const &a)
 {
   if (a.nprob <= 0) return hipSuccess;
-  switch (cls)
+  switch (dcp_class_narrow_q(cls))
   {
-  case 4: return launch_cost_qw<5, 1>(a);
-  case 5: return launch_cost_qw<7, 1>(a);
-  case 6: return launch_cost_qw<10, 1>(a); // one wavefront on the two-wave layout
+  case 5: return launch_cost_qw<5, 1>(a);
+  case 7: return launch_cost_qw<7, 1>(a);
+  case 10: return launch_cost_qw<10, 1>(a); // one wavefront on the two-wave layout
   default: return hipErrorInvalidValue;
   }
 }

@@ -44,6 +44,7 @@ def _lib():
     L.dcp_partition_size.restype = C.c_long
     L.dcp_window_count.argtypes = [C.c_int64, i32]
     L.dcp_window_count.restype = C.c_int64
+    L.dcp_cost_order_map.argtypes = [i32, i32, vp]
     L.dcp_scan_plan_chunks.argtypes = [i32, vp, i32, vp, C.c_double, C.c_double, C.c_int64, C.c_int64, i32, vp, vp,
                                        C.POINTER(i32)]
     L.dcp_window_setup.argtypes = [C.POINTER(_Window), i32, i32]
@@ -246,6 +247,16 @@ class WindowIter:
 def window_count(seq_size: int, core_size: int) -> int:
     """Windows of the no-hit chain of one (read, profile) pair (what WindowIter walks when nothing hits)."""
     return int(_lib().dcp_window_count(int(seq_size), int(core_size)))
+
+
+def cost_order_map(Q: int, W: int):
+    """(cols int32[64 Q W], row stride in floats): where the cost-order copy of the emission rows keeps position k
+    for the cost kernel of Q positions per lane and W wavefronts (csrc/host_logic.h dcp_cost_order_col)."""
+    cols = np.zeros(64 * Q * W, np.int32)
+    stride = int(_lib().dcp_cost_order_map(int(Q), int(W), cols.ctypes.data_as(C.c_void_p)))
+    if stride <= 0:
+        raise ValueError(f"no cost-order map for Q={Q}, W={W}")
+    return cols, stride
 
 
 def plan_chunks(core_sizes, read_lengths, first_cells: float, later_cells: float, max_pairs: int, max_windows: int):

@@ -76,6 +76,11 @@ int dcp_partition_bounds_of(int n, int32_t const *core_sizes, int nparts, int ba
  * walk for a read of seq_size nucleotides and a profile of core_size nodes, counted in O(1) (0 for an empty
  * read or core_size < 1).  Returns the count. */
 int64_t dcp_window_count(int64_t seq_size, int core_size);
+/* The cost-order copy of the emission rows that the cost kernel of Q positions per lane and W wavefronts reads
+ * (csrc/host_logic.h dcp_cost_order_col): cols[k] receives the column of position k, k < 64*Q*W, counted from the
+ * first column (behind the row's 32-float header), and the function returns the floats of one copy row (0 and
+ * nothing written for Q < 1, W < 1 or Q*W > 64). */
+int dcp_cost_order_map(int Q, int W, int32_t *cols);
 /* How dcp_scan_run cuts profiles x reads into cost batches (csrc/host_logic.h dcp_plan_chunks: the rules).
  * dcp_scan_run plans with first_cells = DCP_SCAN_FIRST_CHUNK_CELLS, later_cells = unlimited (both
  * DECIPHON_HIP_CHUNK_CELLS when that is set), max_pairs = DCP_SCAN_CHUNK_PAIRS and max_windows =
