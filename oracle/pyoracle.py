@@ -1,8 +1,9 @@
 """TEST INFRASTRUCTURE ONLY -- ctypes bindings of the parity oracle.
 
 `Oracle`  : oracle/libdcp_oracle.so, our scalar C restatement (dcp_oracle.c).
-`RefLib`  : oracle/_ref/libdcp_ref.so, the reference's own c-core/viterbi.c
-            compiled unmodified (oracle/Makefile `ref`), when present.
+`RefLib`  : oracle/_ref/libdcp_ref.so, the reference's own c-core/viterbi.c,
+            xtrans.c, trellis.c and window.c compiled unmodified
+            (oracle/Makefile `ref`), when present.
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg import this.
 """
 from __future__ import annotations
@@ -11,6 +12,7 @@ import ctypes as C
 import dataclasses
 import os
 import subprocess
+import sys
 
 import numpy as np
 
@@ -169,12 +171,25 @@ class Oracle:
         return int(self.lib.orc_partition_size(nelems, nparts, idx))
 
 
+# the driver's entry points into the reference's xtrans.c, trellis.c and window.c (oracle/ref_glue.c)
+WALK_FUNCS = ("ref_xtrans", "ref_unzip", "ref_windows")
+
+
 class RefLib:
-    """The reference's own viterbi.c behind a flat-array driver (oracle/ref_glue.c)."""
+    """The reference's own viterbi.c, xtrans.c, trellis.c and window.c behind a flat-array driver (oracle/ref_glue.c).
+    A library built by an older recipe of oracle/Makefile holds only the viterbi.c driver: has_walks is then False and
+    xtrans(), unzip() and windows() are not there."""
 
     @staticmethod
     def available() -> bool:
         return os.path.exists(REF_SO)
+
+    @staticmethod
+    def stale(path: str = REF_SO) -> bool:
+        """True when the library at `path` lacks WALK_FUNCS.  Probed in a child process: a library once loaded into
+        this one would stay loaded, whatever a rebuild then writes."""
+        probe = "import ctypes, sys; L = ctypes.CDLL(sys.argv[1]); [getattr(L, n) for n in sys.argv[2:]]"
+        return subprocess.run([sys.executable, "-c", probe, path, *WALK_FUNCS], capture_output=True).returncode != 0
 
     def __init__(self, path: str = REF_SO):
         L = self.lib = C.CDLL(path)
@@ -190,6 +205,11 @@ class RefLib:
         L.ref_path.argtypes = [C.c_void_p, u8p, C.c_int, u32p, u16p]
         L.ref_bench.argtypes = [C.c_int, f32p, f32p, f32p, f32p, f32p, u8p, i64p, C.c_int, C.c_int, C.c_int, f32p]
         L.ref_bench.restype = C.c_double
+        self.has_walks = all(hasattr(L, name) for name in WALK_FUNCS)
+        if self.has_walks:
+            L.ref_xtrans.argtypes = [C.c_int, C.c_int, C.c_int, f32p]
+            L.ref_unzip.argtypes = [C.c_void_p, C.c_int, C.c_int, i32p, i32p]
+            L.ref_windows.argtypes = [C.c_int, C.c_int, i32p, C.c_int, i32p]
         self.h = C.c_void_p(L.ref_new())
         self.K = 0
 
@@ -227,6 +247,39 @@ class RefLib:
         rc = self.lib.ref_path(self.h, seq, L, xnodes, nodes)
         assert rc == 0
         return xnodes, nodes
+
+    def xtrans(self, seq_size: int, multi_hits: bool, hmmer3_compat: bool) -> np.ndarray:
+        """xtrans_init + xtrans_setup + xtrans_setup_viterbi (c-core/xtrans.c): the 13 values handed to viterbi.c."""
+        xt = np.empty(NUM_XTRANS, dtype=np.float32)
+        rc = self.lib.ref_xtrans(int(seq_size), int(multi_hits), int(hmmer3_compat), xt)
+        assert rc == 0, seq_size
+        return xt
+
+    def unzip(self, L: int):
+        """trellis_unzip (c-core/trellis.c) on the trellis of the last path(), L its length -> (state_ids, seqsizes)."""
+        cap, limit = 2 * L + 2 * self.K + 64, (L + 1) * (self.K + 4) + 8
+        while True:
+            ids = np.empty(cap, dtype=np.int32)
+            sizes = np.empty(cap, dtype=np.int32)
+            n = self.lib.ref_unzip(self.h, L, cap, ids, sizes)
+            if n == -1 and cap < limit:  # the path did not fit: trellis_unzip said DCP_ENOMEM
+                cap = min(4 * cap, limit)
+                continue
+            if n < 0:
+                raise RuntimeError(f"ref_unzip failed ({n})")
+            return ids[:n].copy(), sizes[:n].copy()
+
+    NO_HIT = -(2 ** 31)  # ref_windows: leave the last hit position as it is
+
+    def windows(self, seq_size: int, core_size: int, last_hit_pos) -> np.ndarray:
+        """window_setup / window_next / window_set_last_hit_position (c-core/window.c) -> int32[n][2] of [start, stop).
+        last_hit_pos[i] is set after window i (NO_HIT: not set); its length bounds the number of windows."""
+        pos = np.ascontiguousarray(last_hit_pos, dtype=np.int32)
+        ranges = np.empty(2 * len(pos), dtype=np.int32)
+        n = self.lib.ref_windows(int(seq_size), int(core_size), pos, len(pos), ranges)
+        if n < 0:
+            raise RuntimeError(f"ref_windows failed ({n}): {'too many windows' if n == -1 else 'position out of range'}")
+        return ranges[: 2 * n].reshape(n, 2).copy()
 
     def bench(self, prof: Profile, xts: np.ndarray, seqs: np.ndarray, offsets: np.ndarray, nthreads: int,
               repeat: int = 1):

@@ -4,68 +4,60 @@
  * compiles c-core/viterbi.c (+ error.c, loglevel.c) unmodified, straight from
  * /root/reference, and links them with this file into oracle/_ref/libdcp_ref.so.
  * The same library carries, equally unmodified, the other files of the path
- * that need only libc and the reference's own headers -- partition_size.c,
- * state.c (+ bug.c), disambiguate.c, uppercase.c -- whose functions the tests
- * call directly (tests/test_reference_pins.py).
+ * that need only libc, the reference's own headers and the small imm
+ * interfaces of oracle/imm_shim/ -- partition_size.c, state.c (+ bug.c),
+ * disambiguate.c, uppercase.c, xtrans.c, trellis.c (+ xrealloc.c), window.c
+ * -- whose functions the tests call directly (tests/test_reference_pins.py,
+ * tests/test_reference_unzip.py).
  * Nothing of the reference is copied into this repository.
  *
- * c-core/trellis.c is NOT compiled: it includes the third-party imm_path.h,
- * which this image lacks, so it is unbuildable here.  viterbi.c only needs the
- * five trellis *storage* functions (init/setup/cleanup/seek_xnode/seek_node,
- * declared in the reference's own trellis.h); they are restated below.  All
- * back-pointer arithmetic (viterbi.c cost()/after() and trellis.h
- * trellis_set()) is the reference's own code.  trellis_unzip() is not part of
- * this build; the traceback restatement lives in dcp_oracle.c and is pinned by
- * the reference's committed products.tsv paths.
+ * trellis.c provides the trellis storage viterbi.c writes and trellis_unzip()
+ * (ref_unzip); xtrans.c the special transitions (ref_xtrans); window.c the
+ * window walk (ref_windows).  The one restatement left here is window.c's view
+ * of a sequence: sequence_size() and sequence_slice() over a plain length.
  */
+#include "imm_path.h"
+#include "sequence.h"
 #include "trellis.h"
 #include "viterbi.h"
+#include "window.h"
+#include "xtrans.h"
 
+#include <limits.h>
+#include <math.h>
 #include <omp.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
 
-/* ---- trellis storage, after c-core/trellis.c:14-49,115-123 ----------------- */
-void trellis_init(struct trellis *x)
+/* ---- what the reference's files need from outside them ------------------- */
+/* restated: a sequence is its length here (c-core/sequence.c keeps it in imm_seq) */
+int sequence_size(struct sequence const *x) { return x->imm.seq.size; }
+
+struct sequence sequence_slice(struct sequence const *x, struct imm_range r)
 {
-  x->core_size = 0;
-  x->xnodes = NULL;
-  x->nodes = NULL;
-  x->xnode = NULL;
-  x->node = NULL;
+  struct sequence s = *x;
+  s.imm.seq.size = imm_range_size(r);
+  return s;
 }
 
-int trellis_setup(struct trellis *x, int core_size, int seq_size)
+/* xtrans_dump()'s printer; nothing the tests run calls it */
+void imm_dump_array_f32(size_t size, float const *array, FILE *restrict fp)
 {
-  size_t stages = (size_t)seq_size + 1;
-  x->core_size = core_size;
-  x->xnodes = realloc(x->xnodes, sizeof(*x->xnodes) * stages);
-  x->nodes = realloc(x->nodes, sizeof(*x->nodes) * stages * (size_t)core_size);
-  if (!x->xnodes || !x->nodes)
-  {
-    free(x->xnodes);
-    free(x->nodes);
-    x->xnodes = NULL;
-    x->nodes = NULL;
-    return 20; /* DCP_ENOMEM */
-  }
-  return 0;
+  for (size_t i = 0; i < size; ++i) fprintf(fp, i ? ",%.9g" : "%.9g", (double)array[i]);
 }
 
-void trellis_cleanup(struct trellis *x)
-{
-  free(x->xnodes);
-  free(x->nodes);
-  trellis_init(x);
-}
+/* linked with -Wl,--wrap=viterbi_set_extr_trans: every call from another object
+ * file (xtrans_setup_viterbi, ref_set_xtrans) lands here and goes on to
+ * viterbi.c's own setter; ref_xtrans() records what xtrans.c hands over */
+void __real_viterbi_set_extr_trans(struct viterbi *, enum extr_trans_id, float);
+static _Thread_local float *xt_capture;
 
-void trellis_seek_xnode(struct trellis *x, int stage) { x->xnode = x->xnodes + stage; }
-
-void trellis_seek_node(struct trellis *x, int stage, int core_idx)
+void __wrap_viterbi_set_extr_trans(struct viterbi *v, enum extr_trans_id id, float scalar)
 {
-  x->node = x->nodes + (size_t)stage * x->core_size + core_idx;
+  if (xt_capture && (int)id >= 0 && (int)id < 13) xt_capture[id] = scalar;
+  __real_viterbi_set_extr_trans(v, id, scalar);
 }
 
 /* ---- flat driver ------------------------------------------------------------ */
@@ -244,4 +236,69 @@ double ref_bench(int K, float const *trans, float const *match, float const *nul
   free(codes);
   free(refs);
   return (double)(t1.tv_sec - t0.tv_sec) + 1e-9 * (double)(t1.tv_nsec - t0.tv_nsec);
+}
+
+/* ---- the reference's xtrans.c, trellis.c and window.c ---------------------- */
+/* xtrans_init -> xtrans_setup -> xtrans_setup_viterbi (c-core/thread.c:110-113):
+ * out[13] = what xtrans.c hands to viterbi_set_extr_trans, by enum extr_trans_id */
+int ref_xtrans(int seq_size, int multi_hits, int hmmer3_compat, float *out)
+{
+  if (seq_size <= 0) return -1; /* xtrans_setup's BUG_ON */
+  struct viterbi *v = viterbi_new();
+  if (!v) return -1;
+  for (int i = 0; i < 13; ++i) out[i] = NAN;
+  struct xtrans x;
+  xtrans_init(&x);
+  xtrans_setup(&x, multi_hits != 0, hmmer3_compat != 0, seq_size);
+  xt_capture = out;
+  xtrans_setup_viterbi(&x, v);
+  xt_capture = NULL;
+  viterbi_del(v);
+  return 0;
+}
+
+/* trellis_unzip() on the trellis the last ref_path() left (L: its length).
+ * -> number of steps, -1 when more than `cap` */
+int ref_unzip(void *p, int L, int cap, int32_t *state_ids, int32_t *seqsizes)
+{
+  struct ref *r = p;
+  struct imm_step *steps = malloc(sizeof(*steps) * (size_t)(cap > 0 ? cap : 1));
+  if (!steps) return -1;
+  struct imm_path path = {cap, 0, steps};
+  int rc = trellis_unzip(viterbi_trellis(r->v), L, &path);
+  int n = rc ? -1 : path.nsteps;
+  for (int i = 0; i < n; ++i)
+  {
+    state_ids[i] = steps[i].state_id;
+    seqsizes[i] = steps[i].seqsize;
+  }
+  free(steps);
+  return n;
+}
+
+/* window_setup + window_next over a read of seq_size nucleotides; after window
+ * i, window_set_last_hit_position(last_hit_pos[i]) unless that is INT_MIN (no
+ * hit: the position stays what it was).  ranges[2 i], ranges[2 i + 1] = window
+ * i's [start, stop).  -> number of windows; -1 when more than `cap`; -2 when a
+ * position breaks the precondition window_next BUG_ONs on (-1 <= pos < size). */
+int ref_windows(int seq_size, int core_size, int32_t const *last_hit_pos, int cap, int32_t *ranges)
+{
+  struct sequence seq;
+  memset(&seq, 0, sizeof(seq));
+  seq.imm.seq.size = seq_size;
+  struct window w = window_setup(&seq, core_size);
+  int n = 0;
+  while (window_next(&w))
+  {
+    if (n >= cap) return -1;
+    struct imm_range rg = window_range(&w);
+    ranges[2 * n] = rg.start;
+    ranges[2 * n + 1] = rg.stop;
+    int32_t pos = last_hit_pos[n];
+    ++n;
+    if (pos == INT_MIN) continue;
+    if (pos < -1 || pos >= imm_range_size(rg)) return -2;
+    window_set_last_hit_position(&w, pos);
+  }
+  return n;
 }

@@ -186,11 +186,37 @@ def oracle() -> Oracle:
     return _oracle
 
 
+_ref_checked = False
+
+
 def reflib():
-    """The reference's own viterbi.c (oracle/_ref), or None where it was not built."""
-    if not RefLib.available() and os.path.isdir("/root/reference/c-core"):
-        subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "ref"], check=True)
-    return RefLib() if RefLib.available() else None
+    """The reference's own code (oracle/_ref), or None where it was not built.  Where the reference tree exists, a
+    library missing or left by an older recipe of oracle/Makefile (RefLib.stale) is rebuilt first, once per process;
+    elsewhere an older library serves what it holds, and RefLib.has_walks says whether that includes xtrans.c,
+    trellis.c and window.c."""
+    global _ref_checked
+    if not _ref_checked and os.path.isdir("/root/reference/c-core"):
+        make = ["make", "-s", "-C", os.path.join(ROOT, "oracle"), "ref"]
+        if not RefLib.available():
+            subprocess.run(make, check=True)
+        elif RefLib.stale():  # should the rebuild fail, the older library still serves (see below)
+            subprocess.run(make[:1] + ["-B"] + make[1:], check=False)
+    _ref_checked = True
+    if not RefLib.available():
+        return None
+    r = RefLib()
+    if not r.has_walks:
+        import warnings
+
+        warnings.warn("oracle/_ref was built by an older recipe: the reference's xtrans.c, trellis.c and window.c are "
+                      "checked through the goldens alone")
+    return r
+
+
+def walks_reflib():
+    """reflib() where it holds the reference's xtrans.c, trellis.c and window.c, else None."""
+    r = reflib()
+    return r if r is not None and r.has_walks else None
 
 
 def ref_pins_lib(r):

@@ -65,8 +65,8 @@ def tiled_protein(case) -> dict:
     return synth.tile_protein(seeds(), case["K"], 37 * case["idx"], f"TILE{case['K']}")
 
 
-def build_case(case, orc):
-    """-> (Profile in DP-cost space, read uint8[L], xt float32[13])"""
+def build_case(case, orc, xtrans=None):
+    """-> (Profile in DP-cost space, read uint8[L], xt float32[13]); xt from `xtrans` (default orc.xtrans)"""
     from deciphon_amd import synth
     from oracle.dcp_reader import Protein
 
@@ -88,7 +88,7 @@ def build_case(case, orc):
             dom = synth.mutate(synth.back_translate(cons[a : a + 300]), rng, 0.05, 0.02, 0.02)[: L // 3]
             at = int(frac * L)
             seq[at : at + len(dom)] = dom[: L - at]
-    xt = orc.xtrans(max(L // 3, 1), case["mh"], case["h3"])
+    xt = (xtrans or orc.xtrans)(max(L // 3, 1), case["mh"], case["h3"])
     if quant:
         xt = (np.round(xt / quant) * quant).astype(np.float32)
     return prof, seq, xt

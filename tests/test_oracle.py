@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from dcp_testlib import GOLDEN, bits, random_seq, read_fasta, reflib, synth_profile
+from deciphon_amd import host
 
 sys.path.insert(0, GOLDEN)
 from make_golden import LEAK_CASES, MODES, live_cases, synth_case_params, synth_xt  # noqa: E402
@@ -139,6 +140,8 @@ def test_long_profile_goldens(orc):
             return set()
         ids, sizes = orc.unzip(prof.K, len(seq), xn, nd)
         assert np.array_equal(ids, g["path_ids"][a:b]) and np.array_equal(sizes, g["path_sizes"][a:b]), i
+        hid, hsz = host.unzip(prof.K, len(seq), xn, nd)  # dcp_trellis_unzip: the reference's trellis_unzip's path too
+        assert np.array_equal(hid, ids) and np.array_equal(hsz, sizes), i
         total = path_cost(orc, prof, xt, seq, ids, sizes)
         assert abs(total - float(alt)) <= 1e-4 * max(abs(float(alt)), 1.0), (i, total, float(alt))
         return {int(s) >> 14 if int(s) >> 14 < 3 else int(s) & 0x3FFF for s in ids}
@@ -170,6 +173,8 @@ def test_window_cap_golden(orc):
     ids, sizes = orc.unzip(prof.K, len(seq), xn, nd)
     a, b = int(g["path_off"][0]), int(g["path_off"][1])
     assert np.array_equal(ids, g["path_ids"][a:b]) and np.array_equal(sizes, g["path_sizes"][a:b])
+    hid, hsz = host.unzip(prof.K, len(seq), xn, nd)  # dcp_trellis_unzip
+    assert np.array_equal(hid, ids) and np.array_equal(hsz, sizes)
     total = path_cost(orc, prof, xt, seq, ids, sizes)
     assert abs(total - float(alt)) <= 1e-4 * abs(float(alt))
 
