@@ -1,0 +1,413 @@
+// engine_internal.h -- the engine's state and what its translation units share (engine.cpp, engine_profiles.cpp,
+// engine_cost.cpp, engine_path.cpp).  Everything here but struct dcp_hip has C++ linkage in namespace dcp_engine, which
+// exports.map keeps inside the library.
+#pragma once
+#include "../../include/deciphon_hip.h"
+#include "dcp_db.h"
+#include "dcp_errors.h"
+#include "dcp_types.h"
+#include "host_logic.h"
+#include "viterbi_kernels.h"
+
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <deque>
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <string>
+#include <thread>
+#include <vector>
+
+namespace dcp_engine
+{
+
+template <class T> struct DevBuf
+{
+  T *p = nullptr;
+  size_t cap = 0; // elements
+  ~DevBuf() { release(); }
+  void release()
+  {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+  hipError_t reserve(size_t n)
+  {
+    if (n <= cap) return hipSuccess;
+    release();
+    size_t want = n + n / 8 + 64;
+    hipError_t e = hipMalloc((void **)&p, want * sizeof(T));
+    if (e != hipSuccess)
+    {
+      p = nullptr;
+      return e;
+    }
+    cap = want;
+    return hipSuccess;
+  }
+};
+
+// Pinned host memory for results that come back while other batches are in flight: a device-to-host copy into
+// PAGEABLE memory waits for everything the device has been given (measured: the 19 KB hit list of one batch took
+// 370 ms, the rest of the next batch's cost pass), a copy into pinned memory only for its own stream.
+template <class T> struct PinBuf
+{
+  T *p = nullptr;
+  size_t cap = 0;
+  ~PinBuf()
+  {
+    if (p) (void)hipHostFree(p);
+  }
+  hipError_t reserve(size_t n)
+  {
+    if (n <= cap) return hipSuccess;
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    cap = 0;
+    size_t const want = n + n / 4 + 1024;
+    hipError_t const e = hipHostMalloc((void **)&p, want * sizeof(T), hipHostMallocDefault);
+    if (e != hipSuccess)
+    {
+      p = nullptr;
+      return e;
+    }
+    cap = want;
+    return hipSuccess;
+  }
+};
+
+// DP tables of the fast path pass: chunks that are allocated as slices need them and kept until
+// the engine goes (the driver wipes VRAM that is freed, and an allocation that lands on memory
+// still being wiped waits for it at ~30 GB/s -- scripts/alloc_timing.py; growing without ever
+// freeing never meets that).  place() hands out device addresses, reset() starts a new slice.
+struct TableArena
+{
+  static constexpr size_t CHUNK = (size_t)2 << 30;
+  struct Chunk { unsigned char *p; size_t size, used; };
+  std::vector<Chunk> chunks;
+  size_t held = 0;      // bytes in all chunks
+  size_t placed = 0;    // bytes handed out since reset()
+  double alloc_ms = 0;  // time spent in hipMalloc since reset()
+  size_t cur = 0;
+  ~TableArena()
+  {
+    for (Chunk &c : chunks) (void)hipFree(c.p);
+  }
+  void reset()
+  {
+    for (Chunk &c : chunks) c.used = 0;
+    cur = 0;
+    placed = 0;
+    alloc_ms = 0;
+  }
+  // nullptr when `bytes` more would take the arena past `budget` (or the device is full)
+  unsigned char *place(size_t bytes, size_t budget)
+  {
+    bytes = (bytes + 255) & ~(size_t)255;
+    for (; cur < chunks.size(); ++cur)
+    {
+      Chunk &c = chunks[cur];
+      if (c.size - c.used >= bytes)
+      {
+        unsigned char *at = c.p + c.used;
+        c.used += bytes;
+        placed += bytes;
+        return at;
+      }
+    }
+    size_t want = std::max(bytes, std::min(CHUNK, budget > held ? budget - held : 0));
+    if (held + want > budget)
+    {
+      if (placed != 0) return nullptr; // the slice ends here
+      // a lone table is tried whatever the budget says -- unless the budget is a hard limit
+      // (DECIPHON_HIP_PATH_STRICT=1: the caller then fails with DCP_ENOMEM, as trellis_setup does when realloc fails)
+      char const *strict = getenv("DECIPHON_HIP_PATH_STRICT");
+      if (strict && strict[0] == '1') return nullptr;
+      want = bytes;
+    }
+    auto const t0 = std::chrono::steady_clock::now();
+    unsigned char *p = nullptr;
+    if (hipMalloc((void **)&p, want) != hipSuccess)
+    {
+      (void)hipGetLastError();
+      return nullptr;
+    }
+    double const ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    alloc_ms += ms;
+    if (getenv("DECIPHON_HIP_TIMING")) fprintf(stderr, "TableArena: chunk %zu, %.2f GB in %.1f ms\n", chunks.size(), (double)want / 1e9, ms);
+    chunks.push_back(Chunk{p, want, bytes});
+    held += want;
+    placed += bytes;
+    return p;
+  }
+};
+
+struct HostProfile
+{
+  int K, Kp, Q, W, cls;
+  int pack = -1; // shape of the packed cost kernel (several windows per wavefront), -1: none
+  bool narrow = false; // fits its class with one position per lane less (dcp_class_narrow_limit)
+  int cQ = 0, cW = 0;  // shape of the cost kernel its cost-order copy of the rows is for (host_logic.h); 0: no copy
+  int64_t pool_off; // floats
+  std::string accession;
+};
+
+struct PathResult
+{
+  int K = 0, L = 0;
+  float score = 0;
+  size_t trellis_off = 0;      // bytes into d_trellis, valid when has_trellis
+  bool has_trellis = false;    // the literal path kernel has run for this window
+  bool trellis_on_host = false;
+  // the unzipped path, one word per step: state id (c-core/state.h:9-25) | emission length << 16 -- as the device
+  // wrote it, in the pinned buffer it came back in (dcp_hip::h_steps), or in `owned` when the host unzipped the trellis
+  uint32_t const *steps = nullptr;
+  int32_t nsteps = 0;
+  std::vector<uint32_t> owned;
+};
+
+// a side stream for kernels that run beside others, and the event recorded behind its last launch (struct Fork)
+struct Branch
+{
+  hipStream_t stream = nullptr;
+  hipEvent_t joined = nullptr;
+};
+
+// what the launch functions need of a staged window list: whose share of the lists on the device is whose
+struct StagedPlan
+{
+  int c_begin[DCP_NUM_CLASSES + 1] = {0}; // problems of class c are [c_begin[c], c_begin[c+1])
+  int c_wide[DCP_NUM_CLASSES] = {0};      // ... the narrow profiles' first: [c_begin[c], c_wide[c])
+  int pk_begin[DCP_NUM_PACK_SHAPES + 1] = {0};
+  int pg_begin[DCP_NUM_PACK_SHAPES + 1] = {0};
+  double cells = 0;
+};
+
+} // namespace dcp_engine
+
+using namespace dcp_engine; // for the engine's own files only: nothing else includes this
+
+struct dcp_hip
+{
+  int device = 0;
+  hipStream_t stream = nullptr;
+  hipEvent_t fork_ev = nullptr;
+  // one side stream per kernel class, so that the kernels of different
+  // classes (few problems each in small scans) share the GPU instead of queueing
+  Branch cls_branch[DCP_NUM_CLASSES];
+  Branch pack_branch[DCP_NUM_PACK_SHAPES]; // the packed cost kernels, one stream per shape
+  Branch narrow_branch[DCP_NUM_CLASSES];   // the narrow cost kernels of classes 4..6
+  std::string err;
+
+  // profiles
+  std::vector<HostProfile> profiles;
+  size_t committed = 0; // profiles whose descriptors are published
+  DevBuf<float> d_pool;
+  size_t pool_used = 0; // floats of d_pool holding profiles
+  int load_chunks = 0;  // staging chunks the last dcp_hip_load_dcp went through
+  DevBuf<DcpProfileDev> d_profiles;
+
+  // sequences
+  std::vector<int64_t> seq_off, row_off;
+  DevBuf<unsigned char> d_nt;
+  DevBuf<int64_t> d_seq_off, d_row_off;
+  DevBuf<DcpCodeRow> d_rows;
+
+  // mode
+  bool mode_set = false;
+  bool multi_hits = true, hmmer3_compat = false;
+  DevBuf<float> d_xt;
+  int xt_rows = 0;
+  std::vector<float> xt_override; // [rows][DCP_XT_STRIDE], dcp_hip_set_xtrans_table
+
+  // problems / results.  Three sets of window lists and result buffers ("banks"): 0 and 1 for cost passes -- two
+  // batches may be outstanding at once (dcp_hip_cost_hits_begin / _end), the second queued behind the first on the same
+  // kernel streams so that the GPU never drains between them -- and 2 for the path pass, which has its own streams too
+  // (path_set) and may run while cost batches are in flight.  `cur` is the bank the code below works on.
+  struct Bank
+  {
+    DevBuf<DcpProblem> d_problems;
+    DevBuf<DcpPack> d_packs;         // cost pass: windows of short profiles, several per wavefront
+    DevBuf<int2> d_pack_groups;      // ... and, for four-lane groups, the packs of one profile that share a workgroup
+    DevBuf<float> d_out;             // (null, alt) per window
+    DevBuf<uint32_t> d_hits;         // dcp_hip_cost_hits: count, then (window, lrt bits) pairs
+    DevBuf<float> d_ring;            // strip class (K > 4096): the rings of folded rows, one per workgroup in flight
+    PinBuf<uint32_t> h_hits;         // ... on the host: the whole list comes back behind the filter
+    hipEvent_t done_ev = nullptr;    // an outstanding batch: recorded behind its last device operation
+    int n = -1;                      // windows of the outstanding batch, -1: none
+    // the lists go up from pinned memory: a copy from PAGEABLE memory waits for everything the device has been given
+    // (the upload of a batch begun while another was in flight took as long as the rest of that batch's cost pass)
+    PinBuf<DcpProblem> h_problems;
+    PinBuf<DcpPack> h_packs;
+    PinBuf<int2> h_groups;
+    hipEvent_t up_ev = nullptr; // recorded behind the uploads: the pinned lists are not rewritten before
+    bool up_pending = false;
+  };
+  Bank bank[3];
+  int cur = 0;
+  int outstanding[2] = {-1, -1}; // banks of the batches begun and not yet ended, oldest first
+  hipStream_t upload_stream = nullptr;
+  // the path pass's own streams and events, swapped with stream / fork_ev / cls_branch for its duration
+  struct StreamSet
+  {
+    hipStream_t stream = nullptr;
+    hipEvent_t fork_ev = nullptr;
+    Branch cls_branch[DCP_NUM_CLASSES];
+  } path_set;
+  DevBuf<int64_t> d_aux;           // strip class, literal path pass: table and scratch addresses per window
+  DevBuf<int64_t> d_ckpt_addr;     // fast path pass: checkpoint address per window
+  DevBuf<DcpTraceState> d_trace;   // fast path pass: where each window's traceback stands between blocks
+  TableArena tables;               // DP tables of the fast path pass
+  std::vector<int64_t> table_addr; // per window of the slice being staged (device addresses)
+  std::vector<int> path_order;     // fast path pass: request windows, slowest first
+  std::vector<dcp_hip_window> path_sorted;
+  DevBuf<unsigned char> d_trellis; // trellises of the literal path pass
+  std::vector<dcp_hip_window> path_wins; // the windows of the last dcp_hip_path
+  int path_redone = 0;                   // how many of them needed the literal pass
+  int path_group = 1;                    // blocks of a window computed side by side in the fast path pass
+  PinBuf<int32_t> h_nsteps;        // path pass results on the host (pinned: see PinBuf)
+  // the steps of a dcp_hip_path call stay where the copies from the device put them (PathResult::steps points there):
+  // one pinned buffer per slice of the fast pass and one for the literal pass, reused by the next call
+  std::deque<PinBuf<uint32_t>> h_steps;
+  size_t h_steps_used = 0;
+  PinBuf<float> h_out;
+  DevBuf<uint32_t> d_steps, d_compact;
+  DevBuf<int64_t> d_step_off, d_compact_off;
+  DevBuf<int32_t> d_nsteps;
+  std::vector<std::vector<unsigned char>> host_trellis; // fetched on demand, one per window
+  std::vector<PathResult> paths;
+  StagedPlan staged; // dcp_hip_stage: the list itself stays in bank 0's device buffers
+  int staged_n = -1;
+  bool staged_ran = false; // a dcp_hip_run_staged with reps > 0 has filled d_out since the dcp_hip_stage
+
+  // Input generation: moves with every accepted change of the profiles, sequences, mode or xtrans override.  The
+  // staged list and the path results remember the generation they were made under; dcp_hip_run_staged /
+  // _fetch_staged and dcp_hip_path_trellis (which recomputes) refuse once it has moved.
+  uint64_t gen = 0;
+  uint64_t staged_gen = 0;
+  uint64_t path_gen = UINT64_MAX; // UINT64_MAX: the last dcp_hip_path failed or there was none
+};
+
+#define BK(x) ((x)->bank[(x)->cur])
+
+namespace dcp_engine
+{
+
+inline int fail(dcp_hip *x, int rc, char const *what, hipError_t e = hipSuccess)
+{
+  char buf[256];
+  if (e != hipSuccess)
+    snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
+  else
+    snprintf(buf, sizeof buf, "%s", what);
+  x->err = buf;
+  return rc;
+}
+
+#define HIP_TRY(x, call, rc)                                                   \
+  do                                                                           \
+  {                                                                            \
+    hipError_t e_ = (call);                                                    \
+    if (e_ != hipSuccess) return fail((x), (rc), #call, e_);                   \
+  } while (0)
+
+// Kernels that run side by side: each on a branch that waits for fork_ev, recorded on the stream they all come behind;
+// x->stream waits for every branch that was used.  Not forking, everything stays on x->stream and these do nothing.
+struct Fork
+{
+  dcp_hip *x;
+  bool on;
+  std::vector<hipEvent_t> joins;
+  Fork(dcp_hip *x_, bool on_) : x(x_), on(on_) {}
+  int begin(hipStream_t origin)
+  {
+    if (on) HIP_TRY(x, hipEventRecord(x->fork_ev, origin), DCP_EFUNCUSE);
+    return 0;
+  }
+  // a's launches go to b
+  int enter(Branch const &b, DcpLaunch &a)
+  {
+    if (!on) return 0;
+    a.stream = b.stream;
+    HIP_TRY(x, hipStreamWaitEvent(a.stream, x->fork_ev, 0), DCP_EFUNCUSE);
+    return 0;
+  }
+  // b has had its last launch
+  int leave(Branch const &b)
+  {
+    if (!on) return 0;
+    HIP_TRY(x, hipEventRecord(b.joined, b.stream), DCP_EFUNCUSE);
+    joins.push_back(b.joined);
+    return 0;
+  }
+  // after the last launch of all (see launch_cost_all)
+  int join()
+  {
+    for (hipEvent_t ev : joins) HIP_TRY(x, hipStreamWaitEvent(x->stream, ev, 0), DCP_EFUNCUSE);
+    return 0;
+  }
+};
+
+// DECIPHON_HIP_TIMING=1: phase times on stderr.  lap() = ms since the last one, the work given to `stream` included
+// (it synchronises; nullptr: host time only)
+struct Stopwatch
+{
+  bool on;
+  hipStream_t stream;
+  std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+  std::string line; // " <what> <ms> ms" of every named lap
+  explicit Stopwatch(hipStream_t s, bool wanted = true) : on(wanted && getenv("DECIPHON_HIP_TIMING") != nullptr), stream(s) {}
+  double lap()
+  {
+    if (!on) return 0;
+    if (stream) (void)hipStreamSynchronize(stream);
+    auto const now = std::chrono::steady_clock::now();
+    double const ms = std::chrono::duration<double, std::milli>(now - t).count();
+    t = now;
+    return ms;
+  }
+  void lap(char const *what)
+  {
+    if (!on) return;
+    char buf[64];
+    snprintf(buf, sizeof buf, " %s %.1f ms", what, lap());
+    line += buf;
+  }
+};
+
+struct Staged : StagedPlan
+{
+  std::vector<DcpProblem> problems; // sorted by (class, profile); cost pass: without the packed ones
+  std::vector<DcpPack> packs;       // cost pass: sorted by (shape, profile), pk_begin[s] = the first of shape s
+  std::vector<int2> pack_groups;    // shapes with an LDS variant: {first pack, count} per workgroup, from pg_begin[s]
+  size_t arena_bytes = 0;
+  Staged() = default;
+  Staged(Staged const &) = delete;
+  Staged &operator=(Staged const &) = delete;
+};
+
+enum ArenaKind { ARENA_NONE, ARENA_TRELLIS, ARENA_TABLE };
+
+// DP table of one window: float specials[(L+1)][8], float cells[(L+1)][3][Kp] (traceback.h)
+inline size_t table_bytes(int L, int Kp) { return ((size_t)L + 1) * (DCP_SP_STRIDE + 3 * (size_t)Kp) * 4; }
+
+// validates windows and builds the device problem list in the current bank
+// (origin: the stream the lists are uploaded on -- x->stream unless a batch is begun asynchronously)
+int stage(dcp_hip *x, int n, dcp_hip_window const *w, ArenaKind arena_kind, Staged &st, hipStream_t origin = nullptr);
+DcpLaunch launch_args(dcp_hip *x, StagedPlan const &st, int c);
+int launch_all(dcp_hip *x, StagedPlan const &st, bool path);
+int launch_cost_all(dcp_hip *x, StagedPlan const &st, hipStream_t origin = nullptr, int reps = 1);
+
+// batches begun and not ended
+inline int outstanding_batches(dcp_hip const *x) { return (x->outstanding[0] >= 0) + (x->outstanding[1] >= 0); }
+
+inline int refuse_outstanding(dcp_hip *x)
+{
+  return fail(x, DCP_EFUNCUSE, "cost batches are outstanding (dcp_hip_cost_hits_begin): end them first");
+}
+
+} // namespace dcp_engine

@@ -1,0 +1,367 @@
+// engine_profiles.cpp -- the engine's profiles: add, load, commit, clear, and the cost-order staging.
+#include "engine_internal.h"
+
+extern "C" {
+
+// ---- profiles: HBM is the only resident copy ---------------------------------------
+// A profile is laid out on the host in a staging buffer (rows | trans, +inf padded) and
+// copied behind the profiles already resident; nothing Pfam-sized is ever held twice.
+
+// rows | trans, rounded up to 128 bytes: every profile, and the cost-order copy behind its tables, starts on a line
+static size_t canonical_floats(int Kp)
+{
+  size_t const floats = (size_t)DCP_TABLE_SIZE * ((size_t)Kp + DCP_ROW_HDR) + (size_t)DCP_NUM_TRANS * (size_t)Kp;
+  return (floats + 31) & ~(size_t)31;
+}
+
+static size_t profile_floats(HostProfile const &hp)
+{
+  size_t const copy = hp.cQ ? (size_t)DCP_TABLE_SIZE * (size_t)dcp_cost_order_stride(hp.cQ, hp.cW) : 0;
+  return canonical_floats(hp.Kp) + copy;
+}
+
+// The cost-order copy (host_logic.h) of the staged rows, behind the profile's canonical tables, for the profiles whose
+// default cost kernel is a narrow one (dcp_launch_cost_narrow) that gains from it: (5,1) and (10,1), K = 257..320 and
+// 513..640.  Their tail chunks of one and two floats were the most strided loads; per class they run 7-10 % and 6-8 %
+// faster on the copy, while (6,1), (7,1), (8,1) and (6,2) do not move (profiles/r04_cost_order_ab.txt) -- no copy there.
+// Only dcp_cost_kernel<5,1> and <10,1> read it: every other kernel has a shape of its own (the checkpoint and block
+// kernels of the path pass run the class shape) and reads the canonical rows.
+// DECIPHON_HIP_COST_ORDER, read at ingest: 0 = no copies; "poison" = copies, and the canonical match columns of those
+// profiles staged as 0 (a test's proof that the narrow kernels read the copy: their scores stay the oracle's).
+static bool cost_order_pays(int Q, int W) { return W == 1 && (Q == 5 || Q == 10); }
+
+static void cost_order_shape(HostProfile &hp)
+{
+  hp.cQ = hp.cW = 0;
+  char const *e = getenv("DECIPHON_HIP_COST_ORDER");
+  if (!hp.narrow || (e && e[0] == '0')) return;
+  int const q = dcp_class_narrow_q(hp.cls);
+  if (!cost_order_pays(q, 1)) return;
+  hp.cQ = q;
+  hp.cW = 1;
+}
+
+static void stage_cost_order(HostProfile const &hp, float *staged)
+{
+  if (!hp.cQ) return;
+  dcp_cost_order_rows(hp.cQ, hp.cW, hp.K, hp.Kp, staged, staged + canonical_floats(hp.Kp));
+  char const *e = getenv("DECIPHON_HIP_COST_ORDER");
+  if (e && strcmp(e, "poison") == 0)
+    for (int c = 0; c < DCP_TABLE_SIZE; ++c)
+      memset(staged + (size_t)c * ((size_t)hp.Kp + DCP_ROW_HDR) + DCP_ROW_HDR, 0, sizeof(float) * (size_t)hp.K);
+}
+
+static int describe(dcp_hip *x, int K, char const *accession, HostProfile &hp)
+{
+  if (K < 1 || K > DCP_MODEL_MAX) return fail(x, DCP_ELARGECORESIZE, "core size out of range");
+  int const cls = dcp_class_of(K);
+  if (cls < 0) return fail(x, DCP_ELARGECORESIZE, "core size beyond DCP_MAX_CORE_SIZE (16383: state ids keep 14 bits for k + 1)");
+  hp.K = K;
+  hp.cls = cls;
+  dcp_class_shape(cls, &hp.Q, &hp.W);
+  hp.Kp = 64 * hp.Q * hp.W;
+  if (cls == DCP_STRIP_CLASS) hp.Kp *= (K + hp.Kp - 1) / hp.Kp; // whole strips
+  hp.pool_off = 0;
+  hp.accession = accession ? accession : "";
+  hp.narrow = K <= dcp_class_narrow_limit(cls);
+  cost_order_shape(hp);
+  hp.pack = dcp_pack_shape_of(K);
+  if (hp.pack >= 0)
+  {
+    int pq = 0, ps = 0;
+    dcp_pack_shape(hp.pack, &pq, &ps);
+    if (hp.W != 1 || ps * pq > hp.Kp) hp.pack = -1; // the shape reads S * Q columns of a row
+  }
+  return 0;
+}
+
+// grows the device pool to `floats`, keeping what is resident
+static int ensure_pool(dcp_hip *x, size_t floats)
+{
+  if (floats <= x->d_pool.cap) return 0;
+  HIP_TRY(x, hipStreamSynchronize(x->stream), DCP_EFUNCUSE);
+  DevBuf<float> bigger;
+  HIP_TRY(x, bigger.reserve(std::max(floats, x->d_pool.cap + x->d_pool.cap / 2)), DCP_ENOMEM);
+  if (x->pool_used)
+    HIP_TRY(x, hipMemcpy(bigger.p, x->d_pool.p, x->pool_used * sizeof(float), hipMemcpyDeviceToDevice), DCP_EFUNCUSE);
+  x->d_pool.release();
+  x->d_pool.p = bigger.p;
+  x->d_pool.cap = bigger.cap;
+  bigger.p = nullptr;
+  bigger.cap = 0;
+  return 0;
+}
+
+// one profile from a host staging buffer to the end of the pool
+static int push_profile(dcp_hip *x, HostProfile hp, std::vector<float> const &staged, int *index)
+{
+  int rc = ensure_pool(x, x->pool_used + staged.size());
+  if (rc) return rc;
+  hp.pool_off = (int64_t)x->pool_used;
+  HIP_TRY(x, hipMemcpy(x->d_pool.p + x->pool_used, staged.data(), staged.size() * sizeof(float), hipMemcpyHostToDevice),
+          DCP_EFUNCUSE);
+  x->pool_used += staged.size();
+  if (index) *index = (int)x->profiles.size();
+  x->profiles.push_back(hp);
+  ++x->gen;
+  return 0;
+}
+
+// The kernels take E_l = min_k M_l[k] (viterbi_body.h) and bound what a delete run can carry across a
+// wavefront (CostWave::row): both need the delete costs MD, DD to be non-negative, which -log-probabilities
+// are.  Anything else (a positive log-probability in a corrupt file, a hand-made table) is refused.
+static bool delete_costs_ok(float const *trans, int K, int Kp)
+{
+  for (int k = 0; k < K; ++k)
+    if (!(trans[(size_t)DCP_MD * Kp + k] >= 0.0f) || !(trans[(size_t)DCP_DD * Kp + k] >= 0.0f)) return false;
+  return true;
+}
+
+int dcp_hip_add_profile(struct dcp_hip *x, int K, float const *trans, float const *match, float const *null_cost,
+                        float const *bg_cost, int *index)
+{
+  if (!x || !trans || !match || !null_cost || !bg_cost) return DCP_EFUNCUSE;
+  if (outstanding_batches(x)) return refuse_outstanding(x);
+  HIP_TRY(x, hipSetDevice(x->device), DCP_EFUNCUSE);
+  HostProfile hp;
+  int rc = describe(x, K, nullptr, hp);
+  if (rc) return rc;
+  int const Kp = hp.Kp;
+  size_t const stride = (size_t)Kp + DCP_ROW_HDR;
+  std::vector<float> buf(profile_floats(hp), INFINITY);
+  float *r = buf.data();
+  float *t = r + (size_t)DCP_TABLE_SIZE * stride;
+  for (int id = 0; id < DCP_NUM_TRANS; ++id) memcpy(t + (size_t)id * Kp, trans + (size_t)id * K, sizeof(float) * K);
+  if (!delete_costs_ok(t, K, Kp)) return fail(x, DCP_EFUNCUSE, "negative (or NaN) delete cost: costs are -log-probabilities");
+  for (int c = 0; c < DCP_TABLE_SIZE; ++c)
+  {
+    float *hdr = r + (size_t)c * stride;
+    hdr[0] = null_cost[c];
+    hdr[1] = bg_cost[c];
+    hdr[2] = hdr[3] = 0.0f;
+    memcpy(hdr + DCP_ROW_HDR, match + (size_t)c * K, sizeof(float) * K);
+  }
+  stage_cost_order(hp, r);
+  return push_profile(x, hp, buf, index);
+}
+
+int dcp_hip_add_protein(struct dcp_hip *x, int K, float const *node_trans, float const *node_emission,
+                        float const *BMk, float const *null_lprob, float const *bg_lprob, int *index)
+{
+  if (!x || !node_trans || !node_emission || !BMk || !null_lprob || !bg_lprob) return DCP_EFUNCUSE;
+  if (outstanding_batches(x)) return refuse_outstanding(x);
+  HIP_TRY(x, hipSetDevice(x->device), DCP_EFUNCUSE);
+  HostProfile hp;
+  int rc = describe(x, K, nullptr, hp);
+  if (rc) return rc;
+  std::vector<float> buf(profile_floats(hp), INFINITY);
+  float *r = buf.data();
+  float *t = r + (size_t)DCP_TABLE_SIZE * ((size_t)hp.Kp + DCP_ROW_HDR);
+  dcp_setup_profile(K, hp.Kp, node_trans, node_emission, BMk, null_lprob, bg_lprob, t, r);
+  if (!delete_costs_ok(t, K, hp.Kp)) return fail(x, DCP_EFDATA, "positive (or NaN) delete log-probability in the protein");
+  stage_cost_order(hp, r);
+  return push_profile(x, hp, buf, index);
+}
+
+// Streams proteins [first, first+count) of a pressed database into HBM: core sizes are read
+// first (so the pool is sized once), then the proteins are unpacked and transposed into
+// code-major rows by up to 16 host threads, chunk by chunk, into two pinned staging buffers whose
+// H2D copies overlap the unpacking of the next chunk.
+int dcp_hip_load_dcp(struct dcp_hip *x, char const *path, int first, int count)
+{
+  if (!x || !path) return DCP_EFUNCUSE;
+  if (outstanding_batches(x)) return refuse_outstanding(x);
+  HIP_TRY(x, hipSetDevice(x->device), DCP_EFUNCUSE);
+  DcpDbReader db;
+  int rc = db.open(path);
+  if (rc) return fail(x, rc, "cannot open database");
+  int const N = db.num_proteins();
+  if (first < 0 || first > N) return fail(x, DCP_EINVALPART, "first protein out of range");
+  int const last = count < 0 ? N : std::min(N, first + count);
+  int const n = last - first;
+  if (n <= 0)
+  {
+    ++x->gen; // nothing to read, but a successful load ends what was computed before it, as every other does
+    return 0;
+  }
+
+  std::vector<HostProfile> hps((size_t)n);
+  std::vector<size_t> off((size_t)n + 1, 0);
+  for (int i = 0; i < n; ++i)
+  {
+    int K = 0;
+    std::string acc;
+    if ((rc = db.read_protein_head(first + i, K, acc))) return fail(x, rc, "cannot read protein");
+    if ((rc = describe(x, K, acc.c_str(), hps[(size_t)i]))) return rc;
+    off[(size_t)i + 1] = off[(size_t)i] + profile_floats(hps[(size_t)i]);
+  }
+  if ((rc = ensure_pool(x, x->pool_used + off[(size_t)n]))) return rc;
+
+  // staging chunks of 256 MiB; DECIPHON_HIP_STAGE_MB shrinks them (never below one profile of the largest
+  // size present), which is how the tests drive a small database through many chunks
+  size_t chunk_floats = std::max<size_t>((size_t)64 << 20, canonical_floats(DCP_MAX_CORE_SIZE));
+  if (char const *e = getenv("DECIPHON_HIP_STAGE_MB"))
+  {
+    size_t largest = 0;
+    for (int i = 0; i < n; ++i) largest = std::max(largest, off[(size_t)i + 1] - off[(size_t)i]);
+    chunk_floats = std::max<size_t>(((size_t)std::max(atol(e), 1L) << 20) / sizeof(float), largest);
+  }
+  int chunks = 0;
+  float *stage[2] = {nullptr, nullptr};
+  hipEvent_t done[2] = {nullptr, nullptr};
+  bool busy[2] = {false, false};
+  auto cleanup = [&]() {
+    (void)hipStreamSynchronize(x->stream);
+    for (int b = 0; b < 2; ++b)
+    {
+      if (stage[b]) (void)hipHostFree(stage[b]);
+      if (done[b]) (void)hipEventDestroy(done[b]);
+    }
+  };
+  for (int b = 0; b < 2; ++b)
+  {
+    if (hipHostMalloc((void **)&stage[b], std::min(chunk_floats, off[(size_t)n]) * sizeof(float), hipHostMallocDefault) !=
+            hipSuccess ||
+        hipEventCreateWithFlags(&done[b], hipEventDisableTiming) != hipSuccess)
+    {
+      cleanup();
+      return fail(x, DCP_ENOMEM, "cannot allocate pinned staging buffers");
+    }
+  }
+  int b = 0;
+  for (int i0 = 0; i0 < n;)
+  {
+    int i1 = i0 + 1;
+    while (i1 < n && off[(size_t)i1 + 1] - off[(size_t)i0] <= chunk_floats) ++i1;
+    if (busy[b] && hipEventSynchronize(done[b]) != hipSuccess)
+    {
+      cleanup();
+      return fail(x, DCP_EFUNCUSE, "staging copy failed");
+    }
+    float *buf = stage[b];
+    // plain threads, joined per chunk: no runtime is left spinning next to the HIP callbacks
+    std::atomic<int> next_protein{i0}, bad{0};
+    auto work = [&]() {
+      DcpProtein p;
+      for (int i = next_protein.fetch_add(1); i < i1; i = next_protein.fetch_add(1))
+      {
+        int r = db.read_protein(first + i, p);
+        if (r || p.core_size != hps[(size_t)i].K)
+        {
+          int expected = 0;
+          bad.compare_exchange_strong(expected, r ? r : DCP_EFDATA);
+          continue;
+        }
+        float *rows = buf + (off[(size_t)i] - off[(size_t)i0]);
+        float *trans = rows + (size_t)DCP_TABLE_SIZE * ((size_t)hps[(size_t)i].Kp + DCP_ROW_HDR);
+        dcp_setup_profile(p.core_size, hps[(size_t)i].Kp, p.trans.data(), p.emission.data(), p.BMk.data(),
+                          p.null_emission.data(), p.bg_emission.data(), trans, rows);
+        if (!delete_costs_ok(trans, p.core_size, hps[(size_t)i].Kp))
+        {
+          int expected = 0;
+          bad.compare_exchange_strong(expected, DCP_EFDATA); // a positive delete log-probability
+        }
+        stage_cost_order(hps[(size_t)i], rows);
+      }
+    };
+    {
+      unsigned nthreads = std::min<unsigned>({std::max(1u, std::thread::hardware_concurrency()), 16u, (unsigned)(i1 - i0)});
+      std::vector<std::thread> pool;
+      for (unsigned t = 1; t < nthreads; ++t) pool.emplace_back(work);
+      work();
+      for (std::thread &t : pool) t.join();
+    }
+    if (bad)
+    {
+      cleanup();
+      return fail(x, bad, "cannot read protein");
+    }
+    size_t const floats = off[(size_t)i1] - off[(size_t)i0];
+    if (hipMemcpyAsync(x->d_pool.p + x->pool_used + off[(size_t)i0], buf, floats * sizeof(float), hipMemcpyHostToDevice,
+                       x->stream) != hipSuccess ||
+        hipEventRecord(done[b], x->stream) != hipSuccess)
+    {
+      cleanup();
+      return fail(x, DCP_EFUNCUSE, "staging copy failed");
+    }
+    busy[b] = true;
+    b ^= 1;
+    i0 = i1;
+    ++chunks;
+  }
+  cleanup();
+  x->load_chunks = chunks;
+  for (int i = 0; i < n; ++i)
+  {
+    hps[(size_t)i].pool_off = (int64_t)(x->pool_used + off[(size_t)i]);
+    x->profiles.push_back(hps[(size_t)i]);
+  }
+  x->pool_used += off[(size_t)n];
+  ++x->gen;
+  return 0;
+}
+
+int dcp_hip_num_profiles(struct dcp_hip const *x) { return x ? (int)x->profiles.size() : 0; }
+
+int dcp_hip_load_chunks(struct dcp_hip const *x) { return x ? x->load_chunks : 0; }
+
+int64_t dcp_hip_pool_bytes(struct dcp_hip const *x) { return x ? (int64_t)(x->pool_used * sizeof(float)) : 0; }
+
+int dcp_hip_profile_core_size(struct dcp_hip const *x, int i)
+{
+  if (!x || i < 0 || i >= (int)x->profiles.size()) return -1;
+  return x->profiles[(size_t)i].K;
+}
+
+char const *dcp_hip_profile_accession(struct dcp_hip const *x, int i)
+{
+  if (!x || i < 0 || i >= (int)x->profiles.size()) return nullptr;
+  return x->profiles[(size_t)i].accession.c_str();
+}
+
+int dcp_hip_commit_profiles(struct dcp_hip *x)
+{
+  if (!x) return DCP_EFUNCUSE;
+  if (outstanding_batches(x)) return refuse_outstanding(x);
+  HIP_TRY(x, hipSetDevice(x->device), DCP_EFUNCUSE);
+  ++x->gen; // even when there is nothing new to publish (the header: every accepted commit)
+  if (x->committed == x->profiles.size()) return 0;
+  // the tables are already in HBM; what is published here are the profile descriptors
+  HIP_TRY(x, hipStreamSynchronize(x->stream), DCP_EFUNCUSE);
+  std::vector<DcpProfileDev> dev(x->profiles.size());
+  for (size_t i = 0; i < dev.size(); ++i)
+  {
+    HostProfile const &hp = x->profiles[i];
+    dev[i].K = hp.K;
+    dev[i].Kp = hp.Kp;
+    dev[i].Q = hp.Q;
+    dev[i].W = hp.W;
+    dev[i].rows_off = hp.pool_off;
+    dev[i].trans_off = dev[i].rows_off + (int64_t)DCP_TABLE_SIZE * (hp.Kp + DCP_ROW_HDR);
+    dev[i].cost_rows_off = hp.cQ ? hp.pool_off + (int64_t)canonical_floats(hp.Kp) : 0;
+    dev[i].cost_shape = hp.cQ ? DCP_COST_SHAPE(hp.cQ, hp.cW) : 0;
+  }
+  HIP_TRY(x, x->d_profiles.reserve(dev.size()), DCP_ENOMEM);
+  HIP_TRY(x, hipMemcpyAsync(x->d_profiles.p, dev.data(), dev.size() * sizeof(DcpProfileDev), hipMemcpyHostToDevice,
+                            x->stream),
+          DCP_EFUNCUSE);
+  HIP_TRY(x, hipStreamSynchronize(x->stream), DCP_EFUNCUSE);
+  x->committed = x->profiles.size();
+  return 0;
+}
+
+void dcp_hip_clear_profiles(struct dcp_hip *x)
+{
+  if (!x) return;
+  if (outstanding_batches(x))
+  {
+    (void)refuse_outstanding(x); // void in the ABI: the refusal shows in dcp_hip_strerror and num_profiles
+    return;
+  }
+  ++x->gen;
+  x->pool_used = 0;
+  x->profiles.clear();
+  x->committed = 0;
+}
+
+} // extern "C"

@@ -3,10 +3,9 @@
 #include "dcp_types.h"
 #include <hip/hip_runtime.h>
 
-// kernel classes by padded size Kp (dcp_class_of / dcp_class_shape in viterbi_kernels.hip):
+// kernel classes by padded size Kp (dcp_class_of; every class's kernel shapes: DCP_CLASS_TABLE, viterbi_kernels.hip):
 //   0..3: Kp = 64..256, one wavefront, 1..4 positions per lane
-//   4..10: Kp = 384, 512, 768, 1024, 1536, 2048, 4096; cost kernels (6,1) (8,1) (6,2) (4,4) (6,4) (8,4) (8,8),
-//          pass-by-pass path kernel (3,2) (4,2) (3,4) (4,4) (3,8) (4,8) (4,16)
+//   4..10: Kp = 384, 512, 768, 1024, 1536, 2048, 4096, several wavefronts or more positions per lane
 //   11:    4096 < K <= 16383, strip by strip
 #define DCP_NUM_CLASSES 12
 #define DCP_STRIP_CLASS 11      // K > 4096: strips of DCP_STRIP_POSITIONS, state ring in HBM (StripWave)
@@ -19,9 +18,8 @@ int dcp_class_of(int K);                      // -1 when K is not covered
 void dcp_class_shape(int cls, int *Q, int *W);
 
 // Several windows per wavefront (viterbi_pack.h), cost pass of short profiles: shape i runs groups of S lanes
-// with Q positions per lane, (S - 1) * Q positions at most -- (4,1) (4,2) (4,4) (8,2) (8,4) (16,2) (16,3) (16,4)
-// (32,2) (32,3) (32,4): K <= 3, 6, 12, 14, 28, 30, 45, 60, 62, 93, 124.  The tables keep the layout of the class
-// the profile belongs to.
+// with Q positions per lane, (S - 1) * Q positions at most (DCP_PACK_TABLE, viterbi_kernels.hip: K <= 3 .. 124).
+// The tables keep the layout of the class the profile belongs to.
 #define DCP_NUM_PACK_SHAPES 11
 int dcp_pack_shape_of(int K); // -1: no shape holds K
 void dcp_pack_shape(int shape, int *Q, int *S);

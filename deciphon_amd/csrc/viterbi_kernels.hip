@@ -837,12 +837,47 @@ static hipError_t launch_cost_qw(DcpLaunch const &a)
   return hipGetLastError();
 }
 
-template <int Q, int W> static hipError_t launch_path_qw(DcpLaunch const &a)
+// ---- the kernel classes below the strip class, each written once: class, (Q, W) of the cost kernels (cost, cost +
+// checkpoints, cost + store, blocked path), (Q, W) of the pass-by-pass path kernel on the same padded layout ----
+// Classes 0..3 are one wavefront of 1..4 positions per lane.  The cost kernels run the padded sizes 384 .. 4096 with 6
+// or 8 positions per lane, which halves or quarters the wavefronts that meet at the row barrier; 8 per lane fits 256
+// VGPRs (two waves per SIMD) only with the transition arrays parked in LDS between their uses (CostWave::STASH).
+// Measured against the 3/4-per-lane shapes on Pfam-structured tables: K=384 639 -> 857 GCUPS, 512 674 -> 884,
+// 768 517 -> 691, 1536 328 -> 593, 2048 427 -> 548, 4096 190 -> 337; (8,2) for 1024 brought nothing over (4,4).  The
+// pass-by-pass path kernel keeps at most 4 per lane: (3, 2W) / (4, 2W) where the cost kernels have (6, W) / (8, W).
+#define DCP_CLASS_TABLE(X) \
+  X(0, 1, 1, 1, 1) \
+  X(1, 2, 1, 2, 1) \
+  X(2, 3, 1, 3, 1) \
+  X(3, 4, 1, 4, 1) \
+  X(4, 6, 1, 3, 2) \
+  X(5, 8, 1, 4, 2) \
+  X(6, 6, 2, 3, 4) \
+  X(7, 4, 4, 4, 4) \
+  X(8, 6, 4, 3, 8) \
+  X(9, 8, 4, 4, 8) \
+  X(10, 8, 8, 4, 16)
+
+template <int Q_, int W_> struct ClassShape
 {
-  hipLaunchKernelGGL((dcp_path_kernel<Q, W>), dim3((unsigned)a.nprob), dim3(64 * W), 0, a.stream, a.pool, a.profiles,
-                     a.problems, a.code_rows, a.xt_table, a.arena, a.out, a.nprob);
-  return hipGetLastError();
+  static constexpr int Q = Q_, W = W_;
+};
+
+// f(cost ClassShape, path ClassShape) of class cls
+template <class F> static hipError_t with_class(int cls, F f)
+{
+  switch (cls)
+  {
+#define X(cls, Q, W, PQ, PW) \
+  case cls: return f(ClassShape<Q, W>{}, ClassShape<PQ, PW>{});
+    DCP_CLASS_TABLE(X)
+#undef X
+  default: return hipErrorInvalidValue;
+  }
 }
+#define X(...) +1
+static_assert(0 DCP_CLASS_TABLE(X) == DCP_STRIP_CLASS, "one row of DCP_CLASS_TABLE per class below the strip class");
+#undef X
 
 template <bool STORE> static hipError_t launch_strip(DcpLaunch const &a)
 {
@@ -859,12 +894,7 @@ int dcp_class_of(int K)
   // classes 0..3: one wave, Q = 1..4.  K = 61..64 take the 128-column layout: the packed cost kernel that runs
   // them (32 lanes x 3 positions, viterbi_pack.h) reads 96 columns of a row
   if (K <= 256) return K > 60 && K <= 64 ? 1 : (K + 63) / 64 - 1;
-  // Padded sizes 384, 512, 768, 1024, 1536, 2048, 4096.  The cost kernels run them with 6 or 8 positions per
-  // lane -- (6,1) (8,1) (6,2) (4,4) (6,4) (8,4) (8,8) -- which halves or quarters the wavefronts that meet at
-  // the row barrier; 8 per lane fits 256 VGPRs (two waves per SIMD) only with the transition arrays parked in
-  // LDS between their uses (CostWave::STASH).  Measured against the 3/4-per-lane shapes on Pfam-structured
-  // tables: K=384 639 -> 857 GCUPS, 512 674 -> 884, 768 517 -> 691, 1536 328 -> 593, 2048 427 -> 548,
-  // 4096 190 -> 337; (8,2) for 1024 brought nothing over (4,4).  The pass-by-pass path kernel keeps 3/4.
+  // padded sizes 384, 512, 768, 1024, 1536, 2048, 4096 (their kernels: DCP_CLASS_TABLE)
   if (K <= 384) return 4;
   if (K <= 512) return 5;
   if (K <= 768) return 6;
@@ -878,33 +908,15 @@ int dcp_class_of(int K)
 
 void dcp_class_shape(int cls, int *Q, int *W)
 {
-  // the shape of the cost / cost+store kernels; the pass-by-pass path kernel keeps at most 4 positions
-  // per lane and runs the same padded layout as (3, 2W) / (4, 2W) where this says (6, W) / (8, W)
-  static int const q[DCP_NUM_CLASSES] = {1, 2, 3, 4, 6, 8, 6, 4, 6, 8, 8, 4};
-  static int const w[DCP_NUM_CLASSES] = {1, 1, 1, 1, 1, 1, 2, 4, 4, 4, 8, 8}; // the strip class: per strip
-  *Q = q[cls];
-  *W = w[cls];
+  *Q = 4, *W = 8; // the strip class: per strip
+  (void)with_class(cls, [&](auto cost, auto) { return *Q = cost.Q, *W = cost.W, hipSuccess; });
 }
 
 hipError_t dcp_launch_cost(int cls, DcpLaunch const &a)
 {
   if (a.nprob <= 0) return hipSuccess;
-  switch (cls)
-  {
-  case 0: return launch_cost_qw<1, 1>(a);
-  case 1: return launch_cost_qw<2, 1>(a);
-  case 2: return launch_cost_qw<3, 1>(a);
-  case 3: return launch_cost_qw<4, 1>(a);
-  case 4: return launch_cost_qw<6, 1>(a);
-  case 5: return launch_cost_qw<8, 1>(a);
-  case 6: return launch_cost_qw<6, 2>(a);
-  case 7: return launch_cost_qw<4, 4>(a);
-  case 8: return launch_cost_qw<6, 4>(a);
-  case 9: return launch_cost_qw<8, 4>(a);
-  case 10: return launch_cost_qw<8, 8>(a);
-  case DCP_STRIP_CLASS: return launch_strip<false>(a);
-  default: return hipErrorInvalidValue;
-  }
+  if (cls == DCP_STRIP_CLASS) return launch_strip<false>(a);
+  return with_class(cls, [&](auto cost, auto) { return launch_cost_qw<decltype(cost)::Q, decltype(cost)::W>(a); });
 }
 
 // The classes whose rows are padded to 384, 512 and 768 columns: a profile that fits with one position per lane
@@ -928,91 +940,41 @@ hipError_t dcp_launch_cost_narrow(int cls, DcpLaunch const &a)
   }
 }
 
-template <int Q, int W>
-static hipError_t launch_store_qw(DcpLaunch const &a, int64_t const *ckpt_addr, int B, int block, int G, int it)
-{
-  hipLaunchKernelGGL((dcp_cost_store_kernel<Q, W>), dim3((unsigned)a.nprob * (unsigned)(G > 0 ? G : 1)), dim3(64 * W), 0,
-                     a.stream, a.pool, a.profiles, a.problems, a.code_rows, a.xt_table, a.arena, ckpt_addr, B, block, G, it,
-                     a.out, a.nprob);
-  return hipGetLastError();
-}
-
 hipError_t dcp_launch_cost_store(int cls, DcpLaunch const &a, int64_t const *ckpt_addr, int B, int block, int G, int it)
 {
   if (a.nprob <= 0) return hipSuccess;
-  switch (cls)
-  {
-  case 0: return launch_store_qw<1, 1>(a, ckpt_addr, B, block, G, it);
-  case 1: return launch_store_qw<2, 1>(a, ckpt_addr, B, block, G, it);
-  case 2: return launch_store_qw<3, 1>(a, ckpt_addr, B, block, G, it);
-  case 3: return launch_store_qw<4, 1>(a, ckpt_addr, B, block, G, it);
-  case 4: return launch_store_qw<6, 1>(a, ckpt_addr, B, block, G, it);
-  case 5: return launch_store_qw<8, 1>(a, ckpt_addr, B, block, G, it);
-  case 6: return launch_store_qw<6, 2>(a, ckpt_addr, B, block, G, it);
-  case 7: return launch_store_qw<4, 4>(a, ckpt_addr, B, block, G, it);
-  case 8: return launch_store_qw<6, 4>(a, ckpt_addr, B, block, G, it);
-  case 9: return launch_store_qw<8, 4>(a, ckpt_addr, B, block, G, it);
-  case 10: return launch_store_qw<8, 8>(a, ckpt_addr, B, block, G, it);
-  case DCP_STRIP_CLASS: return B == 0 && block == 0 && G == 0 ? launch_strip<true>(a) : hipErrorInvalidValue; // whole tables only
-  default: return hipErrorInvalidValue;
-  }
-}
-
-template <int Q, int W> static hipError_t launch_ckpt_qw(DcpLaunch const &a, int64_t const *ckpt_addr, int B)
-{
-  hipLaunchKernelGGL((dcp_cost_ckpt_kernel<Q, W>), dim3((unsigned)a.nprob), dim3(64 * W), 0, a.stream, a.pool, a.profiles,
-                     a.problems, a.code_rows, a.xt_table, ckpt_addr, B, a.out, a.nprob);
-  return hipGetLastError();
+  if (cls == DCP_STRIP_CLASS) return B == 0 && block == 0 && G == 0 ? launch_strip<true>(a) : hipErrorInvalidValue; // whole tables only
+  return with_class(cls, [&](auto cost, auto) {
+    using C = decltype(cost);
+    hipLaunchKernelGGL((dcp_cost_store_kernel<C::Q, C::W>), dim3((unsigned)a.nprob * (unsigned)(G > 0 ? G : 1)), dim3(64 * C::W),
+                       0, a.stream, a.pool, a.profiles, a.problems, a.code_rows, a.xt_table, a.arena, ckpt_addr, B, block, G,
+                       it, a.out, a.nprob);
+    return hipGetLastError();
+  });
 }
 
 hipError_t dcp_launch_cost_ckpt(int cls, DcpLaunch const &a, int64_t const *ckpt_addr, int B)
 {
   if (a.nprob <= 0) return hipSuccess;
-  switch (cls)
-  {
-  case 0: return launch_ckpt_qw<1, 1>(a, ckpt_addr, B);
-  case 1: return launch_ckpt_qw<2, 1>(a, ckpt_addr, B);
-  case 2: return launch_ckpt_qw<3, 1>(a, ckpt_addr, B);
-  case 3: return launch_ckpt_qw<4, 1>(a, ckpt_addr, B);
-  case 4: return launch_ckpt_qw<6, 1>(a, ckpt_addr, B);
-  case 5: return launch_ckpt_qw<8, 1>(a, ckpt_addr, B);
-  case 6: return launch_ckpt_qw<6, 2>(a, ckpt_addr, B);
-  case 7: return launch_ckpt_qw<4, 4>(a, ckpt_addr, B);
-  case 8: return launch_ckpt_qw<6, 4>(a, ckpt_addr, B);
-  case 9: return launch_ckpt_qw<8, 4>(a, ckpt_addr, B);
-  case 10: return launch_ckpt_qw<8, 8>(a, ckpt_addr, B);
-  default: return hipErrorInvalidValue;
-  }
-}
-
-template <int Q, int W>
-static hipError_t launch_path_blocks_qw(DcpLaunch const &a, int64_t const *ckpt_addr, int B, uint32_t *steps,
-                                        int64_t const *step_off, int32_t *nsteps, DcpTraceState *states)
-{
-  hipLaunchKernelGGL((dcp_path_blocks_kernel<Q, W>), dim3((unsigned)a.nprob), dim3(64 * W), 0, a.stream, a.pool, a.profiles,
-                     a.problems, a.code_rows, a.xt_table, ckpt_addr, B, a.out, steps, step_off, nsteps, states, a.nprob);
-  return hipGetLastError();
+  return with_class(cls, [&](auto cost, auto) {
+    using C = decltype(cost);
+    hipLaunchKernelGGL((dcp_cost_ckpt_kernel<C::Q, C::W>), dim3((unsigned)a.nprob), dim3(64 * C::W), 0, a.stream, a.pool,
+                       a.profiles, a.problems, a.code_rows, a.xt_table, ckpt_addr, B, a.out, a.nprob);
+    return hipGetLastError();
+  });
 }
 
 hipError_t dcp_launch_path_blocks(int cls, DcpLaunch const &a, int64_t const *ckpt_addr, int B, uint32_t *steps,
                                   int64_t const *step_off, int32_t *nsteps, DcpTraceState *states)
 {
   if (a.nprob <= 0) return hipSuccess;
-  switch (cls)
-  {
-  case 0: return launch_path_blocks_qw<1, 1>(a, ckpt_addr, B, steps, step_off, nsteps, states);
-  case 1: return launch_path_blocks_qw<2, 1>(a, ckpt_addr, B, steps, step_off, nsteps, states);
-  case 2: return launch_path_blocks_qw<3, 1>(a, ckpt_addr, B, steps, step_off, nsteps, states);
-  case 3: return launch_path_blocks_qw<4, 1>(a, ckpt_addr, B, steps, step_off, nsteps, states);
-  case 4: return launch_path_blocks_qw<6, 1>(a, ckpt_addr, B, steps, step_off, nsteps, states);
-  case 5: return launch_path_blocks_qw<8, 1>(a, ckpt_addr, B, steps, step_off, nsteps, states);
-  case 6: return launch_path_blocks_qw<6, 2>(a, ckpt_addr, B, steps, step_off, nsteps, states);
-  case 7: return launch_path_blocks_qw<4, 4>(a, ckpt_addr, B, steps, step_off, nsteps, states);
-  case 8: return launch_path_blocks_qw<6, 4>(a, ckpt_addr, B, steps, step_off, nsteps, states);
-  case 9: return launch_path_blocks_qw<8, 4>(a, ckpt_addr, B, steps, step_off, nsteps, states);
-  case 10: return launch_path_blocks_qw<8, 8>(a, ckpt_addr, B, steps, step_off, nsteps, states);
-  default: return hipErrorInvalidValue;
-  }
+  return with_class(cls, [&](auto cost, auto) {
+    using C = decltype(cost);
+    hipLaunchKernelGGL((dcp_path_blocks_kernel<C::Q, C::W>), dim3((unsigned)a.nprob), dim3(64 * C::W), 0, a.stream, a.pool,
+                       a.profiles, a.problems, a.code_rows, a.xt_table, ckpt_addr, B, a.out, steps, step_off, nsteps, states,
+                       a.nprob);
+    return hipGetLastError();
+  });
 }
 
 hipError_t dcp_launch_traceback(DcpLaunch const &a, uint32_t *steps, int64_t const *step_off, int32_t *nsteps,
@@ -1024,87 +986,94 @@ hipError_t dcp_launch_traceback(DcpLaunch const &a, uint32_t *steps, int64_t con
   return hipGetLastError();
 }
 
-// ---- several windows per wavefront: the shapes (lanes per group, positions per lane) by core size ----
-static int const pack_S[DCP_NUM_PACK_SHAPES] = {4, 4, 4, 8, 8, 16, 16, 16, 32, 32, 32};
-static int const pack_Q[DCP_NUM_PACK_SHAPES] = {1, 2, 4, 2, 4, 2, 3, 4, 2, 3, 4};
+// ---- several windows per wavefront: the shapes by core size, each written once ----
+// shape, positions per lane Q, lanes per group S, and for the LDS variant the wavefronts per workgroup (as many as the
+// registers let a CU hold) and the emission lengths whose rows it keeps in LDS: LDS bytes
+#define DCP_PACK_TABLE(X) \
+  X(0, 1, 4, 16, 5)   /* 44 KB */ \
+  X(1, 2, 4, 16, 5)   /* 65 KB */ \
+  X(2, 4, 4, 12, 5)   /* 87 KB */ \
+  X(3, 2, 8, 16, 4)   /* 27 KB */ \
+  X(4, 4, 8, 12, 4)   /* 44 KB */ \
+  X(5, 2, 16, 16, 4)  /* 49 KB */ \
+  X(6, 3, 16, 12, 4)  /* 71 KB */ \
+  X(7, 4, 16, 12, 4)  /* 87 KB */ \
+  X(8, 2, 32, 16, 4)  /* 92 KB */ \
+  X(9, 3, 32, 12, 4)  /* 136 KB */ \
+  X(10, 4, 32, 8, 3)  /* 43 KB: lengths 1..3 only */
 
-int dcp_pack_shape_of(int K)
+template <int Q_, int S_, int WG_, int NLDS_> struct PackShape
 {
-  // DECIPHON_HIP_PACK_PREFER=<shape>: that shape for every profile it holds (throughput experiments)
-  static int const prefer = getenv("DECIPHON_HIP_PACK_PREFER") ? atoi(getenv("DECIPHON_HIP_PACK_PREFER")) : -1;
-  if (prefer >= 0 && prefer < DCP_NUM_PACK_SHAPES && K <= (pack_S[prefer] - 1) * pack_Q[prefer]) return prefer;
-  for (int i = 0; i < DCP_NUM_PACK_SHAPES; ++i)
-    if (K <= (pack_S[i] - 1) * pack_Q[i]) return i; // the first that holds it costs the fewest instructions per cell
-  return -1;
+  static constexpr int Q = Q_, S = S_, WG = WG_, NLDS = NLDS_;
+};
+
+// f(PackShape of `shape`)
+template <class F> static hipError_t with_pack_shape(int shape, F f)
+{
+  switch (shape)
+  {
+#define X(shape, Q, S, WG, NLDS) \
+  case shape: return f(PackShape<Q, S, WG, NLDS>{});
+    DCP_PACK_TABLE(X)
+#undef X
+  default: return hipErrorInvalidValue;
+  }
 }
+#define X(...) +1
+static_assert(0 DCP_PACK_TABLE(X) == DCP_NUM_PACK_SHAPES, "one row of DCP_PACK_TABLE per shape");
+#undef X
 
 void dcp_pack_shape(int shape, int *Q, int *S)
 {
-  *Q = pack_Q[shape];
-  *S = pack_S[shape];
+  *Q = *S = 0;
+  (void)with_pack_shape(shape, [&](auto p) { return *Q = p.Q, *S = p.S, hipSuccess; });
 }
 
-template <int Q, int S, bool LATE = DCP_PACK_LATE(Q), int WAVES = DCP_PACK_WAVES(Q)>
-static hipError_t launch_pack_qs(DcpLaunch const &a, DcpPack const *packs, int npack, uint32_t ncode_rows)
+int dcp_pack_shape_of(int K)
 {
-  hipLaunchKernelGGL((dcp_cost_pack_kernel<Q, S, LATE, WAVES>), dim3((unsigned)npack), dim3(64), 0, a.stream, a.pool,
-                     a.profiles, packs, a.code_rows, ncode_rows, a.xt_table, a.out, npack);
-  return hipGetLastError();
+  auto const holds = [K](int shape) {
+    int Q, S;
+    dcp_pack_shape(shape, &Q, &S);
+    return K <= (S - 1) * Q;
+  };
+  // DECIPHON_HIP_PACK_PREFER=<shape>: that shape for every profile it holds (throughput experiments)
+  static int const prefer = getenv("DECIPHON_HIP_PACK_PREFER") ? atoi(getenv("DECIPHON_HIP_PACK_PREFER")) : -1;
+  if (prefer >= 0 && prefer < DCP_NUM_PACK_SHAPES && holds(prefer)) return prefer;
+  for (int i = 0; i < DCP_NUM_PACK_SHAPES; ++i)
+    if (holds(i)) return i; // the first that holds it costs the fewest instructions per cell
+  return -1;
 }
 
 hipError_t dcp_launch_cost_pack(int shape, DcpLaunch const &a, DcpPack const *packs, int npack, uint32_t ncode_rows)
 {
   if (npack <= 0) return hipSuccess;
-  switch (shape)
-  {
-  case 0: return launch_pack_qs<1, 4>(a, packs, npack, ncode_rows);
-  case 1: return launch_pack_qs<2, 4>(a, packs, npack, ncode_rows);
-  case 2: return launch_pack_qs<4, 4>(a, packs, npack, ncode_rows);
-  case 3: return launch_pack_qs<2, 8>(a, packs, npack, ncode_rows);
-  case 4: return launch_pack_qs<4, 8>(a, packs, npack, ncode_rows);
-  case 5: return launch_pack_qs<2, 16>(a, packs, npack, ncode_rows);
-  case 6: return launch_pack_qs<3, 16>(a, packs, npack, ncode_rows);
-  case 7: return launch_pack_qs<4, 16>(a, packs, npack, ncode_rows);
-  case 8: return launch_pack_qs<2, 32>(a, packs, npack, ncode_rows);
-  case 9: return launch_pack_qs<3, 32>(a, packs, npack, ncode_rows);
-  case 10: return launch_pack_qs<4, 32>(a, packs, npack, ncode_rows);
-  default: return hipErrorInvalidValue;
-  }
+  return with_pack_shape(shape, [&](auto p) {
+    using P = decltype(p);
+    hipLaunchKernelGGL((dcp_cost_pack_kernel<P::Q, P::S>), dim3((unsigned)npack), dim3(64), 0, a.stream, a.pool, a.profiles,
+                       packs, a.code_rows, ncode_rows, a.xt_table, a.out, npack);
+    return hipGetLastError();
+  });
 }
 
-// wavefronts per workgroup of the LDS variants, by shape: as many as the registers let a CU hold.  Groups of 32
-// lanes keep every row in L2: two rows per load are not what binds them, and the LDS variants measured 3-5 %
-// slower there (K = 93: 711 against 745 GCUPS) while groups of 8 and 16 gained up to 27 % (K = 28: 580 -> 737).
-static int const pack_lds_wg[DCP_NUM_PACK_SHAPES] = {16, 16, 12, 16, 12, 16, 12, 12, 0, 0, 0};
-int dcp_pack_lds_waves(int shape) { return shape >= 0 && shape < DCP_NUM_PACK_SHAPES ? pack_lds_wg[shape] : 0; }
-
-template <int Q, int S, int WG, int NLDS, bool LATE = DCP_PACK_LATE(Q)>
-static hipError_t launch_pack_lds(DcpLaunch const &a, DcpPack const *packs, int2 const *groups, int ngroups, uint32_t ncode_rows)
+// Groups of 32 lanes keep every row in L2: two rows per load are not what binds them, and the LDS variants measured
+// 3-5 % slower there (K = 93: 711 against 745 GCUPS) while groups of 8 and 16 gained up to 27 % (K = 28: 580 -> 737).
+int dcp_pack_lds_waves(int shape)
 {
-  hipLaunchKernelGGL((dcp_cost_pack_lds_kernel<Q, S, WG, NLDS, LATE>), dim3((unsigned)ngroups), dim3(64 * WG), 0, a.stream,
-                     a.pool, a.profiles, packs, groups, a.code_rows, ncode_rows, a.xt_table, a.out, ngroups);
-  return hipGetLastError();
+  int waves = 0;
+  (void)with_pack_shape(shape, [&](auto p) { return waves = p.S < 32 ? p.WG : 0, hipSuccess; });
+  return waves;
 }
 
 hipError_t dcp_launch_cost_pack_lds(int shape, DcpLaunch const &a, DcpPack const *packs, int2 const *groups, int ngroups,
                                     uint32_t ncode_rows)
 {
   if (ngroups <= 0) return hipSuccess;
-  switch (shape) // (Q, S, wavefronts, emission lengths in LDS): LDS bytes
-  {
-  case 0: return launch_pack_lds<1, 4, 16, 5>(a, packs, groups, ngroups, ncode_rows);  // 44 KB
-  case 1: return launch_pack_lds<2, 4, 16, 5>(a, packs, groups, ngroups, ncode_rows);  // 65 KB
-  case 2: return launch_pack_lds<4, 4, 12, 5>(a, packs, groups, ngroups, ncode_rows);  // 87 KB
-  case 3: return launch_pack_lds<2, 8, 16, 4>(a, packs, groups, ngroups, ncode_rows);  // 27 KB
-  case 4: return launch_pack_lds<4, 8, 12, 4>(a, packs, groups, ngroups, ncode_rows);  // 44 KB
-  case 5: return launch_pack_lds<2, 16, 16, 4>(a, packs, groups, ngroups, ncode_rows); // 49 KB
-  case 6: return launch_pack_lds<3, 16, 12, 4>(a, packs, groups, ngroups, ncode_rows); // 71 KB
-  case 7: return launch_pack_lds<4, 16, 12, 4>(a, packs, groups, ngroups, ncode_rows);  // 87 KB
-  case 8: return launch_pack_lds<2, 32, 16, 4>(a, packs, groups, ngroups, ncode_rows); // 92 KB
-  case 9: return launch_pack_lds<3, 32, 12, 4>(a, packs, groups, ngroups, ncode_rows); // 136 KB
-  case 10: return launch_pack_lds<4, 32, 8, 3>(a, packs, groups, ngroups, ncode_rows); // 43 KB: lengths 1..3 only
-  default: return hipErrorInvalidValue;
-  }
+  return with_pack_shape(shape, [&](auto p) {
+    using P = decltype(p);
+    hipLaunchKernelGGL((dcp_cost_pack_lds_kernel<P::Q, P::S, P::WG, P::NLDS>), dim3((unsigned)ngroups), dim3(64 * P::WG), 0,
+                       a.stream, a.pool, a.profiles, packs, groups, a.code_rows, ncode_rows, a.xt_table, a.out, ngroups);
+    return hipGetLastError();
+  });
 }
 
 hipError_t dcp_launch_cost_fused(DcpLaunch const &a)
@@ -1118,21 +1087,12 @@ hipError_t dcp_launch_cost_fused(DcpLaunch const &a)
 hipError_t dcp_launch_path(int cls, DcpLaunch const &a)
 {
   if (a.nprob <= 0) return hipSuccess;
-  switch (cls)
-  {
-  case 0: return launch_path_qw<1, 1>(a);
-  case 1: return launch_path_qw<2, 1>(a);
-  case 2: return launch_path_qw<3, 1>(a);
-  case 3: return launch_path_qw<4, 1>(a);
-  case 4: return launch_path_qw<3, 2>(a);
-  case 5: return launch_path_qw<4, 2>(a);
-  case 6: return launch_path_qw<3, 4>(a);
-  case 7: return launch_path_qw<4, 4>(a);
-  case 8: return launch_path_qw<3, 8>(a);
-  case 9: return launch_path_qw<4, 8>(a);
-  case 10: return launch_path_qw<4, 16>(a);
-  default: return hipErrorInvalidValue;
-  }
+  return with_class(cls, [&](auto, auto path) {
+    using P = decltype(path);
+    hipLaunchKernelGGL((dcp_path_kernel<P::Q, P::W>), dim3((unsigned)a.nprob), dim3(64 * P::W), 0, a.stream, a.pool,
+                       a.profiles, a.problems, a.code_rows, a.xt_table, a.arena, a.out, a.nprob);
+    return hipGetLastError();
+  });
 }
 
 hipError_t dcp_launch_encode(unsigned char const *nt, int64_t const *seq_off, int64_t const *row_off, int nseq,

@@ -59,7 +59,7 @@ def choose_qw(K: int, path: bool = False):
     """(positions per lane, waves per problem) of the cost kernels -- or, path=True, of the
     pass-by-pass path kernel, which keeps at most 4 positions per lane and runs (3, 2W) where
     the cost kernel runs (6, W) / (8, W) on the same padded layout
-    (deciphon_amd/csrc/viterbi_kernels.hip: dcp_class_of / dcp_class_shape / dcp_launch_path)."""
+    (deciphon_amd/csrc/viterbi_kernels.hip: dcp_class_of / DCP_CLASS_TABLE)."""
     if K <= 256:
         return (2 if 60 < K <= 64 else max(1, (K + 63) // 64)), 1  # 61..64: the 128-column layout (dcp_class_of)
     shapes = ((3, 2), (4, 2), (3, 4), (4, 4), (3, 8), (4, 8), (4, 16)) if path else \

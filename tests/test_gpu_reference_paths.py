@@ -17,7 +17,7 @@ from make_golden import MODES, XT_ROWS, synth_case_params, synth_xt  # noqa: E40
 
 pytestmark = pytest.mark.gpu
 
-# the forms of the path pass (deciphon_amd/csrc/engine.cpp): blocks side by side (default), checkpoints every 50 rows,
+# the forms of the path pass (deciphon_amd/csrc/engine_path.cpp): blocks side by side (default), checkpoints every 50 rows,
 # one workgroup walking its window's blocks (dcp_path_blocks_kernel), a launch per block and phase, and the literal
 # pass with the device unzip (dcp_unzip_kernel)
 PATH_MODES = {
