@@ -87,6 +87,9 @@ struct DcpPack
 #define DCP_CKPT_ROWS_DEFAULT 500
 #define DCP_CKPT_SP 6 // lane rows of specials per checkpoint: Spre[5], X
 DCP_HDI long long dcp_ckpt_floats(int Kp, int W) { return 10LL * Kp + (long long)DCP_CKPT_SP * 64 * W; } // W waves per window
+// the strip class (K > 4096, StripWave) cannot fold B of a row into its ring -- rest[5][Kp], Ipre[5][Kp] -- and saves
+// B of the five rows behind the lane rows (padded to 32 bytes)
+DCP_HDI long long dcp_strip_ckpt_floats(int Kp, int W) { return dcp_ckpt_floats(Kp, W) + 8; }
 
 // blocks of a window of L rows with checkpoints every B rows (B = 0: one block, the whole window)
 DCP_HDI int dcp_num_blocks(int L, int B) { return B <= 0 || L <= B + 5 ? 1 : (L - 5 + B - 1) / B; }
@@ -99,6 +102,9 @@ DCP_HDI long long dcp_block_table_floats(int L, int Kp, int B)
 {
   return (long long)dcp_block_slots(L, B) * (DCP_SP_STRIDE + 3LL * Kp);
 }
+
+// rows of the trellis that the replay of one block can serve (row_replay.h): B + 5 and row 0, for block 0
+DCP_HDI int dcp_replay_block_rows(int B) { return B + 6; }
 
 // where the traceback of one window stands between blocks (all zero = not started)
 struct DcpTraceState

@@ -80,6 +80,13 @@ template <class T> struct PinBuf
   }
 };
 
+// DECIPHON_HIP_PATH_STRICT=1: the path pass's budget is a hard limit (what exceeds it is a DCP_ENOMEM)
+inline bool path_budget_strict()
+{
+  char const *strict = getenv("DECIPHON_HIP_PATH_STRICT");
+  return strict && strict[0] == '1';
+}
+
 // DP tables of the fast path pass: chunks that are allocated as slices need them and kept until
 // the engine goes (the driver wipes VRAM that is freed, and an allocation that lands on memory
 // still being wiped waits for it at ~30 GB/s -- scripts/alloc_timing.py; growing without ever
@@ -90,12 +97,19 @@ struct TableArena
   struct Chunk { unsigned char *p; size_t size, used; };
   std::vector<Chunk> chunks;
   size_t held = 0;      // bytes in all chunks
-  size_t placed = 0;    // bytes handed out since reset()
+  size_t placed = 0;    // bytes handed out since reset() (not bytes allocated: chunks are kept and reused)
   double alloc_ms = 0;  // time spent in hipMalloc since reset()
   size_t cur = 0;
   ~TableArena()
   {
     for (Chunk &c : chunks) (void)hipFree(c.p);
+  }
+  // the largest placement the chunks held so far can take (0: none held)
+  size_t largest_chunk() const
+  {
+    size_t m = 0;
+    for (Chunk const &c : chunks) m = std::max(m, c.size);
+    return m;
   }
   void reset()
   {
@@ -125,8 +139,7 @@ struct TableArena
       if (placed != 0) return nullptr; // the slice ends here
       // a lone table is tried whatever the budget says -- unless the budget is a hard limit
       // (DECIPHON_HIP_PATH_STRICT=1: the caller then fails with DCP_ENOMEM, as trellis_setup does when realloc fails)
-      char const *strict = getenv("DECIPHON_HIP_PATH_STRICT");
-      if (strict && strict[0] == '1') return nullptr;
+      if (path_budget_strict()) return nullptr;
       want = bytes;
     }
     auto const t0 = std::chrono::steady_clock::now();
@@ -269,6 +282,9 @@ struct dcp_hip
   std::vector<dcp_hip_window> path_wins; // the windows of the last dcp_hip_path
   int path_redone = 0;                   // how many of them needed the literal pass
   int path_group = 1;                    // blocks of a window computed side by side in the fast path pass
+  std::vector<char> path_in_blocks;      // per window of path_sorted: a strip-class window whose table is held in blocks
+  int path_blocked = 0;                  // how many of those the last dcp_hip_path had (dcp_hip_path_blocked)
+  int64_t path_table_bytes = 0;          // the most of tables.placed at one time since the last dcp_hip_path began
   PinBuf<int32_t> h_nsteps;        // path pass results on the host (pinned: see PinBuf)
   // the steps of a dcp_hip_path call stay where the copies from the device put them (PathResult::steps points there):
   // one pinned buffer per slice of the fast pass and one for the literal pass, reused by the next call
@@ -394,6 +410,11 @@ enum ArenaKind { ARENA_NONE, ARENA_TRELLIS, ARENA_TABLE };
 
 // DP table of one window: float specials[(L+1)][8], float cells[(L+1)][3][Kp] (traceback.h)
 inline size_t table_bytes(int L, int Kp) { return ((size_t)L + 1) * (DCP_SP_STRIDE + 3 * (size_t)Kp) * 4; }
+
+// trellis of one window: uint32 xnodes[L+1], uint16 nodes[(L+1)][K] (c-core/trellis.h:12-21); in the arena of a staged
+// list (ARENA_TRELLIS) the windows follow each other in the order given, each from a multiple of 16 bytes
+inline size_t trellis_bytes(int L, int K) { return ((size_t)L + 1) * 4 + ((size_t)L + 1) * (size_t)K * 2; }
+inline size_t trellis_stride(int L, int K) { return (trellis_bytes(L, K) + 15) & ~(size_t)15; }
 
 // validates windows and builds the device problem list in the current bank
 // (origin: the stream the lists are uploaded on -- x->stream unless a batch is begun asynchronously)

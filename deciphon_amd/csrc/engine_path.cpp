@@ -23,12 +23,41 @@ int ckpt_rows()
 }
 // one block's table, then the window's checkpoints (16-byte aligned)
 size_t block_table_bytes(int L, int Kp, int B) { return (size_t)dcp_block_slots(L, B) * (DCP_SP_STRIDE + 3 * (size_t)Kp) * 4; }
-size_t ckpt_bytes(int L, int Kp, int W, int B) { return (size_t)(dcp_num_blocks(L, B) - 1) * (size_t)dcp_ckpt_floats(Kp, W) * 4; }
-// (G tables side by side when G blocks of a window are computed at once: dcp_cost_store_kernel)
-size_t fast_bytes(int L, int Kp, int W, int B, int G = 1)
+// (strip: a window of the strip class, whose checkpoints carry B of five rows as well)
+size_t ckpt_bytes(int L, int Kp, int W, int B, bool strip = false)
 {
-  return (((size_t)std::min(G, dcp_num_blocks(L, B)) * block_table_bytes(L, Kp, B) + 15) & ~(size_t)15) + ckpt_bytes(L, Kp, W, B);
+  return (size_t)(dcp_num_blocks(L, B) - 1) * (size_t)(strip ? dcp_strip_ckpt_floats(Kp, W) : dcp_ckpt_floats(Kp, W)) * 4;
 }
+// the G tables of a window whose G blocks are computed at once (dcp_cost_store_kernel); its checkpoints come behind them
+size_t group_tables_bytes(int L, int Kp, int B, int G)
+{
+  return ((size_t)std::min(G, dcp_num_blocks(L, B)) * block_table_bytes(L, Kp, B) + 15) & ~(size_t)15;
+}
+size_t fast_bytes(int L, int Kp, int W, int B, int G = 1, bool strip = false)
+{
+  return group_tables_bytes(L, Kp, B, G) + ckpt_bytes(L, Kp, W, B, strip);
+}
+
+// Does this window of the strip class go in blocks?  `whole` = what it takes otherwise: its whole table (fast pass),
+// or that and the replay scratch of all its rows (literal pass).  Where that fits the budget the window keeps it: its
+// rows are walked once instead of twice.  Where it does not the window is taken a block at a time like every other
+// class -- unless the budget is strict: DECIPHON_HIP_PATH_STRICT=1 refuses a strip window whose WHOLE table exceeds the
+// budget, as it always has (its block table might fit; the rule is kept because callers and tests rely on it).
+bool strip_in_blocks(size_t whole, int B, size_t budget) { return B > 0 && whole > budget && !path_budget_strict(); }
+
+// The G block tables, the checkpoints and (literal pass) the replay scratch of a window are ONE placement, and a
+// placement lies in one chunk of the arena.  Once the arena holds chunks -- dcp_hip_path_reserve sets the whole budget
+// aside in chunks of TableArena::CHUNK -- a placement beyond the largest of them would be allocated on top of what is
+// held, outside the budget: G is held to what a chunk takes.  per_block, fixed: bytes of one more block, of the rest.
+int group_chunk_cap(dcp_hip const *x, size_t per_block, size_t fixed)
+{
+  size_t const chunk = x->tables.largest_chunk();
+  if (chunk == 0 || per_block == 0) return INT32_MAX; // nothing held yet: the first chunk is made to measure
+  size_t const slack = 1024; // the alignments of group_tables_bytes and TableArena::place
+  return chunk > fixed + slack + per_block ? (int)std::min<size_t>((chunk - fixed - slack) / per_block, (size_t)INT32_MAX) : 1;
+}
+
+void note_placed(dcp_hip *x) { x->path_table_bytes = std::max(x->path_table_bytes, (int64_t)x->tables.placed); }
 
 // the path pass works on its own bank and streams (see dcp_hip::bank): swapped in for the duration of a call
 struct PathContext
@@ -151,71 +180,146 @@ size_t path_budget(dcp_hip *x)
   return std::max(std::min(want, avail > 2 * margin ? avail - margin : avail / 2), (size_t)256 << 20);
 }
 
+// The literal pass of the profiles beyond 4096 positions (strip class): the register-resident path kernel does not
+// reach them; their trellis is replayed row by row from the DP table (row_replay.h), into d_trellis at trel_off[j] for
+// window w[sl[..]] = j, its score into slot j of d_out.  The tables are placed slice by slice within the budget like
+// the fast pass's.  A window keeps its whole table, with (L + 1) * 3 * K floats of scratch, where the two fit the
+// budget; where they do not -- and the budget is not strict, see strip_in_blocks -- the table comes a block at a time
+// from checkpoints, G blocks side by side, and a block serves the rows of the traceback's partition (dcp_types.h).
+// count_blocked: the windows taken in blocks go into x->path_blocked (a dcp_hip_path whose fast pass was skipped).
+int literal_strips(dcp_hip *x, std::vector<dcp_hip_window> const &w, std::vector<int> const &sl,
+                   std::vector<size_t> const &trel_off, bool count_blocked)
+{
+  int const n = (int)w.size();
+  size_t const budget = path_budget(x);
+  int const B = ckpt_rows();
+  auto const scratch_bytes = [](int rows, int K) { return (size_t)rows * 3 * (size_t)K * sizeof(float); };
+  auto const aligned = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
+  std::vector<char> blocked(sl.size(), 0);
+  int G = 1;
+  {
+    // as many blocks side by side as the budget holds for the window that needs the most
+    double fixed = 0, one = 0;
+    int most = 1, cap = INT32_MAX;
+    for (size_t i = 0; i < sl.size(); ++i)
+    {
+      dcp_hip_window const &v = w[(size_t)sl[i]];
+      HostProfile const &hp = x->profiles[(size_t)v.profile];
+      int const L = v.stop - v.start;
+      if (L < 1) return fail(x, DCP_EZEROSEQ, "empty window");
+      blocked[i] = strip_in_blocks(aligned(table_bytes(L, hp.Kp)) + scratch_bytes(L + 1, hp.K), B, budget);
+      if (!blocked[i]) continue;
+      size_t const per_block = block_table_bytes(L, hp.Kp, B) + scratch_bytes(dcp_replay_block_rows(B), hp.K);
+      fixed = std::max(fixed, (double)ckpt_bytes(L, hp.Kp, hp.W, B, true));
+      one = std::max(one, (double)per_block);
+      most = std::max(most, dcp_num_blocks(L, B));
+      cap = std::min(cap, group_chunk_cap(x, per_block, ckpt_bytes(L, hp.Kp, hp.W, B, true)));
+      if (count_blocked) ++x->path_blocked;
+    }
+    double const room = 0.9 * (double)budget - fixed;
+    if (one > 0 && room > one) G = (int)std::min<double>(room / one, (double)most);
+    G = std::min(G, cap);
+    if (char const *e = getenv("DECIPHON_HIP_PATH_GROUP")) G = std::max(atoi(e), 1);
+    G = std::max(1, std::min(G, most));
+  }
+  HIP_TRY(x, x->d_aux.reserve(4 * sl.size()), DCP_ENOMEM);
+  for (size_t sb = 0; sb < sl.size();)
+  {
+    size_t se = sb;
+    x->tables.reset();
+    x->table_addr.clear();
+    std::vector<dcp_hip_window> ws;
+    std::vector<int64_t> aux; // [4][windows of the slice]: trellis, scratch, checkpoints, score slot
+    std::vector<int64_t> scr, ckp;
+    int max_rows = 0, max_blocks = 0;
+    for (; se < sl.size(); ++se)
+    {
+      dcp_hip_window const &v = w[(size_t)sl[se]];
+      HostProfile const &hp = x->profiles[(size_t)v.profile];
+      int const L = v.stop - v.start;
+      // one placement per window: its table(s), then the checkpoints, then the scratch
+      size_t const tables = aligned(blocked[se] ? fast_bytes(L, hp.Kp, hp.W, B, G, true) : table_bytes(L, hp.Kp));
+      int const nb = blocked[se] ? dcp_num_blocks(L, B) : 1;
+      int const rows = blocked[se] ? std::min(G, nb) * dcp_replay_block_rows(B) : L + 1;
+      unsigned char *t = x->tables.place(tables + scratch_bytes(rows, hp.K), budget);
+      if (!t) break;
+      x->table_addr.push_back((int64_t)(uintptr_t)t);
+      ws.push_back(v);
+      scr.push_back((int64_t)(uintptr_t)(t + tables));
+      ckp.push_back(blocked[se] ? (int64_t)(uintptr_t)t + (int64_t)group_tables_bytes(L, hp.Kp, B, G) : 0);
+      max_rows = std::max(max_rows, rows);
+      if (blocked[se]) max_blocks = std::max(max_blocks, nb);
+    }
+    if (se == sb) return fail(x, DCP_ENOMEM, "no device memory for the DP table of a long profile's path pass");
+    note_placed(x);
+    int const ns = (int)ws.size();
+    Staged ss;
+    int rc = stage(x, ns, ws.data(), ARENA_TABLE, ss);
+    if (rc) return rc;
+    aux.resize(4 * (size_t)ns);
+    for (int i = 0; i < ns; ++i)
+    {
+      int const j = sl[sb + (size_t)i];
+      aux[(size_t)i] = (int64_t)(uintptr_t)(x->d_trellis.p + trel_off[(size_t)j]);
+      aux[(size_t)ns + i] = scr[(size_t)i];
+      aux[2 * (size_t)ns + i] = ckp[(size_t)i];
+      aux[3 * (size_t)ns + i] = j;
+    }
+    HIP_TRY(x, hipMemcpyAsync(x->d_aux.p, aux.data(), aux.size() * sizeof(int64_t), hipMemcpyHostToDevice, x->stream),
+            DCP_EFUNCUSE);
+    DcpLaunch a = launch_args(x, ss, DCP_STRIP_CLASS);
+    a.arena = nullptr;
+    // (null, alt) of the slice's windows go behind the n scores of the pass
+    DcpLaunch store = a;
+    store.out = a.out + n;
+    if (max_blocks == 0)
+    {
+      HIP_TRY(x, dcp_launch_cost_store(DCP_STRIP_CLASS, store, nullptr, 0, 0), DCP_EFUNCUSE);
+      HIP_TRY(x, dcp_launch_replay(a, x->d_aux.p, B, 1, 0, max_rows), DCP_EFUNCUSE);
+    }
+    else
+    {
+      int64_t const *d_ckpt = x->d_aux.p + 2 * (size_t)ns;
+      HIP_TRY(x, dcp_launch_strip_ckpt(store, d_ckpt, B), DCP_EFUNCUSE);
+      for (int it = 0; it * G < max_blocks; ++it)
+      {
+        HIP_TRY(x, dcp_launch_strip_store(store, d_ckpt, B, G, it), DCP_EFUNCUSE);
+        HIP_TRY(x, dcp_launch_replay(a, x->d_aux.p, B, G, it, max_rows), DCP_EFUNCUSE);
+      }
+    }
+    HIP_TRY(x, hipStreamSynchronize(x->stream), DCP_EFUNCUSE); // aux is read by the copy above; the next slice reuses the tables
+    sb = se;
+  }
+  return 0;
+}
+
 // The literal path pass (viterbi_path as the reference runs it, pass by pass, with the
 // trellis in HBM) + trellis_unzip on the device, for the windows path_wins[idx[..]].
-int path_literal(dcp_hip *x, std::vector<int> const &idx)
+int path_literal(dcp_hip *x, std::vector<int> const &idx, bool count_blocked = false)
 {
   int const n = (int)idx.size();
   if (n == 0) return 0;
   std::vector<dcp_hip_window> w((size_t)n);
   for (int j = 0; j < n; ++j) w[(size_t)j] = x->path_wins[(size_t)idx[(size_t)j]];
-  // Profiles beyond 4096 positions (strip class): the register-resident path kernel does not reach
-  // them; their trellis is replayed row by row from the DP table (row_replay.h).  Step 1, before
-  // the problem list below replaces this one on the device: the tables.
-  std::vector<int64_t> tab((size_t)n, 0), scr((size_t)n, 0);
-  int max_rows = 0;
+  // where stage() will put every window's trellis (ARENA_TRELLIS)
+  std::vector<size_t> trel_off((size_t)n + 1, 0);
+  std::vector<int> sl; // the windows of the strip class
+  for (int j = 0; j < n; ++j)
   {
-    std::vector<int> sl; // local indices of the strip-class windows
-    for (int j = 0; j < n; ++j)
-      if (x->profiles[(size_t)w[(size_t)j].profile].cls == DCP_STRIP_CLASS) sl.push_back(j);
-    if (!sl.empty())
-    {
-      std::vector<dcp_hip_window> ws(sl.size());
-      x->tables.reset();
-      x->table_addr.clear();
-      // as much as the device gives (these windows are rare) unless the budget is a hard limit
-      char const *strict = getenv("DECIPHON_HIP_PATH_STRICT");
-      size_t const room = strict && strict[0] == '1' ? path_budget(x) : (size_t)1 << 40;
-      for (size_t i = 0; i < sl.size(); ++i)
-      {
-        dcp_hip_window const &v = w[(size_t)sl[i]];
-        ws[i] = v;
-        HostProfile const &hp = x->profiles[(size_t)v.profile];
-        int const L = v.stop - v.start;
-        unsigned char *t = L >= 0 ? x->tables.place(table_bytes(L, hp.Kp), room) : nullptr;
-        unsigned char *a = t ? x->tables.place(((size_t)L + 1) * 3 * (size_t)hp.K * sizeof(float), room) : nullptr;
-        if (!t || !a) return fail(x, DCP_ENOMEM, "no device memory for the DP table of a long profile's path pass");
-        x->table_addr.push_back((int64_t)(uintptr_t)t);
-        tab[(size_t)sl[i]] = (int64_t)(uintptr_t)t;
-        scr[(size_t)sl[i]] = (int64_t)(uintptr_t)a;
-        max_rows = std::max(max_rows, L + 1);
-      }
-      Staged ss;
-      int rc0 = stage(x, (int)ws.size(), ws.data(), ARENA_TABLE, ss);
-      if (rc0) return rc0;
-      HIP_TRY(x, BK(x).d_out.reserve(2 * (size_t)n), DCP_ENOMEM);
-      DcpLaunch a = launch_args(x, ss, DCP_STRIP_CLASS);
-      a.arena = nullptr;
-      HIP_TRY(x, dcp_launch_cost_store(DCP_STRIP_CLASS, a, nullptr, 0, 0), DCP_EFUNCUSE);
-    }
+    HostProfile const &hp = x->profiles[(size_t)w[(size_t)j].profile];
+    int const L = w[(size_t)j].stop - w[(size_t)j].start;
+    trel_off[(size_t)j + 1] = trel_off[(size_t)j] + trellis_stride(std::max(L, 0), hp.K);
+    if (hp.cls == DCP_STRIP_CLASS) sl.push_back(j);
   }
+  HIP_TRY(x, BK(x).d_out.reserve(3 * (size_t)n), DCP_ENOMEM);
+  HIP_TRY(x, x->d_trellis.reserve(trel_off[(size_t)n]), DCP_ENOMEM);
+  int rc = 0;
+  // the strip class first: the problem list below replaces its lists on the device
+  if (!sl.empty() && (rc = literal_strips(x, w, sl, trel_off, count_blocked))) return rc;
   Staged st;
-  int rc = stage(x, n, w.data(), ARENA_TRELLIS, st);
-  if (rc) return rc;
-  HIP_TRY(x, BK(x).d_out.reserve(2 * (size_t)n), DCP_ENOMEM);
-  HIP_TRY(x, x->d_trellis.reserve(st.arena_bytes), DCP_ENOMEM);
-  if ((rc = launch_all(x, st, true))) return rc;
-  if (max_rows > 0) // step 2 for the strip class: the rows of every such window side by side
-  {
-    HIP_TRY(x, x->d_aux.reserve(2 * (size_t)n), DCP_ENOMEM);
-    HIP_TRY(x, hipMemcpyAsync(x->d_aux.p, tab.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, x->stream),
-            DCP_EFUNCUSE);
-    HIP_TRY(x, hipMemcpyAsync(x->d_aux.p + n, scr.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, x->stream),
-            DCP_EFUNCUSE);
-    DcpLaunch a = launch_args(x, st, DCP_STRIP_CLASS);
-    HIP_TRY(x, dcp_launch_replay(a, x->d_aux.p, x->d_aux.p + n, max_rows), DCP_EFUNCUSE);
-    HIP_TRY(x, hipStreamSynchronize(x->stream), DCP_EFUNCUSE); // tab/scr are read by the copies above
-  }
+  if ((rc = stage(x, n, w.data(), ARENA_TRELLIS, st))) return rc;
+  if (st.arena_bytes != trel_off[(size_t)n]) return fail(x, DCP_EFUNCUSE, "trellis arena laid out otherwise than expected");
+  if ((rc = launch_all(x, st, true))) return rc; // (not the strip class)
 
   std::vector<int64_t> step_off;
   if ((rc = stage_steps(x, st, n, step_off))) return rc;
@@ -286,17 +390,17 @@ int path_fast(dcp_hip *x, int b, int e, std::vector<int> &redo)
   // checkpoints sit behind each window's block table (dcp_hip_path placed fast_bytes per window)
   std::vector<int64_t> ckpt_addr((size_t)n, 0), step_off;
   StreamDrain drain{x->stream}; // destroyed before the two: an early return does not pull them from under a copy
-  int max_blocks = 1;
+  int max_blocks = 1, strip_blocks = 0; // strip_blocks > 0: windows of the strip class that go in blocks
   for (DcpProblem const &p : st.problems)
   {
     HostProfile const &hp = x->profiles[(size_t)p.profile];
-    if (hp.cls != DCP_STRIP_CLASS) // (the strip class keeps whole tables: dcp_hip_path placed table_bytes for it)
-    {
-      int const nb = dcp_num_blocks(p.L, B);
-      ckpt_addr[(size_t)p.out] =
-          p.trellis + (int64_t)(((size_t)std::min(x->path_group, nb) * block_table_bytes(p.L, hp.Kp, B) + 15) & ~(size_t)15);
-      max_blocks = std::max(max_blocks, nb);
-    }
+    // (a window of the strip class that keeps its whole table has no checkpoints: address 0, dcp_hip_path placed
+    // table_bytes for it)
+    if (hp.cls == DCP_STRIP_CLASS && !x->path_in_blocks[(size_t)(b + p.out)]) continue;
+    int const nb = dcp_num_blocks(p.L, B);
+    ckpt_addr[(size_t)p.out] = p.trellis + (int64_t)group_tables_bytes(p.L, hp.Kp, B, x->path_group);
+    int &most = hp.cls == DCP_STRIP_CLASS ? strip_blocks : max_blocks;
+    most = std::max(most, nb);
   }
   HIP_TRY(x, x->d_ckpt_addr.reserve((size_t)n), DCP_ENOMEM);
   HIP_TRY(x, hipMemcpyAsync(x->d_ckpt_addr.p, ckpt_addr.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, x->stream),
@@ -323,10 +427,24 @@ int path_fast(dcp_hip *x, int b, int e, std::vector<int> &redo)
       if (a.nprob <= 0) continue;
       a.arena = nullptr; // DcpProblem::trellis holds the table's address
       if ((rc = fk.enter(x->cls_branch[c], a))) return rc;
-      if (c == DCP_STRIP_CLASS) // their tables hold the whole window: one block
+      if (c == DCP_STRIP_CLASS && strip_blocks == 0) // their tables hold the whole window: one block
       {
         HIP_TRY(x, dcp_launch_cost_store(c, a, nullptr, 0, 0), DCP_EFUNCUSE);
         HIP_TRY(x, dcp_launch_traceback(a, x->d_steps.p, x->d_step_off.p, x->d_nsteps.p, x->d_trace.p, 0, 0), DCP_EFUNCUSE);
+      }
+      else if (c == DCP_STRIP_CLASS)
+      {
+        // some go in blocks: their checkpoints, then G blocks at a time; a window that keeps its whole table (no
+        // checkpoint address) is one block of the first round
+        int const G = std::max(x->path_group, 1);
+        HIP_TRY(x, dcp_launch_strip_ckpt(a, x->d_ckpt_addr.p, B), DCP_EFUNCUSE);
+        for (int it = 0; it * G < strip_blocks; ++it)
+        {
+          HIP_TRY(x, dcp_launch_strip_store(a, x->d_ckpt_addr.p, B, G, it), DCP_EFUNCUSE);
+          HIP_TRY(x, dcp_launch_traceback(a, x->d_steps.p, x->d_step_off.p, x->d_nsteps.p, x->d_trace.p, B, 0, G, it,
+                                          x->d_ckpt_addr.p),
+                  DCP_EFUNCUSE);
+        }
       }
       else if (x->path_group <= 1 && fused) // one launch: every window walks its own blocks (dcp_path_blocks_kernel)
         HIP_TRY(x, dcp_launch_path_blocks(c, a, x->d_ckpt_addr.p, B, x->d_steps.p, x->d_step_off.p, x->d_nsteps.p, x->d_trace.p),
@@ -392,7 +510,9 @@ int path_run(dcp_hip *x, int n, dcp_hip_window const *w)
   if (n == 0) return 0;
   std::vector<int> redo;
   char const *mode = getenv("DECIPHON_HIP_PATH"); // "literal": skip the fast pass (tests, debugging)
-  if (mode && strcmp(mode, "literal") == 0)
+  bool const literal_only = mode && strcmp(mode, "literal") == 0;
+  x->path_in_blocks.clear();
+  if (literal_only)
     for (int i = 0; i < n; ++i) redo.push_back(i);
   else
   {
@@ -420,22 +540,28 @@ int path_run(dcp_hip *x, int n, dcp_hip_window const *w)
     // fills the GPU by itself).  DECIPHON_HIP_PATH_GROUP overrides.
     {
       double one = 0, fixed = 0;
-      int most = 1;
+      int most = 1, cap = INT32_MAX;
+      x->path_in_blocks.assign((size_t)n, 0);
       for (int i = 0; i < n; ++i)
       {
         HostProfile const &hp = x->profiles[(size_t)ws[i].profile];
         int const L = ws[i].stop - ws[i].start;
-        if (hp.cls == DCP_STRIP_CLASS)
+        bool const strip = hp.cls == DCP_STRIP_CLASS;
+        if (strip && !strip_in_blocks(table_bytes(L, hp.Kp), B, budget))
           fixed += (double)table_bytes(L, hp.Kp);
         else
         {
+          x->path_in_blocks[(size_t)i] = strip;
+          x->path_blocked += strip;
           one += (double)block_table_bytes(L, hp.Kp, B);
-          fixed += (double)ckpt_bytes(L, hp.Kp, hp.W, B);
+          fixed += (double)ckpt_bytes(L, hp.Kp, hp.W, B, strip);
           most = std::max(most, dcp_num_blocks(L, B));
+          cap = std::min(cap, group_chunk_cap(x, block_table_bytes(L, hp.Kp, B), ckpt_bytes(L, hp.Kp, hp.W, B, strip)));
         }
       }
       double const room = 0.9 * (double)budget - fixed;
       int G = one > 0 && room > one ? (int)std::min<double>(room / one, (double)most) : 1;
+      G = std::min(G, cap); // (group_chunk_cap: a window's placement stays inside a chunk of a held arena)
       if (char const *e = getenv("DECIPHON_HIP_PATH_GROUP")) G = std::max(atoi(e), 1);
       x->path_group = std::max(1, std::min(G, most));
     }
@@ -446,16 +572,20 @@ int path_run(dcp_hip *x, int n, dcp_hip_window const *w)
       x->table_addr.clear();
       while (e < n)
       {
-        // one block's table and the checkpoints (dcp_types.h); the whole table beyond 4096 positions
+        // the block tables and the checkpoints (dcp_types.h); beyond 4096 positions the whole table where it fits
         HostProfile const &hp = x->profiles[(size_t)ws[e].profile];
         int const L = ws[e].stop - ws[e].start;
-        unsigned char *at = x->tables.place(
-            hp.cls == DCP_STRIP_CLASS ? table_bytes(L, hp.Kp) : fast_bytes(L, hp.Kp, hp.W, B, x->path_group), budget);
+        bool const strip = hp.cls == DCP_STRIP_CLASS;
+        unsigned char *at = x->tables.place(strip && !x->path_in_blocks[(size_t)e]
+                                                ? table_bytes(L, hp.Kp)
+                                                : fast_bytes(L, hp.Kp, hp.W, B, x->path_group, strip),
+                                            budget);
         if (!at) break;
         x->table_addr.push_back((int64_t)(uintptr_t)at);
         ++e;
       }
       if (e == b) return fail(x, DCP_ENOMEM, "a window's DP table does not fit the device memory left");
+      note_placed(x);
       int rc = path_fast(x, b, e, redo);
       if (rc) return rc;
       b = e;
@@ -463,7 +593,7 @@ int path_run(dcp_hip *x, int n, dcp_hip_window const *w)
     std::sort(redo.begin(), redo.end());
   }
   x->path_redone = (int)redo.size();
-  return path_literal(x, redo);
+  return path_literal(x, redo, literal_only);
 }
 
 } // namespace
@@ -479,6 +609,8 @@ int dcp_hip_path(struct dcp_hip *x, int n, struct dcp_hip_window const *w)
   x->paths.clear();
   x->path_wins.clear();
   x->host_trellis.clear();
+  x->path_table_bytes = 0;
+  x->path_blocked = 0;
   int const rc = path_run(x, n, w);
   if (rc)
   {
@@ -570,6 +702,10 @@ int dcp_hip_path_trellis(struct dcp_hip const *cx, int i, uint32_t const **xnode
 }
 
 int dcp_hip_path_redone(struct dcp_hip const *x) { return x ? x->path_redone : 0; }
+
+int64_t dcp_hip_path_table_bytes(struct dcp_hip const *x) { return x ? x->path_table_bytes : 0; }
+
+int dcp_hip_path_blocked(struct dcp_hip const *x) { return x ? x->path_blocked : 0; }
 
 float dcp_hip_path_score(struct dcp_hip const *x, int i)
 {

@@ -30,8 +30,9 @@ DCP_HD void dcp_replay_row(DcpTraceIn const &in, int l, float *acc, uint32_t *xn
   float const INF = __builtin_inff();
   int const K = in.K, Kp = in.Kp;
   size_t const stride = (size_t)Kp + DCP_ROW_HDR;
-  auto SP = [&](int z, int i) { return in.sp[(size_t)z * DCP_SP_STRIDE + i]; }; // 0 N, 1 B, 2 J, 3 E, 4 C
-  auto CELL = [&](int z, int s, int k) { return k < 0 ? INF : in.cells[((size_t)z * 3 + s) * (size_t)Kp + k]; };
+  int const base = in.row_base; // a block's table (dcp_types.h): row z at slot z - row_base; rows l-5 .. l-1 are read
+  auto SP = [&](int z, int i) { return in.sp[(size_t)(z - base) * DCP_SP_STRIDE + i]; }; // 0 N, 1 B, 2 J, 3 E, 4 C
+  auto CELL = [&](int z, int s, int k) { return k < 0 ? INF : in.cells[((size_t)(z - base) * 3 + s) * (size_t)Kp + k]; };
   auto TR = [&](int id, int k) { return in.trans[(size_t)id * Kp + k]; };
   float const *xt = in.xt;
   float *Ma = acc, *Ia = acc + K, *Da = acc + 2 * (size_t)K;

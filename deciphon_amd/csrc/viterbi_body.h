@@ -561,8 +561,54 @@ template <int Q, int W, bool STORE = false> struct StripWave
   uint32_t stride_bytes;
   DcpCodeRow const *__restrict__ codes;
   int tick = 0; // parity of the next exchange
+  // blocks (dcp_types.h, "fast path pass in blocks"), as CostWave: ckpt_every > 0 saves the state after every
+  // ckpt_every-th row into ckpt_out -- the ten ring rows, Spre[5] and X per lane, and Bz[5], which CostWave has folded
+  // into its ring (dcp_strip_ckpt_floats); ckpt_in resumes from such a state at row row_base, and rows are stored at
+  // table slot l - row_base
+  float *__restrict__ ckpt_out = nullptr;
+  float const *__restrict__ ckpt_in = nullptr;
+  int ckpt_every = 0;
+  int row_base = 0;
 
   enum { KS = 64 * Q * W };
+
+  // a lane copies the positions it owns in every strip: what it reads from the ring it has written itself
+  DCP_FN void save_ring(float *__restrict__ to)
+  {
+    for (int s = 0; s < S; ++s)
+      for (int z = 0; z < 10; ++z)
+      {
+        lf v[Q];
+        load_q<Q>(ring + (size_t)z * Kp + (size_t)s * KS, g.lane, v);
+        store_q<Q>(to + (size_t)z * Kp + (size_t)s * KS, g.lane, v);
+      }
+    float *sp = to + (size_t)10 * Kp;
+#pragma unroll
+    for (int z = 0; z < 5; ++z)
+    {
+      store_lane(sp + z * 64 * W, g.lane, Spre[z]);
+      store_f32_lane0(sp + DCP_CKPT_SP * 64 * W + z, g.lane, Bz[z]);
+    }
+    store_lane(sp + 5 * 64 * W, g.lane, X);
+  }
+  DCP_FN void load_ring(float const *__restrict__ from)
+  {
+    for (int s = 0; s < S; ++s)
+      for (int z = 0; z < 10; ++z)
+      {
+        lf v[Q];
+        load_q<Q>(from + (size_t)z * Kp + (size_t)s * KS, g.lane, v);
+        store_q<Q>(ring + (size_t)z * Kp + (size_t)s * KS, g.lane, v);
+      }
+    float const *sp = from + (size_t)10 * Kp;
+#pragma unroll
+    for (int z = 0; z < 5; ++z)
+    {
+      Spre[z] = load_lane(sp + z * 64 * W, g.lane);
+      Bz[z] = sp[DCP_CKPT_SP * 64 * W + z];
+    }
+    X = load_lane(sp + 5 * 64 * W, g.lane);
+  }
 
   DCP_FN void init(float const *__restrict__ pool, DcpProfileDev const &pf, DcpCodeRow const *__restrict__ code_rows,
                    float const *__restrict__ xt)
@@ -607,11 +653,15 @@ template <int Q, int W, bool STORE = false> struct StripWave
       lf DD[Q];
       load_q<Q>(trans + (size_t)DCP_DD * Kp + (size_t)s * KS, lane, DD);
       g.put_tdd_strip(s, DD); // what running through a whole wave of this strip's delete states costs
+      if (ckpt_in) continue;  // a block that starts at row row_base > 0: load_ring below
       for (int z = 0; z < 10; ++z) store_q<Q>(ring + (size_t)z * Kp + (size_t)s * KS, lane, infq);
       if (STORE)
         for (int z = 0; z < 3; ++z) store_q<Q>(tab_cells + (size_t)z * Kp + (size_t)s * KS, lane, infq);
     }
-    if (STORE) store_sp_lane0(tab_sp, lane, inf, lf_splat(SB), inf, inf, inf);
+    if (ckpt_in)
+      load_ring(ckpt_in);
+    else if (STORE)
+      store_sp_lane0(tab_sp, lane, inf, lf_splat(SB), inf, inf, inf);
     g.put_carry_inf(0);
     g.put_carry_inf(1);
     g.sync();
@@ -760,7 +810,7 @@ template <int Q, int W, bool STORE = false> struct StripWave
       store_q<Q>(ring + (size_t)(5 + P) * Kp + col, lane, ipre);
       if (STORE)
       {
-        float *trow = tab_cells + (size_t)l * 3 * (size_t)Kp + col;
+        float *trow = tab_cells + (size_t)(l - row_base) * 3 * (size_t)Kp + col;
         store_q<Q>(trow, lane, M);
         store_q<Q>(trow + Kp, lane, I);
         store_q<Q>(trow + 2 * (size_t)Kp, lane, D);
@@ -781,27 +831,31 @@ template <int Q, int W, bool STORE = false> struct StripWave
     if (STORE)
     {
       float const C = g.get_lane(GS_X0 + (l & 1), X, 2);
-      store_sp_lane0(tab_sp + (size_t)l * DCP_SP_STRIDE, lane, lf_splat(N), lf_splat(B), lf_splat(J), lf_splat(E),
+      store_sp_lane0(tab_sp + (size_t)(l - row_base) * DCP_SP_STRIDE, lane, lf_splat(N), lf_splat(B), lf_splat(J), lf_splat(E),
                      lf_splat(C));
     }
   }
 
-  // out[0] = viterbi_null(), out[1] = viterbi_cost()
-  DCP_FN void run(int L, float *out)
+  // out[0] = viterbi_null(), out[1] = viterbi_cost().  Lend < L: stop after row Lend (a block; out untouched).
+  DCP_FN void run(int L, float *out, int Lend = -1)
   {
-    int l = 1;
-    for (; l + 4 <= L; l += 5)
+    if (Lend < 0 || Lend > L) Lend = L;
+    int l = row_base + 1; // row_base is a multiple of 5: the block starts in phase 1 like row 1
+    for (; l + 4 <= Lend; l += 5)
     {
       row<1>(l);
       row<2>(l + 1);
       row<3>(l + 2);
       row<4>(l + 3);
       row<0>(l + 4);
+      if (ckpt_every > 0 && (l + 4) % ckpt_every == 0 && l + 4 + 5 < L) // checkpoint j exists iff j * B < L - 5
+        save_ring(ckpt_out + (size_t)((l + 4) / ckpt_every - 1) * (size_t)dcp_strip_ckpt_floats(Kp, W));
     }
-    if (l <= L) row<1>(l++);
-    if (l <= L) row<2>(l++);
-    if (l <= L) row<3>(l++);
-    if (l <= L) row<4>(l++);
+    if (l <= Lend) row<1>(l++);
+    if (l <= Lend) row<2>(l++);
+    if (l <= Lend) row<3>(l++);
+    if (l <= Lend) row<4>(l++);
+    if (Lend < L) return;
     g.sync();
     g.put_lanes4(GS_X, X);
     g.sync();

@@ -56,14 +56,27 @@ hipError_t dcp_launch_cost_ckpt(int cls, DcpLaunch const &a, int64_t const *ckpt
 // every window, g = 0 .. G - 1, into table g of the window's G block tables (dcp_block_table_floats apart), one
 // workgroup per (window, g); the traceback then walks those blocks, the highest first
 hipError_t dcp_launch_cost_store(int cls, DcpLaunch const &a, int64_t const *ckpt_addr, int B, int block, int G = 0, int it = 0);
+// (ckpt_addr != NULL, strip class: a window with ckpt_addr[out] == 0 keeps its whole table -- one block, B = 0 -- whatever B)
 hipError_t dcp_launch_traceback(DcpLaunch const &a, uint32_t *steps, int64_t const *step_off, int32_t *nsteps,
-                                DcpTraceState *states, int B, int block, int G = 0, int it = 0);
+                                DcpTraceState *states, int B, int block, int G = 0, int it = 0,
+                                int64_t const *ckpt_addr = nullptr);
+// the strip class in blocks, B > 0 per window: ckpt_addr[out] != 0 = the window's checkpoints (dcp_strip_ckpt_floats
+// each), its G block tables at DcpProblem::trellis; 0 = the window keeps its whole table there and is one block.
+// _ckpt: the checkpoints of the former.  _store: launch `it` of the groups of G blocks of every window (as
+// dcp_launch_cost_store with G > 0; a.arena is not used), to be followed by dcp_launch_traceback(.., B, 0, G, it, ckpt_addr)
+hipError_t dcp_launch_strip_ckpt(DcpLaunch const &a, int64_t const *ckpt_addr, int B);
+hipError_t dcp_launch_strip_store(DcpLaunch const &a, int64_t const *ckpt_addr, int B, int G, int it);
 // the same for every window of a.problems (one class, not the strip class) in ONE launch: a workgroup takes its window
 // through the checkpoints, then block by block through rows + traceback (DcpProblem::trellis = the table's address)
 hipError_t dcp_launch_path_blocks(int cls, DcpLaunch const &a, int64_t const *ckpt_addr, int B, uint32_t *steps,
                                   int64_t const *step_off, int32_t *nsteps, DcpTraceState *states);
-// strip class: the trellis replayed row by row from the DP tables at table_addr[out] (scratch: 3*K floats per row)
-hipError_t dcp_launch_replay(DcpLaunch const &a, int64_t const *table_addr, int64_t const *scratch_addr, int max_rows);
+// strip class: the trellis replayed row by row (row_replay.h) from the tables dcp_launch_cost_store (whole) or
+// dcp_launch_strip_store (launch `it` of the groups of G blocks) has just written at DcpProblem::trellis of a.problems.
+// aux[4][a.nprob], indexed by DcpProblem::out: the window's trellis (device address), its scratch (3 K floats per row:
+// L + 1 rows for a whole table, dcp_replay_block_rows(B) per block table), its checkpoints (0: whole table, as for
+// dcp_launch_traceback) and the slot of a.out its score goes to.  A block serves the rows of the traceback's partition.
+// max_rows: the most rows (threads) a window has in this launch.
+hipError_t dcp_launch_replay(DcpLaunch const &a, int64_t const *aux, int B, int G, int it, int max_rows);
 hipError_t dcp_launch_compact_steps(uint32_t const *steps, int64_t const *step_off, int64_t const *compact_off,
                                     uint32_t *out, int n, hipStream_t stream);
 // packs of one shape: one wavefront each; a.problems is not used

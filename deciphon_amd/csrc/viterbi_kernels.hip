@@ -175,17 +175,94 @@ __global__ __launch_bounds__(64 * W) void dcp_strip_kernel(float const *__restri
   }
 }
 
-// one row of one window's trellis
+// The strip class in blocks (dcp_types.h), per window: ckpt_addr[out] != 0 is a window whose table is held a block at a
+// time, 0 one that keeps its whole table (one block, B = 0) -- a request may mix the two.  First the checkpoints of the
+// windows that go in blocks ...
+template <int Q, int W>
+__global__ __launch_bounds__(64 * W) void dcp_strip_ckpt_kernel(float const *__restrict__ pool,
+                                                            DcpProfileDev const *__restrict__ profiles,
+                                                            DcpProblem const *__restrict__ problems,
+                                                            DcpCodeRow const *__restrict__ code_rows,
+                                                            float const *__restrict__ xt_table,
+                                                            int64_t const *__restrict__ ckpt_addr, int B,
+                                                            float *__restrict__ ring, float *__restrict__ out, int nprob)
+{
+  for (int p = (int)blockIdx.x; p < nprob; p += (int)gridDim.x)
+  {
+    DcpProblem const pb = problems[p];
+    int64_t const ck = ckpt_addr[pb.out];
+    if (ck == 0 || dcp_num_blocks(pb.L, B) <= 1) continue; // (uniform: no barrier is skipped by a part of the workgroup)
+    DcpProfileDev const pf = profiles[pb.profile];
+    StripWave<Q, W, false> w;
+    w.ring = ring + (size_t)blockIdx.x * DCP_RING_FLOATS;
+    w.ckpt_out = dcp_global<float>((uintptr_t)ck);
+    w.ckpt_every = B;
+    w.init(pool, pf, code_rows + pb.code_row, xt_table + (size_t)pb.xt_row * DCP_XT_STRIDE);
+    w.run(pb.L, out + 2 * (size_t)pb.out);
+    __syncthreads(); // the next problem re-initialises the LDS records
+  }
+}
+
+// ... then launch `it` of the groups of G blocks, as dcp_cost_store_kernel: item i = (window i / G, table i % G), block
+// nb - 1 - (it * G + i % G) of that window.  A workgroup owns one ring and takes items in turn.
+template <int Q, int W>
+__global__ __launch_bounds__(64 * W) void dcp_strip_store_kernel(float const *__restrict__ pool,
+                                                             DcpProfileDev const *__restrict__ profiles,
+                                                             DcpProblem const *__restrict__ problems,
+                                                             DcpCodeRow const *__restrict__ code_rows,
+                                                             float const *__restrict__ xt_table,
+                                                             int64_t const *__restrict__ ckpt_addr, int B, int G, int it,
+                                                             float *__restrict__ ring, float *__restrict__ out, int nprob)
+{
+  for (int i = (int)blockIdx.x; i < nprob * G; i += (int)gridDim.x)
+  {
+    int const sub = i % G;
+    DcpProblem const pb = problems[i / G];
+    int64_t const ck = ckpt_addr[pb.out];
+    int const Bw = ck != 0 ? B : 0;
+    int const nb = dcp_num_blocks(pb.L, Bw);
+    int const block = nb - 1 - (it * G + sub);
+    if (block < 0) continue;
+    DcpProfileDev const pf = profiles[pb.profile];
+    StripWave<Q, W, true> w;
+    w.ring = ring + (size_t)blockIdx.x * DCP_RING_FLOATS;
+    w.tab_sp = dcp_global<float>((uintptr_t)pb.trellis) + (size_t)sub * dcp_block_table_floats(pb.L, pf.Kp, Bw);
+    w.tab_cells = w.tab_sp + (size_t)dcp_block_slots(pb.L, Bw) * DCP_SP_STRIDE;
+    w.row_base = block * Bw;
+    if (block > 0)
+      w.ckpt_in = dcp_global<float const>((uintptr_t)ck) + (size_t)(block - 1) * (size_t)dcp_strip_ckpt_floats(pf.Kp, W);
+    w.init(pool, pf, code_rows + pb.code_row, xt_table + (size_t)pb.xt_row * DCP_XT_STRIDE);
+    int const last = Bw > 0 ? (block + 1) * Bw + 5 : pb.L;
+    w.run(pb.L, out + 2 * (size_t)pb.out, last < pb.L ? last : pb.L);
+    __syncthreads();
+  }
+}
+
+// one row of one window's trellis: thread r of the window in launch `it` (dcp_launch_replay)
 __device__ void dcp_replay_one(float const *__restrict__ pool, DcpProfileDev const *__restrict__ profiles,
                                DcpProblem const pb, DcpCodeRow const *__restrict__ code_rows,
-                               float const *__restrict__ xt_table, unsigned char *__restrict__ arena,
-                               int64_t const *__restrict__ table_addr, int64_t const *__restrict__ scratch_addr,
-                               float *__restrict__ out)
+                               float const *__restrict__ xt_table, int64_t const *__restrict__ aux, int naux, int B, int G,
+                               int it, float *__restrict__ out)
 {
-  int const l = (int)(blockIdx.x * 64u + threadIdx.x);
+  int const r = (int)(blockIdx.x * 64u + threadIdx.x);
+  int const Bw = aux[2 * (size_t)naux + pb.out] != 0 ? B : 0; // no checkpoints: the whole table, one block
+  int sub = 0, block = 0, l = r;
+  size_t acc_row = (size_t)r;
+  if (Bw > 0)
+  {
+    int const per = dcp_replay_block_rows(Bw);
+    sub = r / per;
+    if (sub >= G) return;
+    block = dcp_num_blocks(pb.L, Bw) - 1 - (it * G + sub);
+    if (block < 0) return;
+    l = (block > 0 ? block * Bw + 6 : 0) + r % per;
+    if (l > (block + 1) * Bw + 5) return;
+  }
+  else if (it > 0)
+    return;
   if (l > pb.L) return;
   DcpProfileDev const pf = profiles[pb.profile];
-  uint32_t *xnodes = reinterpret_cast<uint32_t *>(arena + pb.trellis);
+  uint32_t *xnodes = dcp_global<uint32_t>((uintptr_t)aux[pb.out]);
   uint16_t *nodes = reinterpret_cast<uint16_t *>(xnodes + (pb.L + 1)) + (size_t)l * pf.K;
   if (l == 0) // before(): every field 0 (c-core/viterbi.c:602-629)
   {
@@ -197,37 +274,40 @@ __device__ void dcp_replay_one(float const *__restrict__ pool, DcpProfileDev con
   in.K = pf.K;
   in.Kp = pf.Kp;
   in.L = pb.L;
-  in.sp = dcp_global<float const>((uintptr_t)table_addr[pb.out]);
-  in.cells = in.sp + (size_t)(pb.L + 1) * DCP_SP_STRIDE;
+  in.sp = dcp_global<float const>((uintptr_t)pb.trellis) + (size_t)sub * dcp_block_table_floats(pb.L, pf.Kp, Bw);
+  in.cells = in.sp + (size_t)dcp_block_slots(pb.L, Bw) * DCP_SP_STRIDE;
+  in.row_base = block * Bw;
   in.rows = pool + pf.rows_off;
   in.trans = pool + pf.trans_off;
   in.codes = code_rows + pb.code_row;
   in.xt = xt_table + (size_t)pb.xt_row * DCP_XT_STRIDE;
-  float *acc = dcp_global<float>((uintptr_t)scratch_addr[pb.out]) + (size_t)l * 3 * pf.K;
+  float *acc = dcp_global<float>((uintptr_t)aux[(size_t)naux + pb.out]) + acc_row * 3 * pf.K;
   dcp_replay_row(in, l, acc, xnodes + l, nodes);
   if (l == pb.L) // T of the last row: the score viterbi_path returns (c-core/viterbi.c:585-586,599)
-    out[pb.out] = __builtin_fminf(in.sp[(size_t)l * DCP_SP_STRIDE + 3] + in.xt[DCP_ET],
-                                  in.sp[(size_t)l * DCP_SP_STRIDE + 4] + in.xt[DCP_CT]);
+  {
+    float const *last = in.sp + (size_t)(l - in.row_base) * DCP_SP_STRIDE;
+    out[aux[3 * (size_t)naux + pb.out]] = __builtin_fminf(last[3] + in.xt[DCP_ET], last[4] + in.xt[DCP_CT]);
+  }
 }
 
 // The pass-by-pass trellis of profiles beyond 4096 positions: every row replayed from the DP table
 // by one thread (row_replay.h).  blockIdx.y (strided: the y extent of a grid stops at 65535) = problem,
-// blockIdx.x * 64 + threadIdx.x = row.
+// blockIdx.x * 64 + threadIdx.x = row of the window in this launch.
 __global__ __launch_bounds__(64) void dcp_replay_kernel(
     float const *__restrict__ pool, DcpProfileDev const *__restrict__ profiles, DcpProblem const *__restrict__ problems,
-    DcpCodeRow const *__restrict__ code_rows, float const *__restrict__ xt_table, unsigned char *__restrict__ arena,
-    int64_t const *__restrict__ table_addr, int64_t const *__restrict__ scratch_addr, float *__restrict__ out, int nprob)
+    DcpCodeRow const *__restrict__ code_rows, float const *__restrict__ xt_table, int64_t const *__restrict__ aux, int B,
+    int G, int it, float *__restrict__ out, int nprob)
 {
   for (int p = (int)blockIdx.y; p < nprob; p += (int)gridDim.y)
-    dcp_replay_one(pool, profiles, problems[p], code_rows, xt_table, arena, table_addr, scratch_addr, out);
+    dcp_replay_one(pool, profiles, problems[p], code_rows, xt_table, aux, nprob, B, G, it, out);
 }
 
-hipError_t dcp_launch_replay(DcpLaunch const &a, int64_t const *table_addr, int64_t const *scratch_addr, int max_rows)
+hipError_t dcp_launch_replay(DcpLaunch const &a, int64_t const *aux, int B, int G, int it, int max_rows)
 {
   if (a.nprob <= 0) return hipSuccess;
+  if (!aux || B < 0 || B % 5 || G < 1 || it < 0 || max_rows < 1) return hipErrorInvalidValue;
   hipLaunchKernelGGL(dcp_replay_kernel, dim3((unsigned)((max_rows + 63) / 64), (unsigned)(a.nprob < 65535 ? a.nprob : 65535)), dim3(64), 0, a.stream,
-                     a.pool, a.profiles, a.problems, a.code_rows, a.xt_table, a.arena, table_addr, scratch_addr, a.out,
-                     a.nprob);
+                     a.pool, a.profiles, a.problems, a.code_rows, a.xt_table, aux, B, G, it, a.out, a.nprob);
   return hipGetLastError();
 }
 
@@ -418,11 +498,13 @@ __global__ __launch_bounds__(64) void dcp_traceback_kernel(
     float const *__restrict__ pool, DcpProfileDev const *__restrict__ profiles, DcpProblem const *__restrict__ problems,
     DcpCodeRow const *__restrict__ code_rows, float const *__restrict__ xt_table,
     unsigned char const *__restrict__ arena, uint32_t *__restrict__ steps, int64_t const *__restrict__ step_off,
-    int32_t *__restrict__ nsteps, DcpTraceState *__restrict__ states, int B, int block, int G, int it, int nprob)
+    int32_t *__restrict__ nsteps, DcpTraceState *__restrict__ states, int B, int block, int G, int it,
+    int64_t const *__restrict__ ckpt_addr, int nprob)
 {
   int const p = (int)blockIdx.x;
   if (p >= nprob) return;
   DcpProblem const pb = problems[p];
+  if (ckpt_addr && ckpt_addr[pb.out] == 0) B = 0; // strip class: this window keeps its whole table (dcp_strip_store_kernel)
   int const nb = dcp_num_blocks(pb.L, B);
   DcpTraceState *st = states + pb.out;
   if (st->status != 0) return; // finished, or given up, in a later block
@@ -943,7 +1025,8 @@ hipError_t dcp_launch_cost_narrow(int cls, DcpLaunch const &a)
 hipError_t dcp_launch_cost_store(int cls, DcpLaunch const &a, int64_t const *ckpt_addr, int B, int block, int G, int it)
 {
   if (a.nprob <= 0) return hipSuccess;
-  if (cls == DCP_STRIP_CLASS) return B == 0 && block == 0 && G == 0 ? launch_strip<true>(a) : hipErrorInvalidValue; // whole tables only
+  // whole tables here; in blocks: dcp_launch_strip_store
+  if (cls == DCP_STRIP_CLASS) return B == 0 && block == 0 && G == 0 ? launch_strip<true>(a) : hipErrorInvalidValue;
   return with_class(cls, [&](auto cost, auto) {
     using C = decltype(cost);
     hipLaunchKernelGGL((dcp_cost_store_kernel<C::Q, C::W>), dim3((unsigned)a.nprob * (unsigned)(G > 0 ? G : 1)), dim3(64 * C::W),
@@ -977,12 +1060,33 @@ hipError_t dcp_launch_path_blocks(int cls, DcpLaunch const &a, int64_t const *ck
   });
 }
 
+hipError_t dcp_launch_strip_ckpt(DcpLaunch const &a, int64_t const *ckpt_addr, int B)
+{
+  if (a.nprob <= 0) return hipSuccess;
+  if (!a.ring || !ckpt_addr || B <= 0 || B % 5) return hipErrorInvalidValue;
+  unsigned const grid = (unsigned)(a.nprob < DCP_RING_SLOTS ? a.nprob : DCP_RING_SLOTS);
+  hipLaunchKernelGGL((dcp_strip_ckpt_kernel<4, 8>), dim3(grid), dim3(512), 0, a.stream, a.pool, a.profiles, a.problems,
+                     a.code_rows, a.xt_table, ckpt_addr, B, a.ring, a.out, a.nprob);
+  return hipGetLastError();
+}
+
+hipError_t dcp_launch_strip_store(DcpLaunch const &a, int64_t const *ckpt_addr, int B, int G, int it)
+{
+  if (a.nprob <= 0) return hipSuccess;
+  if (!a.ring || !ckpt_addr || B <= 0 || B % 5 || G < 1 || it < 0) return hipErrorInvalidValue;
+  long long const items = (long long)a.nprob * G;
+  unsigned const grid = (unsigned)(items < DCP_RING_SLOTS ? items : DCP_RING_SLOTS);
+  hipLaunchKernelGGL((dcp_strip_store_kernel<4, 8>), dim3(grid), dim3(512), 0, a.stream, a.pool, a.profiles, a.problems,
+                     a.code_rows, a.xt_table, ckpt_addr, B, G, it, a.ring, a.out, a.nprob);
+  return hipGetLastError();
+}
+
 hipError_t dcp_launch_traceback(DcpLaunch const &a, uint32_t *steps, int64_t const *step_off, int32_t *nsteps,
-                                DcpTraceState *states, int B, int block, int G, int it)
+                                DcpTraceState *states, int B, int block, int G, int it, int64_t const *ckpt_addr)
 {
   if (a.nprob <= 0) return hipSuccess;
   hipLaunchKernelGGL(dcp_traceback_kernel, dim3((unsigned)a.nprob), dim3(64), 0, a.stream, a.pool, a.profiles, a.problems,
-                     a.code_rows, a.xt_table, a.arena, steps, step_off, nsteps, states, B, block, G, it, a.nprob);
+                     a.code_rows, a.xt_table, a.arena, steps, step_off, nsteps, states, B, block, G, it, ckpt_addr, a.nprob);
   return hipGetLastError();
 }
 

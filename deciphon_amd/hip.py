@@ -79,6 +79,9 @@ def load_library() -> C.CDLL:
     L.dcp_hip_fetch_staged.argtypes = [vp, vp, vp]
     L.dcp_hip_path.argtypes = [vp, i32, vp]
     L.dcp_hip_path_redone.argtypes = [vp]
+    L.dcp_hip_path_table_bytes.argtypes = [vp]
+    L.dcp_hip_path_table_bytes.restype = C.c_int64
+    L.dcp_hip_path_blocked.argtypes = [vp]
     L.dcp_hip_path_reserve.argtypes = [vp, C.c_int64]
     L.dcp_hip_path_nsteps.argtypes = [vp, i32]
     L.dcp_hip_path_steps.argtypes = [vp, i32, vp, vp]
@@ -312,6 +315,18 @@ class Engine:
     def path_reserve(self, nbytes: int):
         """Set HBM aside for the path pass's DP tables now (its clearing overlaps what follows)."""
         self._check(self.lib.dcp_hip_path_reserve(self.h, int(nbytes)))
+
+    @property
+    def path_table_bytes(self) -> int:
+        """The most HBM bytes of DP tables, checkpoints and replay scratch the last path() -- and the path_trellis()
+        calls after it -- had placed at one time."""
+        return int(self.lib.dcp_hip_path_table_bytes(self.h))
+
+    @property
+    def path_blocked(self) -> int:
+        """How many windows of profiles beyond 4096 positions the last path() took a block at a time because their
+        whole DP table exceeded the budget (DECIPHON_HIP_PATH_BUDGET_MB)."""
+        return int(self.lib.dcp_hip_path_blocked(self.h))
 
     def path_steps_packed(self, i: int) -> np.ndarray:
         """Window i's steps of the last path() as the engine holds them (state id | emission length << 16), copied."""

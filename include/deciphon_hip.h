@@ -141,6 +141,16 @@ int dcp_hip_cost_hits_end(struct dcp_hip *, int *nhits, int32_t *hit_window, flo
  * reference's pass order resolves are redone with the literal pass-by-pass kernel.  The
  * trellis itself is produced (by the literal kernel, for the whole batch) only when
  * dcp_hip_path_trellis is called.  DECIPHON_HIP_PATH=literal forces the literal pass.
+ * The fast pass never holds a window's whole DP table: it keeps checkpoints every DECIPHON_HIP_CKPT_ROWS rows (500)
+ * and one table of that many rows per block being recomputed, within DECIPHON_HIP_PATH_BUDGET_MB.  A profile beyond
+ * 4096 positions keeps the whole table of a window where that fits the budget (its rows are then walked once, not
+ * twice) and goes in blocks like the others where it does not.  DECIPHON_HIP_PATH_STRICT=1 makes the budget a hard
+ * limit -- DCP_ENOMEM instead of an allocation beyond it -- and, for profiles beyond 4096 positions, keeps an older
+ * rule: a window whose WHOLE table exceeds the budget is refused, although its blocks might fit.  The literal pass
+ * of such profiles replays the trellis from the DP table with 3 * K floats of scratch per row; it follows the same rule
+ * for table + scratch: where the two exceed the budget (and it is not strict) the table comes block by block from the
+ * same checkpoints and the scratch shrinks to a block's rows.  Only the trellis itself, (L + 1) * (4 + 2 K) bytes, the
+ * output of dcp_hip_path_trellis, is held whole, outside the budget.
  * A window with no finite path at all (viterbi_cost = +inf, which the reference never sends
  * here: c-core/thread.c:118-121) yields 0 steps and score +inf. */
 int dcp_hip_path(struct dcp_hip *, int n, struct dcp_hip_window const *);
@@ -151,6 +161,15 @@ int dcp_hip_path(struct dcp_hip *, int n, struct dcp_hip_window const *);
 int dcp_hip_path_reserve(struct dcp_hip *, int64_t bytes);
 /* how many windows of the last dcp_hip_path needed the literal pass */
 int dcp_hip_path_redone(struct dcp_hip const *);
+/* The most bytes of DP tables, checkpoints and replay scratch that the last dcp_hip_path -- and the
+ * dcp_hip_path_trellis calls that followed it -- had placed in HBM at one time.  Bytes PLACED in the engine's table
+ * arena, which is kept and reused from call to call (and set aside by dcp_hip_path_reserve): not bytes allocated. */
+int64_t dcp_hip_path_table_bytes(struct dcp_hip const *);
+/* How many windows of profiles beyond 4096 positions the last dcp_hip_path took in blocks: those whose whole table
+ * exceeded the budget in its fast pass, or, where DECIPHON_HIP_PATH=literal skipped that, those whose table + scratch
+ * did in the literal pass.  A dcp_hip_path_trellis afterwards does not change the count (its literal pass adds the
+ * scratch to the table, so it may take in blocks a window that the fast pass did not). */
+int dcp_hip_path_blocked(struct dcp_hip const *);
 /* number of steps of window i's path (S ... T) */
 int dcp_hip_path_nsteps(struct dcp_hip const *, int i);
 /* state ids (c-core/state.h:9-25, state.c:92-96) and emission lengths of every step */
