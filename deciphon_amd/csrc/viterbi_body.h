@@ -46,6 +46,64 @@
 #endif
 constexpr int dcp_lazy_turns(int Q) { return Q >= DCP_LAZY_POSITIONS ? 1 : (DCP_LAZY_POSITIONS + Q - 1) / Q; }
 
+// The lazy D->D turns of a wave that holds a whole profile (the reference's loop, c-core/viterbi.c:569-580).  D comes in
+// as every lane's own chain Dl[q]; c is what enters the lane, the final D of the left neighbour's last position.  The
+// final row is D[q] = min(Dl[q], T_q(c)), T_q(c) = (((c + DD[0]) + DD[1]) + ..) + DD[q]: Dl[q] <= Dl[q-1] + DD[q]
+// already, min is exact and fp32 addition monotone, so min(Dl[q], min(Dl[q-1], T_{q-1}) + DD[q]) is the same bits, and
+// the carries only fall from turn to turn, so the last one decides.  A turn therefore moves the carry alone -- the add
+// chain, one min at the lane's last position, the shift: Q + 2 instructions -- and D is written once, by the last turn
+// (2Q + 1).  Behind the vote (rare) the loop carries c, D[0] for the vote and the last position; D is written once
+// more after it.  Returns the last shift, the k-1 neighbour of position 0.
+template <int Q, int TURNS> DCP_FN lf dcp_lazy_turns_carry(lf (&D)[Q], lf const (&DD)[Q], lf &shD)
+{
+  lf c = lane_shift_up_keep(D[Q - 1], shD);
+#pragma unroll
+  for (int turn = 1; turn < TURNS; ++turn)
+  {
+    lf r = c + DD[0];
+#pragma unroll
+    for (int q = 1; q < Q; ++q) r = r + DD[q];
+    c = lane_shift_up_keep(lmin(D[Q - 1], r), shD);
+  }
+  if constexpr (TURNS > 0)
+  {
+    lf r = c + DD[0];
+    D[0] = lmin(D[0], r);
+#pragma unroll
+    for (int q = 1; q < Q; ++q)
+    {
+      r = r + DD[q];
+      D[q] = lmin(D[q], r);
+    }
+    c = lane_shift_up_keep(D[Q - 1], shD);
+  }
+  lf x = c + DD[0];
+  if (wave_any(llt(x, D[0]))) // one more lane boundary per turn
+  {
+    lf d0 = D[0], last = D[Q - 1], applied;
+    do
+    {
+      applied = c;
+      d0 = lmin(d0, x);
+      lf r = x;
+#pragma unroll
+      for (int q = 1; q < Q; ++q) r = r + DD[q];
+      last = Q > 1 ? lmin(last, r) : d0;
+      c = lane_shift_up_keep(last, shD);
+      x = c + DD[0];
+    } while (wave_any(llt(x, d0)));
+    lf r = applied + DD[0];
+    D[0] = lmin(D[0], r);
+#pragma unroll
+    for (int q = 1; q < Q; ++q)
+    {
+      r = r + DD[q];
+      D[q] = lmin(D[q], r);
+    }
+  }
+  return c;
+}
+
 // STORE = true additionally writes every row's final values to a DP table in HBM
 // (cells[l][{M,I,D}][Kp] and specials[l][8] = N,B,J,E,C) for the traceback of
 // traceback.h -- the fast path pass.
@@ -67,8 +125,9 @@ constexpr int dcp_lazy_turns(int Q) { return Q >= DCP_LAZY_POSITIONS ? 1 : (DCP_
 #endif
 template <int Q, int W, bool STORE = false, int POLICY = DCP_SHAPE_POLICY(Q, W)> struct CostWave
 {
-  // lazy D->D turns taken before the first vote: a turn is 2Q + 2 instructions straight-line, a vote costs a
-  // ballot, a scalar branch and the register copies of a loop.  Extra turns change nothing (min is idempotent).
+  // lazy D->D turns taken before the first vote (dcp_lazy_turns_carry): a turn is Q + 2 instructions straight-line,
+  // the last one 2Q + 1; a vote costs an add, a compare and a scalar branch.  Extra turns change nothing (min is
+  // idempotent).
   static constexpr int TURNS = dcp_lazy_turns(Q);
   static constexpr bool LATE_FETCH = (POLICY & 1) != 0;
   static constexpr bool STASH = (POLICY & 6) != 0;
@@ -295,25 +354,7 @@ template <int Q, int W, bool STORE = false, int POLICY = DCP_SHAPE_POLICY(Q, W)>
       D[0] = Msh0 + MD[0];
 #pragma unroll
       for (int q = 1; q < Q; ++q) D[q] = lmin(M[q - 1] + MD[q], D[q - 1] + DD[q]);
-      Dsh0 = lane_shift_up_keep(D[Q - 1], shD);
-      lf x = Dsh0 + DD[0];
-#pragma unroll
-      for (int turn = 0; turn < TURNS; ++turn)
-      {
-        D[0] = lmin(D[0], x);
-#pragma unroll
-        for (int q = 1; q < Q; ++q) D[q] = lmin(D[q], D[q - 1] + DD[q]);
-        Dsh0 = lane_shift_up_keep(D[Q - 1], shD);
-        x = Dsh0 + DD[0];
-      }
-      while (wave_any(llt(x, D[0]))) // one more lane boundary per turn
-      {
-        D[0] = lmin(D[0], x);
-#pragma unroll
-        for (int q = 1; q < Q; ++q) D[q] = lmin(D[q], D[q - 1] + DD[q]);
-        Dsh0 = lane_shift_up_keep(D[Q - 1], shD);
-        x = Dsh0 + DD[0];
-      }
+      Dsh0 = dcp_lazy_turns_carry<Q, TURNS>(D, DD, shD);
     }
     else
     {

@@ -263,25 +263,8 @@ template <int Q, int S, int TURNS = dcp_lazy_turns(Q), int NLDS = 0, bool LATE =
     D[0] = Msh0 + MD[0];
 #pragma unroll
     for (int q = 1; q < Q; ++q) D[q] = lmin(M[q - 1] + MD[q], D[q - 1] + DD[q]);
-    lf Dsh0 = lane_shift_up_keep(D[Q - 1], shD);
-    lf x = Dsh0 + DD[0];
-#pragma unroll
-    for (int turn = 0; turn < TURNS; ++turn)
-    {
-      D[0] = lmin(D[0], x);
-#pragma unroll
-      for (int q = 1; q < Q; ++q) D[q] = lmin(D[q], D[q - 1] + DD[q]);
-      Dsh0 = lane_shift_up_keep(D[Q - 1], shD);
-      x = Dsh0 + DD[0];
-    }
-    while (wave_any(llt(x, D[0])))
-    {
-      D[0] = lmin(D[0], x);
-#pragma unroll
-      for (int q = 1; q < Q; ++q) D[q] = lmin(D[q], D[q - 1] + DD[q]);
-      Dsh0 = lane_shift_up_keep(D[Q - 1], shD);
-      x = Dsh0 + DD[0];
-    }
+    // (the separators' DD is +inf: nothing is carried from one group into the next)
+    lf const Dsh0 = dcp_lazy_turns_carry<Q, TURNS>(D, DD, shD);
 
     if constexpr (LATE)
     {
