@@ -46,6 +46,18 @@ DCP_FN lf lane_shift_up(lf x, float fill)
       __builtin_amdgcn_update_dpp(__float_as_int(fill), __float_as_int(x), 0x138, 0xf, 0xf, false));
 }
 
+// Zero-filled, of a value that may have been shifted before in another basic block.  The DPP combiner folds a shift
+// into the additions that use it only inside the shift's own block, and two identical shifts are merged into the
+// first: the empty asm makes x a new value to the compiler (no instruction, the same register), so this shift stays
+// where it is written, next to its addition, and becomes that addition's DPP operand.
+#define DCP_LANE_SHIFT_UP_AGAIN 1
+DCP_FN lf lane_shift_up(lf x, float fill);
+DCP_FN lf lane_shift_up_again(lf &x)
+{
+  asm volatile("" : "+v"(x));
+  return lane_shift_up(x, 0.0f);
+}
+
 // The same into a register that is kept across rows: wave_shr:1 never writes lane 0,
 // so once lane 0 of `keep` holds the fill value it stays there and no constant has to
 // be re-materialised per shift.

@@ -51,19 +51,23 @@ constexpr int dcp_lazy_turns(int Q) { return Q >= DCP_LAZY_POSITIONS ? 1 : (DCP_
 // final row is D[q] = min(Dl[q], T_q(c)), T_q(c) = (((c + DD[0]) + DD[1]) + ..) + DD[q]: Dl[q] <= Dl[q-1] + DD[q]
 // already, min is exact and fp32 addition monotone, so min(Dl[q], min(Dl[q-1], T_{q-1}) + DD[q]) is the same bits, and
 // the carries only fall from turn to turn, so the last one decides.  A turn therefore moves the carry alone -- the add
-// chain, one min at the lane's last position, the shift: Q + 2 instructions -- and D is written once, by the last turn
-// (2Q + 1).  Behind the vote (rare) the loop carries c, D[0] for the vote and the last position; D is written once
-// more after it.  Returns the last shift, the k-1 neighbour of position 0.
-template <int Q, int TURNS> DCP_FN lf dcp_lazy_turns_carry(lf (&D)[Q], lf const (&DD)[Q], lf &shD)
+// chain, one min at the lane's last position: Q + 1 instructions -- and D is written once, by the last turn (2Q).
+// Every shift is zero-filled and consumed by additions only, so it rides as the DPP operand of its add: the first
+// lane's DD[0] is +inf (CostWave::init sees to it, a pack's first lane is a separator) and 0 + inf is the +inf a k-1
+// shift must deliver there.  Behind the vote (rare) the loop carries the unshifted last position, D[0] for the vote
+// and the source of the carry that was applied last; D is written once more after it.  Returns the UNSHIFTED source
+// of the last carry -- D[Q - 1] where no lane voted for a further turn, in its register -- for the caller to shift
+// in front of the addition that takes it as the k-1 neighbour of position 0 (lane_shift_up_again).
+template <int Q, int TURNS> DCP_FN lf dcp_lazy_turns_carry(lf (&D)[Q], lf const (&DD)[Q])
 {
-  lf c = lane_shift_up_keep(D[Q - 1], shD);
+  lf c = lane_shift_up(D[Q - 1], 0.0f);
 #pragma unroll
   for (int turn = 1; turn < TURNS; ++turn)
   {
     lf r = c + DD[0];
 #pragma unroll
     for (int q = 1; q < Q; ++q) r = r + DD[q];
-    c = lane_shift_up_keep(lmin(D[Q - 1], r), shD);
+    c = lane_shift_up(lmin(D[Q - 1], r), 0.0f);
   }
   if constexpr (TURNS > 0)
   {
@@ -75,24 +79,23 @@ template <int Q, int TURNS> DCP_FN lf dcp_lazy_turns_carry(lf (&D)[Q], lf const 
       r = r + DD[q];
       D[q] = lmin(D[q], r);
     }
-    c = lane_shift_up_keep(D[Q - 1], shD);
   }
-  lf x = c + DD[0];
+  lf last = D[Q - 1];
+  lf x = lane_shift_up(last, 0.0f) + DD[0];
   if (wave_any(llt(x, D[0]))) // one more lane boundary per turn
   {
-    lf d0 = D[0], last = D[Q - 1], applied;
+    lf d0 = D[0], applied;
     do
     {
-      applied = c;
+      applied = last; // unshifted: what the carry of this turn was shifted from
       d0 = lmin(d0, x);
       lf r = x;
 #pragma unroll
       for (int q = 1; q < Q; ++q) r = r + DD[q];
       last = Q > 1 ? lmin(last, r) : d0;
-      c = lane_shift_up_keep(last, shD);
-      x = c + DD[0];
+      x = lane_shift_up(last, 0.0f) + DD[0];
     } while (wave_any(llt(x, d0)));
-    lf r = applied + DD[0];
+    lf r = lane_shift_up(applied, 0.0f) + DD[0];
     D[0] = lmin(D[0], r);
 #pragma unroll
     for (int q = 1; q < Q; ++q)
@@ -101,8 +104,15 @@ template <int Q, int TURNS> DCP_FN lf dcp_lazy_turns_carry(lf (&D)[Q], lf const 
       D[q] = lmin(D[q], r);
     }
   }
-  return c;
+  return last;
 }
+
+// A shift that is consumed in another basic block than an earlier, identical one (behind the vote of the lazy turns):
+// the compiler folds a shift into an addition of its own block only, so the value is shifted once more where it is
+// needed.  lane_ops_gpu.h keeps the two from being merged into one; elsewhere the plain shift does.
+#ifndef DCP_LANE_SHIFT_UP_AGAIN
+DCP_FN lf lane_shift_up_again(lf &x) { return lane_shift_up(x, 0.0f); }
+#endif
 
 // STORE = true additionally writes every row's final values to a DP table in HBM
 // (cells[l][{M,I,D}][Kp] and specials[l][8] = N,B,J,E,C) for the traceback of
@@ -174,7 +184,6 @@ template <int Q, int W, bool STORE = false, int POLICY = DCP_SHAPE_POLICY(Q, W)>
   lf sa, sb;
   lf X;
   lf NBv, EBv, JBv;    // uniform, pinned to VGPRs
-  lf shM, shI, shD;    // destinations of the k-1 shifts; lane 0 stays +inf
   float nil[5], bgv[5];
   float ET, CT, RR;
   float E;
@@ -194,7 +203,10 @@ template <int Q, int W, bool STORE = false, int POLICY = DCP_SHAPE_POLICY(Q, W)>
   // Issues everything the row coded in `cr` needs for its five emission lengths (one
   // scalar offset each), then pulls the codes of the row after it.  Codes run two rows
   // ahead of the DP and emissions one, so neither the scalar nor the vector load
-  // latency sits on the row-to-row critical path.
+  // latency sits on the row-to-row critical path.  Every row fetches, the last one too (its
+  // `cr` is the last row's own codes once more, l_after being clamped to L): a fetch under a
+  // condition would make em, nil, bgv and cr "new or old" values at the back edge of the
+  // unrolled loop, which cost Q + 2 register copies per row.
   DCP_FN void fetch(int l_after, int L)
   {
 #pragma unroll
@@ -257,7 +269,18 @@ template <int Q, int W, bool STORE = false, int POLICY = DCP_SHAPE_POLICY(Q, W)>
     NBv = lf_pin(xt[DCP_NB]);
     EBv = lf_pin(xt[DCP_EB]);
     JBv = lf_pin(xt[DCP_JB]);
-    shM = shI = shD = lf_splat(DCP_INF);
+    if constexpr (W == 1)
+    {
+      // Position 0 has no k-1 neighbour.  The shifts of row() put 0 into the first lane and leave the +inf to the
+      // transition they are added to: whatever a caller's tables hold at k = 0 of these five arrays is ignored.
+      lm const first = lequ(lane, lu_splat(0));
+      lf const inf = lf_splat(DCP_INF);
+      MM[0] = lsel(first, inf, MM[0]);
+      MD[0] = lsel(first, inf, MD[0]);
+      IM[0] = lsel(first, inf, IM[0]);
+      DM[0] = lsel(first, inf, DM[0]);
+      DD[0] = lsel(first, inf, DD[0]);
+    }
     g.put_tdd(DD); // W > 1: what running through a whole wave of delete states costs (row())
     if constexpr (STASH)
     {
@@ -325,8 +348,7 @@ template <int Q, int W, bool STORE = false, int POLICY = DCP_SHAPE_POLICY(Q, W)>
               Spre[DCP_SL(P, 2)] + nil[1], Spre[DCP_SL(P, 1)] + nil[0]);
 
     // emissions of this row are consumed: fetch the next row's behind the rest
-    if constexpr (!LATE_FETCH)
-      if (l < L) fetch(l + 2, L);
+    if constexpr (!LATE_FETCH) fetch(l + 2, L);
 
     lf m = M[0];
 #pragma unroll
@@ -341,8 +363,9 @@ template <int Q, int W, bool STORE = false, int POLICY = DCP_SHAPE_POLICY(Q, W)>
     }
     if constexpr (W == 1)
     {
-      Msh0 = lane_shift_up_keep(M[Q - 1], shM);
-      Ish0 = lane_shift_up_keep(I[Q - 1], shI);
+      // the k-1 shifts: 0 enters the first lane, where MM, MD, IM, DM and DD are +inf (init); each is the DPP
+      // operand of the one or two additions that use it
+      Msh0 = lane_shift_up(M[Q - 1], 0.0f);
       E = wave_min(m);
       N = read_lane(X, 0);
       J = read_lane(X, 1);
@@ -354,7 +377,7 @@ template <int Q, int W, bool STORE = false, int POLICY = DCP_SHAPE_POLICY(Q, W)>
       D[0] = Msh0 + MD[0];
 #pragma unroll
       for (int q = 1; q < Q; ++q) D[q] = lmin(M[q - 1] + MD[q], D[q - 1] + DD[q]);
-      Dsh0 = dcp_lazy_turns_carry<Q, TURNS>(D, DD, shD);
+      Dsh0 = dcp_lazy_turns_carry<Q, TURNS>(D, DD); // (unshifted yet)
     }
     else
     {
@@ -455,8 +478,15 @@ template <int Q, int W, bool STORE = false, int POLICY = DCP_SHAPE_POLICY(Q, W)>
       // the next row's emissions are asked for only now (ten positions per lane with MD, DD and D alive beside them
       // would not fit 256 registers: 23 scratch accesses per row)
       sched_fence();
-      if (l < L) fetch(l + 2, L);
+      fetch(l + 2, L);
       sched_fence();
+    }
+    if constexpr (W == 1)
+    {
+      // the fold's k-1 neighbours of position 0, shifted here, in the block of the additions that take them
+      Msh0 = lane_shift_up_again(M[Q - 1]);
+      Ish0 = lane_shift_up_again(I[Q - 1]);
+      Dsh0 = lane_shift_up_again(Dsh0);
     }
     if constexpr (CHUNKED)
     {
@@ -540,11 +570,9 @@ template <int Q, int W, bool STORE = false, int POLICY = DCP_SHAPE_POLICY(Q, W)>
   {
     if (Lend < 0 || Lend > L) Lend = L;
     int l = row_base + 1; // row_base is a multiple of 5: the block starts in phase 1 like row 1
-    if (l <= Lend)
-    {
-      cr = codes[l];
-      fetch(l + 1, Lend);
-    }
+    // (unconditional like every fetch, clamped like every fetch: an empty window reads the codes of its row 0)
+    cr = codes[l <= Lend ? l : Lend];
+    fetch(l + 1, Lend);
     for (; l + 4 <= Lend; l += 5)
     {
       row<1>(l, Lend);

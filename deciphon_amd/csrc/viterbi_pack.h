@@ -79,7 +79,6 @@ template <int Q, int S, int TURNS = dcp_lazy_turns(Q), int NLDS = 0, bool LATE =
   lf sa, sb, nbjb;      // special transitions by special lane: Xpre = min(E + sa, X + sb); B candidates X + nbjb
   lf X, E;
   lf EBv;
-  lf shM, shI, shD;     // destinations of the k-1 shifts (lane 0 of the wave stays +inf)
   lf Xs, Es;            // X and E of the group's own last row
   lu Lg;                // window length of the lane's group (0: idle group)
   lu crow;              // index of the group's code row 0
@@ -148,6 +147,16 @@ template <int Q, int S, int TURNS = dcp_lazy_turns(Q), int NLDS = 0, bool LATE =
     }
   }
 
+  // What row l does once its own operands are consumed: the next row's go out (its codes arrived a row ago) together
+  // with the codes of the row after it.  Every row does, the last one too -- it reads its own operands once more, the
+  // code row being clamped to Lmax as CostWave::fetch clamps it: under a condition em and code would be "new or old"
+  // values at the back edge of the unrolled loop, a register copy each per five rows.
+  DCP_FN void fetch_next(int l, int Lmax)
+  {
+    fetch_rows();
+    fetch_codes(l + 2 <= Lmax ? l + 2 : Lmax);
+  }
+
   DCP_FN void init(float const *__restrict__ pool, DcpProfileDev const &pf, DcpCodeRow const *__restrict__ code_rows,
                    uint32_t ncode_rows, float const *__restrict__ xt_table, DcpPack const &pk,
                    lds_float const *lds_table = nullptr)
@@ -190,7 +199,6 @@ template <int Q, int S, int TURNS = dcp_lazy_turns(Q), int NLDS = 0, bool LATE =
               lsel(l1, load_f32_at(xt_table, xrow + (uint32_t)DCP_JJ),
                    lsel(l2, load_f32_at(xt_table, xrow + (uint32_t)DCP_CC), lsel(l3, RR, inf))));
     nbjb = lsel(l0, NB, lsel(l1, JB, inf));
-    shM = shI = shD = inf;
     // row 0 (c-core/viterbi.c:471-473, :703): S = 0, B = SB, R = -RR, rest +inf
 #pragma unroll
     for (int s = 0; s < 5; ++s)
@@ -238,20 +246,13 @@ template <int Q, int S, int TURNS = dcp_lazy_turns(Q), int NLDS = 0, bool LATE =
 
     // this row's operands are consumed: the next row's (its codes arrived a row ago) go out now,
     // together with the codes of the row after it
-    if constexpr (!LATE)
-    {
-      if (l < Lmax)
-      {
-        fetch_rows();
-        fetch_codes(l + 2);
-      }
-    }
+    if constexpr (!LATE) fetch_next(l, Lmax);
 
     lf m = M[0];
 #pragma unroll
     for (int q = 1; q < Q; ++q) m = lmin(m, M[q]);
-    lf const Msh0 = lane_shift_up_keep(M[Q - 1], shM);
-    lf const Ish0 = lane_shift_up_keep(I[Q - 1], shI);
+    // (zero-filled: the wave's first lane is a separator, whose transitions are +inf; see dcp_lazy_turns_carry)
+    lf Msh0 = lane_shift_up(M[Q - 1], 0.0f);
     E = group_min<S>(m);                                   // E_l = min_k M_l[k] (see viterbi_body.h)
     lf const B = lmin(E + EBv, group_min01<S>(X + nbjb)); // c-core/viterbi.c:495-496,582-583 (N, J: lanes 0, 1)
 
@@ -264,21 +265,21 @@ template <int Q, int S, int TURNS = dcp_lazy_turns(Q), int NLDS = 0, bool LATE =
 #pragma unroll
     for (int q = 1; q < Q; ++q) D[q] = lmin(M[q - 1] + MD[q], D[q - 1] + DD[q]);
     // (the separators' DD is +inf: nothing is carried from one group into the next)
-    lf const Dsh0 = dcp_lazy_turns_carry<Q, TURNS>(D, DD, shD);
+    lf Dsh0 = dcp_lazy_turns_carry<Q, TURNS>(D, DD); // (unshifted yet)
 
     if constexpr (LATE)
     {
       sched_fence();
-      if (l < Lmax)
-      {
-        fetch_rows();
-        fetch_codes(l + 2);
-      }
+      fetch_next(l, Lmax);
       sched_fence();
     }
     // fold row l into the ring (slot P held row l-5, no longer needed)
     lf BM[Q], MM[Q], IM[Q], DM[Q], II[Q], MI[Q];
     get_fold_trans(fold, BM, MM, IM, DM, II, MI);
+    // the k-1 neighbours of position 0, shifted in the block of the additions that take them
+    Msh0 = lane_shift_up_again(M[Q - 1]);
+    lf const Ish0 = lane_shift_up_again(I[Q - 1]);
+    Dsh0 = lane_shift_up_again(Dsh0);
 #pragma unroll
     for (int q = 0; q < Q; ++q)
     {

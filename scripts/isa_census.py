@@ -4,7 +4,12 @@
 VALU / DPP / s_nop / SALU / SMEM / VMEM / LDS / branch counts.  The row loop is unrolled x5, so
 "per row" = loop total / 5 (lazy D->D inner loops and the blocks only a further turn reaches are listed
 separately: they run a data-dependent number of times).  Only the unrolled loop is counted, not the loops of the
-one to four rows behind it.
+one to four rows behind it.  A block that runs once per unrolled iteration (the back edge: copies into the registers
+the loop header expects) is part of the loop and counts at a fifth of a row like every other block.
+Register copies are counted apart, among the VALU-class as well: plain VGPR <- VGPR (v_mov_b32_e32 vA, vB: a value
+that is "new or old" at a join), VGPR <- SGPR or constant (v_mov_b32_e32 vA, sB: a uniform value the compiler wants
+in a vector register), and v_mov_b32_dpp (a cross-lane move that was not folded into its consumer); of the DPP
+instructions, those that shift by one lane (wave_shr:1) are listed by opcode.
 usage: isa_census.py kernels.s <mangled-name-substring>"""
 import re
 import sys
@@ -64,6 +69,11 @@ for l in body:
         cur[2][kind(s)] += 1
         if s.startswith("v_mov_b32_e32"):
             cur[2]["mov"] += 1  # plain register copies, counted among the VALU as well
+            cur[2]["mov_vv" if re.match(r"v_mov_b32_e32\s+v\d+,\s*v\d+", s) else "mov_vs"] += 1
+        if s.startswith("v_mov_b32_dpp"):
+            cur[2]["mov_dpp"] += 1
+        if "wave_shr:1" in s:
+            cur[2]["shr:" + s.split()[0]] += 1
         last = s
         cur[3] = "Depth=2" in cur[1] or "Inner Loop" in cur[1]
 # the unrolled row loop: the first loop header of depth 1 and what names it (the one to four rows behind it have
@@ -86,4 +96,7 @@ print("row-loop blocks (5 rows), inner lazy loops and blocks behind the vote exc
 print("behind the vote, outside the inner loops (5 rows):", dict(rare))
 print("inner lazy loops (5 rows; a `while` loop's header block runs once per row and once per further turn):", dict(lazy))
 v = tot["valu"] + tot["dpp"] + tot["lane"]
+shr = ", ".join(f"{k[4:]} {n / 5:.1f}" for k, n in sorted(tot.items()) if k.startswith("shr:")) or "none"
+print(f"copies per row: v_mov_b32_e32 VGPR<-VGPR {tot['mov_vv'] / 5:.1f}, VGPR<-SGPR/constant {tot['mov_vs'] / 5:.1f}, "
+      f"v_mov_b32_dpp {tot['mov_dpp'] / 5:.1f}; wave_shr:1 per row: {shr}")
 print(f"per row: VALU-class {v / 5:.1f} (+ s_nop {tot['nop'] / 5:.1f}), SALU {tot['salu'] / 5:.1f}, SMEM {tot['smem'] / 5:.1f}, VMEM {tot['vmem'] / 5:.1f}, LDS {tot['lds'] / 5:.1f}, branches {tot['branch'] / 5:.1f}; of the VALU {tot['mov'] / 5:.1f} v_mov_b32_e32")
