@@ -2,6 +2,7 @@
 #include "host_logic.h"
 #include "../../include/deciphon_host.h"
 #include "dcp_errors.h"
+#include "dcp_states.h"
 
 #include <algorithm>
 #include <initializer_list>
@@ -178,18 +179,6 @@ int dcp_encode_sequence(char const *data, int64_t n, uint8_t *out)
   return rc;
 }
 
-namespace
-{
-enum
-{
-  ST_M = 0 << 14, ST_I = 1 << 14, ST_D = 2 << 14, ST_X = 3 << 14, // c-core/state.h:9-25
-  ST_S = ST_X | 3, ST_N = ST_X | 4, ST_B = ST_X | 5, ST_E = ST_X | 6, ST_J = ST_X | 7, ST_C = ST_X | 8, ST_T = ST_X | 9,
-};
-inline int msb(int id) { return id & (3 << 14); }
-inline bool is_core(int id) { return msb(id) != ST_X; }
-inline int core_idx(int id) { return (id & 0x3FFF) - 1; }
-} // namespace
-
 int dcp_unzip(int K, int L, uint32_t const *xnodes, uint16_t const *nodes, std::vector<int32_t> &state_ids,
               std::vector<int32_t> &seqsizes)
 {
@@ -202,56 +191,12 @@ int dcp_unzip(int K, int L, uint32_t const *xnodes, uint16_t const *nodes, std::
   while (state != ST_S || stage)
   {
     if (++steps > limit) return DCP_EINVALSTATE;
-    int size = 0, prev = 0;
-    if (!is_core(state))
-    {
-      uint32_t const x = xnodes[stage];
-      // field offsets/widths: c-core/trellis.h:42-56, c-core/state.h:27-39
-      switch (state)
-      {
-      case ST_N: { unsigned v = x & 0xF; size = (int)(v % 5) + 1; prev = v / 5 ? ST_N : ST_S; break; }
-      case ST_B: { unsigned v = (x >> 4) & 0x3; static int const from[4] = {ST_S, ST_N, ST_E, ST_J}; prev = from[v]; break; }
-      case ST_E: { unsigned v = (x >> 6) & 0x7FFF; prev = (v & 1 ? ST_D : ST_M) | (int)(v / 2 + 1); break; }
-      case ST_C: { unsigned v = (x >> 21) & 0xF; size = (int)(v % 5) + 1; prev = v / 5 ? ST_C : ST_E; break; }
-      case ST_T: { unsigned v = (x >> 25) & 0x1; prev = v ? ST_C : ST_E; break; }
-      case ST_J: { unsigned v = (x >> 26) & 0xF; size = (int)(v % 5) + 1; prev = v / 5 ? ST_J : ST_E; break; }
-      default: return DCP_EINVALSTATE;
-      }
-    }
-    else
-    {
-      int const idx = core_idx(state);
-      if (idx < 0 || idx >= K) return DCP_EINVALSTATE;
-      uint16_t const w = nodes[(size_t)stage * (size_t)K + (size_t)idx];
-      if (msb(state) == ST_M)
-      {
-        unsigned v = w & 0x1F;
-        size = (int)(v % 5) + 1;
-        unsigned s = v / 5;
-        if (s == 0) prev = ST_B;
-        else
-        {
-          if (idx <= 0) return DCP_EINVALSTATE; // BUG_ON(idx <= 0), c-core/trellis.c:72
-          prev = (s == 1 ? ST_M : s == 2 ? ST_I : ST_D) | idx;
-        }
-      }
-      else if (msb(state) == ST_D)
-      {
-        unsigned v = (w >> 5) & 0x1;
-        if (idx <= 0) return DCP_EINVALSTATE;
-        prev = (v ? ST_D : ST_M) | idx;
-      }
-      else
-      {
-        unsigned v = (w >> 6) & 0xF;
-        size = (int)(v % 5) + 1;
-        prev = (v / 5 ? ST_I : ST_M) | (idx + 1);
-      }
-    }
+    DcpStep const step = dcp_trellis_step(K, xnodes, nodes, state, stage);
+    if (step.prev < 0) return DCP_EINVALSTATE;
     state_ids.push_back(state);
-    seqsizes.push_back(size);
-    state = prev;
-    stage -= size;
+    seqsizes.push_back(step.size);
+    state = step.prev;
+    stage -= step.size;
     if (stage < 0) return DCP_EINVALSTATE;
   }
   state_ids.push_back(state);

@@ -25,7 +25,7 @@
 
 // acc: scratch of 3*K floats (the running M, I, D of the row).  Writes xnode (c-core/trellis.h:
 // 42-56) and nodes[0..K) (c-core/trellis.h:12-21, c-core/viterbi.c:631-694).  l >= 1.
-DCP_HD void dcp_replay_row(DcpTraceIn const &in, int l, float *acc, uint32_t *xnode, uint16_t *nodes)
+DCP_HDI void dcp_replay_row(DcpTraceIn const &in, int l, float *acc, uint32_t *xnode, uint16_t *nodes)
 {
   float const INF = __builtin_inff();
   int const K = in.K, Kp = in.Kp;

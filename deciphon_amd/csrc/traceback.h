@@ -13,16 +13,17 @@
 // between MD and DD, between the candidates of B or T, or a D state tying the row minimum E
 // (c-core/viterbi.c:538-586 resolves those by pass history) -- the walk gives up
 // (DCP_TB_TIE) and the caller runs the literal path kernel for that window.
+//
+// One source for the GPU, the host and the wave emulator (tests/emul): the candidates of the visited state are
+// spread over the 64 lanes of a wavefront in the reference's order -- lane j = (5 - t) * names + name -- so that one
+// step costs two load round trips instead of a chain of them, and the first candidate equal to the stored value is
+// the lowest set bit of a ballot.  What crosses lanes goes through a lane policy:
+//   leader()  : true on the lane that writes buf and *st
+//   ballot(f) : 64-bit mask of f(lane) over the 64 lanes
+//   max_of(f) : the maximum of f(lane) over the 64 lanes
+// DcpLanesHost below takes the lanes one after the other; the wavefront's own is DcpLanesWave (lane_ops_gpu.h).
 #pragma once
-#include "dcp_types.h"
-
-#ifndef DCP_HD
-#ifdef __HIPCC__
-#define DCP_HD __host__ __device__ inline
-#else
-#define DCP_HD inline
-#endif
-#endif
+#include "dcp_states.h"
 
 enum { DCP_TB_OVERFLOW = -1, DCP_TB_TIE = -2, DCP_TB_BAD = -3 };
 
@@ -40,29 +41,60 @@ struct DcpTraceIn
   int row_base = 0, lo = -1;
 };
 
+// A window's side of a DcpTraceIn; the table (sp, cells, row_base) and lo are the caller's to set.
+DCP_HDI DcpTraceIn dcp_trace_in(float const *pool, DcpProfileDev const &pf, DcpCodeRow const *codes, float const *xt, int L)
+{
+  DcpTraceIn in;
+  in.K = pf.K;
+  in.Kp = pf.Kp;
+  in.L = L;
+  in.sp = in.cells = nullptr;
+  in.rows = pool + pf.rows_off;
+  in.trans = pool + pf.trans_off;
+  in.codes = codes;
+  in.xt = xt;
+  return in;
+}
+
+struct DcpLanesHost
+{
+  DCP_HDI static bool leader() { return true; }
+  template <class F> DCP_HDI static uint64_t ballot(F f)
+  {
+    uint64_t mask = 0;
+    for (int lane = 0; lane < 64; ++lane) mask |= (uint64_t)(f(lane) ? 1 : 0) << lane;
+    return mask;
+  }
+  template <class F> DCP_HDI static int max_of(F f)
+  {
+    int best = f(0);
+    for (int lane = 1; lane < 64; ++lane)
+    {
+      int const v = f(lane);
+      best = v > best ? v : best;
+    }
+    return best;
+  }
+};
+
 // Writes the steps (state_id | seqsize << 16) from the END of buf backwards; returns their
 // number, or a DCP_TB_* code -- or 0 when the walk stopped at in.lo with where it stands in *st
 // (st != NULL: resume from *st unless it is fresh, i.e. zeroed -- no state id is 0).
-DCP_HD int dcp_traceback(DcpTraceIn const &in, uint32_t *buf, int64_t cap, DcpTraceState *st = nullptr)
+template <class Lanes = DcpLanesHost>
+DCP_HDI int dcp_traceback(DcpTraceIn const &in, uint32_t *buf, int64_t cap, DcpTraceState *st = nullptr)
 {
-  enum
-  {
-    ST_M = 0 << 14, ST_I = 1 << 14, ST_D = 2 << 14, ST_X = 3 << 14, // c-core/state.h:9-25
-    ST_S = ST_X | 3, ST_N = ST_X | 4, ST_B = ST_X | 5, ST_E = ST_X | 6, ST_J = ST_X | 7, ST_C = ST_X | 8, ST_T = ST_X | 9,
-  };
   float const INF = __builtin_inff();
   int const K = in.K, Kp = in.Kp;
   size_t const stride = (size_t)Kp + DCP_ROW_HDR;
   int const base = in.row_base;
   auto SP = [&](int l, int i) { return in.sp[(size_t)(l - base) * DCP_SP_STRIDE + i]; }; // 0 N, 1 B, 2 J, 3 E, 4 C
   auto CELL = [&](int l, int s, int k) { return k < 0 ? INF : in.cells[((size_t)(l - base) * 3 + s) * (size_t)Kp + k]; };
-  auto ROW = [&](int l, int t) { return in.rows + (size_t)in.codes[l].c[t - 1] * stride; };
   auto TR = [&](int id, int k) { return in.trans[(size_t)id * Kp + k]; };
   float const *xt = in.xt;
 
   int state = ST_T, stage = in.L;
   int64_t n = 0;
-  if (st && st->state != 0)
+  if (st && st->state != 0) // resume where the block after this one stopped (uniform: every lane reads the same)
   {
     state = st->state;
     stage = st->stage;
@@ -70,15 +102,19 @@ DCP_HD int dcp_traceback(DcpTraceIn const &in, uint32_t *buf, int64_t cap, DcpTr
   }
   while (state != ST_S || stage)
   {
-    if (stage <= in.lo)
+    if (stage <= in.lo) // the rest of the path lies in the block before this one
     {
-      st->state = state;
-      st->stage = stage;
-      st->n = n;
+      if (Lanes::leader())
+      {
+        st->state = state;
+        st->stage = stage;
+        st->n = n;
+      }
       return 0;
     }
     int size = 0, prev = -1;
-    if ((state & ST_X) == ST_X)
+    DcpCodeRow const cr = in.codes[stage];
+    if (!is_core(state))
     {
       if (state == ST_T)
       {
@@ -90,17 +126,22 @@ DCP_HD int dcp_traceback(DcpTraceIn const &in, uint32_t *buf, int64_t cap, DcpTr
       {
         int const self = state == ST_N ? 0 : state == ST_J ? 2 : 4;
         float const target = SP(stage, self);
+        if (!(target < INF)) return DCP_TB_BAD;
         float const t_in = state == ST_N ? xt[DCP_SN] : state == ST_J ? xt[DCP_EJ] : xt[DCP_EC];
         float const t_self = state == ST_N ? xt[DCP_NN] : state == ST_J ? xt[DCP_JJ] : xt[DCP_CC];
-        for (int t = stage < 5 ? stage : 5; t >= 1 && prev < 0; --t)
-        {
+        uint64_t const mask = Lanes::ballot([&](int lane) {
+          int const t = 5 - (lane >> 1), which = lane & 1; // from S (N) or E (J, C), then the state itself
+          if (lane >= 10 || t > stage) return false;
           int const z = stage - t;
-          float const nil = ROW(stage, t)[0];
+          float const nil = in.rows[(size_t)cr.c[t - 1] * stride];
           float const from = state == ST_N ? (z == 0 ? 0.0f : INF) : SP(z, 3); // S of row z, or E of row z
-          if ((from + t_in) + nil == target) { prev = state == ST_N ? ST_S : ST_E; size = t; }
-          else if ((SP(z, self) + t_self) + nil == target) { prev = state; size = t; }
-        }
-        if (prev < 0 || !(target < INF)) return DCP_TB_BAD;
+          float const cand = which == 0 ? (from + t_in) + nil : (SP(z, self) + t_self) + nil;
+          return cand == target;
+        });
+        if (!mask) return DCP_TB_BAD;
+        int const j = __builtin_ctzll(mask);
+        size = 5 - (j >> 1);
+        prev = (j & 1) ? state : (state == ST_N ? ST_S : ST_E);
       }
       else if (state == ST_B)
       {
@@ -122,54 +163,66 @@ DCP_HD int dcp_traceback(DcpTraceIn const &in, uint32_t *buf, int64_t cap, DcpTr
         if (!(target < INF)) return DCP_TB_BAD;
         int Qr = (K - 1) / DCP_REF_LANES + 1;
         if (Qr < 2) Qr = 2;
-        int best = -1;
-        for (int k = 0; k < K; ++k)
-        {
-          if (CELL(stage, 2, k) == target) return DCP_TB_TIE; // a D candidate at the minimum: pass history decides
-          if (CELL(stage, 0, k) == target && (best < 0 || k / Qr > best / Qr)) best = k;
-        }
-        if (best < 0) return DCP_TB_BAD;
-        prev = ST_M | (best + 1);
+        // key = (reference lane << 16) | (65535 - k): highest lane, then lowest k; above every key, D_TIE
+        int const D_TIE = 0x7fffffff;
+        int const key = Lanes::max_of([&](int lane) {
+          int best = -1;
+          for (int k = lane; k < K; k += 64)
+          {
+            int const cand = CELL(stage, 2, k) == target   ? D_TIE // a D candidate at the minimum: pass history decides
+                             : CELL(stage, 0, k) == target ? ((k / Qr) << 16) | (65535 - k)
+                                                           : -1;
+            best = cand > best ? cand : best;
+          }
+          return best;
+        });
+        if (key == D_TIE) return DCP_TB_TIE;
+        if (key < 0) return DCP_TB_BAD;
+        prev = ST_M | ((65535 - (key & 0xffff)) + 1);
       }
       else
         return DCP_TB_BAD;
     }
     else
     {
-      int const k = (state & 0x3FFF) - 1;
-      int const kind = state & ST_X;
+      int const k = core_idx(state);
       if (k < 0 || k >= K) return DCP_TB_BAD;
-      if (kind == ST_M)
+      if (msb(state) == ST_M)
       {
         float const target = CELL(stage, 0, k);
         if (!(target < INF)) return DCP_TB_BAD;
-        float const BM = TR(DCP_BM, k), MM = TR(DCP_MM, k), IM = TR(DCP_IM, k), DM = TR(DCP_DM, k);
-        for (int t = stage < 5 ? stage : 5; t >= 1 && prev < 0; --t)
-        {
+        uint64_t const mask = Lanes::ballot([&](int lane) {
+          int const t = 5 - (lane >> 2), name = lane & 3; // BM, MM, IM, DM
+          if (lane >= 20 || t > stage) return false;
           int const z = stage - t;
-          float const m = ROW(stage, t)[DCP_ROW_HDR + k];
-          if ((SP(z, 1) + BM) + m == target) prev = ST_B;
-          else if ((CELL(z, 0, k - 1) + MM) + m == target) prev = ST_M | k;
-          else if ((CELL(z, 1, k - 1) + IM) + m == target) prev = ST_I | k;
-          else if ((CELL(z, 2, k - 1) + DM) + m == target) prev = ST_D | k;
-          if (prev >= 0) size = t;
-        }
-        if (prev < 0) return DCP_TB_BAD;
+          float const m = in.rows[(size_t)cr.c[t - 1] * stride + DCP_ROW_HDR + k];
+          float const x = name == 0 ? SP(z, 1) : CELL(z, name - 1, k - 1);
+          float const tr = TR(name == 0 ? DCP_BM : name == 1 ? DCP_MM : name == 2 ? DCP_IM : DCP_DM, k);
+          return (x + tr) + m == target;
+        });
+        if (!mask) return DCP_TB_BAD;
+        int const j = __builtin_ctzll(mask);
+        size = 5 - (j >> 2);
+        int const nm = j & 3;
+        prev = nm == 0 ? ST_B : (nm == 1 ? ST_M : nm == 2 ? ST_I : ST_D) | k;
       }
-      else if (kind == ST_I)
+      else if (msb(state) == ST_I)
       {
         float const target = CELL(stage, 1, k);
         if (!(target < INF)) return DCP_TB_BAD;
-        float const II = TR(DCP_II, k), MI = TR(DCP_MI, k);
-        for (int t = stage < 5 ? stage : 5; t >= 1 && prev < 0; --t)
-        {
+        uint64_t const mask = Lanes::ballot([&](int lane) {
+          int const t = 5 - (lane >> 1), name = lane & 1; // II, MI
+          if (lane >= 10 || t > stage) return false;
           int const z = stage - t;
-          float const bg = ROW(stage, t)[1];
-          if ((CELL(z, 1, k) + II) + bg == target) prev = ST_I | (k + 1);
-          else if ((CELL(z, 0, k) + MI) + bg == target) prev = ST_M | (k + 1);
-          if (prev >= 0) size = t;
-        }
-        if (prev < 0) return DCP_TB_BAD;
+          float const bg = in.rows[(size_t)cr.c[t - 1] * stride + 1];
+          float const x = name == 0 ? CELL(z, 1, k) : CELL(z, 0, k);
+          float const tr = TR(name == 0 ? DCP_II : DCP_MI, k);
+          return (x + tr) + bg == target;
+        });
+        if (!mask) return DCP_TB_BAD;
+        int const j = __builtin_ctzll(mask);
+        size = 5 - (j >> 1);
+        prev = ((j & 1) ? ST_M : ST_I) | (k + 1);
       }
       else
       {
@@ -179,13 +232,13 @@ DCP_HD int dcp_traceback(DcpTraceIn const &in, uint32_t *buf, int64_t cap, DcpTr
       }
     }
     if (n + 1 >= cap) return DCP_TB_OVERFLOW;
-    buf[cap - 1 - n] = (uint32_t)state | ((uint32_t)size << 16);
+    if (Lanes::leader()) buf[cap - 1 - n] = (uint32_t)state | ((uint32_t)size << 16);
     ++n;
     state = prev;
     stage -= size;
     if (stage < 0) return DCP_TB_BAD;
   }
   if (n >= cap) return DCP_TB_OVERFLOW;
-  buf[cap - 1 - n] = (uint32_t)state;
+  if (Lanes::leader()) buf[cap - 1 - n] = (uint32_t)state;
   return (int)(n + 1);
 }

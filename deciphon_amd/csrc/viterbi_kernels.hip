@@ -270,17 +270,10 @@ __device__ void dcp_replay_one(float const *__restrict__ pool, DcpProfileDev con
     for (int k = 0; k < pf.K; ++k) nodes[k] = 0;
     return;
   }
-  DcpTraceIn in;
-  in.K = pf.K;
-  in.Kp = pf.Kp;
-  in.L = pb.L;
+  DcpTraceIn in = dcp_trace_in(pool, pf, code_rows + pb.code_row, xt_table + (size_t)pb.xt_row * DCP_XT_STRIDE, pb.L);
   in.sp = dcp_global<float const>((uintptr_t)pb.trellis) + (size_t)sub * dcp_block_table_floats(pb.L, pf.Kp, Bw);
   in.cells = in.sp + (size_t)dcp_block_slots(pb.L, Bw) * DCP_SP_STRIDE;
   in.row_base = block * Bw;
-  in.rows = pool + pf.rows_off;
-  in.trans = pool + pf.trans_off;
-  in.codes = code_rows + pb.code_row;
-  in.xt = xt_table + (size_t)pb.xt_row * DCP_XT_STRIDE;
   float *acc = dcp_global<float>((uintptr_t)aux[(size_t)naux + pb.out]) + acc_row * 3 * pf.K;
   dcp_replay_row(in, l, acc, xnodes + l, nodes);
   if (l == pb.L) // T of the last row: the score viterbi_path returns (c-core/viterbi.c:585-586,599)
@@ -311,189 +304,19 @@ hipError_t dcp_launch_replay(DcpLaunch const &a, int64_t const *aux, int B, int 
   return hipGetLastError();
 }
 
-// Fast path pass, step 2: one WAVEFRONT walks one window's DP table back from T to S.
-// Same decisions as the scalar dcp_traceback() of traceback.h (which documents them and
-// is what the CPU tests exercise); here the candidates of the visited state are spread
-// over the lanes in the reference's order -- lane j = (5 - t) * names + name -- so that
-// one step costs two load round trips instead of a chain of them, and the first
-// candidate equal to the stored value is the lowest set bit of a ballot.
-__device__ int dcp_traceback_wave(DcpTraceIn const &in, uint32_t *buf, int64_t cap, DcpTraceState *st)
+// What a walk that came to its end (r != 0: finished, or given up) leaves for the host and for the launches after
+// it; true when it did.
+__device__ __forceinline__ bool dcp_trace_end(int r, DcpTraceState *st, int32_t *nsteps)
 {
-  enum
+  if (r != 0 && DcpLanesWave::leader())
   {
-    ST_M = 0 << 14, ST_I = 1 << 14, ST_D = 2 << 14, ST_X = 3 << 14,
-    ST_S = ST_X | 3, ST_N = ST_X | 4, ST_B = ST_X | 5, ST_E = ST_X | 6, ST_J = ST_X | 7, ST_C = ST_X | 8, ST_T = ST_X | 9,
-  };
-  float const INF = __builtin_inff();
-  int const lane = (int)(threadIdx.x & 63);
-  int const K = in.K, Kp = in.Kp;
-  size_t const stride = (size_t)Kp + DCP_ROW_HDR;
-  int const base = in.row_base;
-  auto SP = [&](int l, int i) { return in.sp[(size_t)(l - base) * DCP_SP_STRIDE + i]; };
-  auto CELL = [&](int l, int s, int k) { return k < 0 ? INF : in.cells[((size_t)(l - base) * 3 + s) * (size_t)Kp + k]; };
-  auto TR = [&](int id, int k) { return in.trans[(size_t)id * Kp + k]; };
-  float const *xt = in.xt;
-
-  int state = ST_T, stage = in.L;
-  int64_t n = 0;
-  if (st && st->state != 0) // resume where the block after this one stopped (uniform: every lane reads the same)
-  {
-    state = st->state;
-    stage = st->stage;
-    n = st->n;
+    st->status = r > 0 ? 1 : r;
+    *nsteps = r;
   }
-  while (state != ST_S || stage)
-  {
-    if (stage <= in.lo) // the rest of the path lies in the block before this one
-    {
-      if (lane == 0)
-      {
-        st->state = state;
-        st->stage = stage;
-        st->n = n;
-      }
-      return 0;
-    }
-    int size = 0, prev = -1;
-    DcpCodeRow const cr = in.codes[stage];
-    if ((state & ST_X) == ST_X)
-    {
-      if (state == ST_T)
-      {
-        float const a = SP(stage, 3) + xt[DCP_ET], b = SP(stage, 4) + xt[DCP_CT];
-        if (a == b) return a < INF ? DCP_TB_TIE : DCP_TB_BAD;
-        prev = a < b ? ST_E : ST_C;
-      }
-      else if (state == ST_N || state == ST_J || state == ST_C)
-      {
-        int const self = state == ST_N ? 0 : state == ST_J ? 2 : 4;
-        float const target = SP(stage, self);
-        if (!(target < INF)) return DCP_TB_BAD;
-        float const t_in = state == ST_N ? xt[DCP_SN] : state == ST_J ? xt[DCP_EJ] : xt[DCP_EC];
-        float const t_self = state == ST_N ? xt[DCP_NN] : state == ST_J ? xt[DCP_JJ] : xt[DCP_CC];
-        int const t = 5 - (lane >> 1), which = lane & 1;
-        bool hit = false;
-        if (lane < 10 && t <= stage)
-        {
-          int const z = stage - t;
-          float const nil = in.rows[(size_t)cr.c[t - 1] * stride];
-          float const from = state == ST_N ? (z == 0 ? 0.0f : INF) : SP(z, 3);
-          float const cand = which == 0 ? (from + t_in) + nil : (SP(z, self) + t_self) + nil;
-          hit = cand == target;
-        }
-        unsigned long long const mask = __ballot(hit);
-        if (!mask) return DCP_TB_BAD;
-        int const j = __ffsll((long long)mask) - 1;
-        size = 5 - (j >> 1);
-        prev = (j & 1) ? state : (state == ST_N ? ST_S : ST_E);
-      }
-      else if (state == ST_B)
-      {
-        if (stage == 0) prev = ST_S;
-        else
-        {
-          float const target = SP(stage, 1);
-          int const eN = SP(stage, 0) + xt[DCP_NB] == target, eE = SP(stage, 3) + xt[DCP_EB] == target,
-                    eJ = SP(stage, 2) + xt[DCP_JB] == target;
-          if (eN + eE + eJ != 1 || !(target < INF)) return eN + eE + eJ > 1 ? DCP_TB_TIE : DCP_TB_BAD;
-          prev = eN ? ST_N : eE ? ST_E : ST_J;
-        }
-      }
-      else if (state == ST_E)
-      {
-        float const target = SP(stage, 3);
-        if (!(target < INF)) return DCP_TB_BAD;
-        int Qr = (K - 1) / DCP_REF_LANES + 1;
-        if (Qr < 2) Qr = 2;
-        int key = -1; // (reference lane << 16) | (65535 - k): highest lane, then lowest k
-        bool dtie = false;
-        for (int k = lane; k < K; k += 64)
-        {
-          dtie = dtie || CELL(stage, 2, k) == target;
-          if (CELL(stage, 0, k) == target)
-          {
-            int const cand = ((k / Qr) << 16) | (65535 - k);
-            key = cand > key ? cand : key;
-          }
-        }
-        if (__ballot(dtie)) return DCP_TB_TIE;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1)
-        {
-          int const o = __shfl_xor(key, d);
-          key = o > key ? o : key;
-        }
-        if (key < 0) return DCP_TB_BAD;
-        prev = ST_M | ((65535 - (key & 0xffff)) + 1);
-      }
-      else
-        return DCP_TB_BAD;
-    }
-    else
-    {
-      int const k = (state & 0x3FFF) - 1;
-      int const kind = state & ST_X;
-      if (k < 0 || k >= K) return DCP_TB_BAD;
-      if (kind == ST_M)
-      {
-        float const target = CELL(stage, 0, k);
-        if (!(target < INF)) return DCP_TB_BAD;
-        int const t = 5 - (lane >> 2), name = lane & 3; // BM, MM, IM, DM
-        bool hit = false;
-        if (lane < 20 && t <= stage)
-        {
-          int const z = stage - t;
-          float const m = in.rows[(size_t)cr.c[t - 1] * stride + DCP_ROW_HDR + k];
-          float const x = name == 0 ? SP(z, 1) : CELL(z, name - 1, k - 1);
-          float const tr = TR(name == 0 ? DCP_BM : name == 1 ? DCP_MM : name == 2 ? DCP_IM : DCP_DM, k);
-          hit = (x + tr) + m == target;
-        }
-        unsigned long long const mask = __ballot(hit);
-        if (!mask) return DCP_TB_BAD;
-        int const j = __ffsll((long long)mask) - 1;
-        size = 5 - (j >> 2);
-        int const nm = j & 3;
-        prev = nm == 0 ? ST_B : (nm == 1 ? ST_M : nm == 2 ? ST_I : ST_D) | k;
-      }
-      else if (kind == ST_I)
-      {
-        float const target = CELL(stage, 1, k);
-        if (!(target < INF)) return DCP_TB_BAD;
-        int const t = 5 - (lane >> 1), name = lane & 1; // II, MI
-        bool hit = false;
-        if (lane < 10 && t <= stage)
-        {
-          int const z = stage - t;
-          float const bg = in.rows[(size_t)cr.c[t - 1] * stride + 1];
-          float const x = name == 0 ? CELL(z, 1, k) : CELL(z, 0, k);
-          float const tr = TR(name == 0 ? DCP_II : DCP_MI, k);
-          hit = (x + tr) + bg == target;
-        }
-        unsigned long long const mask = __ballot(hit);
-        if (!mask) return DCP_TB_BAD;
-        int const j = __ffsll((long long)mask) - 1;
-        size = 5 - (j >> 1);
-        prev = ((j & 1) ? ST_M : ST_I) | (k + 1);
-      }
-      else
-      {
-        float const a = CELL(stage, 0, k - 1) + TR(DCP_MD, k), b = CELL(stage, 2, k - 1) + TR(DCP_DD, k);
-        if (a == b) return a < INF ? DCP_TB_TIE : DCP_TB_BAD;
-        prev = (a < b ? ST_M : ST_D) | k;
-      }
-    }
-    if (n + 1 >= cap) return DCP_TB_OVERFLOW;
-    if (lane == 0) buf[cap - 1 - n] = (uint32_t)state | ((uint32_t)size << 16);
-    ++n;
-    state = prev;
-    stage -= size;
-    if (stage < 0) return DCP_TB_BAD;
-  }
-  if (n >= cap) return DCP_TB_OVERFLOW;
-  if (lane == 0) buf[cap - 1 - n] = (uint32_t)state;
-  return (int)(n + 1);
+  return r != 0;
 }
 
+// Fast path pass, step 2: one WAVEFRONT walks one window's DP table back from T to S (traceback.h).
 __global__ __launch_bounds__(64) void dcp_traceback_kernel(
     float const *__restrict__ pool, DcpProfileDev const *__restrict__ profiles, DcpProblem const *__restrict__ problems,
     DcpCodeRow const *__restrict__ code_rows, float const *__restrict__ xt_table,
@@ -509,14 +332,7 @@ __global__ __launch_bounds__(64) void dcp_traceback_kernel(
   DcpTraceState *st = states + pb.out;
   if (st->status != 0) return; // finished, or given up, in a later block
   DcpProfileDev const pf = profiles[pb.profile];
-  DcpTraceIn in;
-  in.K = pf.K;
-  in.Kp = pf.Kp;
-  in.L = pb.L;
-  in.rows = pool + pf.rows_off;
-  in.trans = pool + pf.trans_off;
-  in.codes = code_rows + pb.code_row;
-  in.xt = xt_table + (size_t)pb.xt_row * DCP_XT_STRIDE;
+  DcpTraceIn in = dcp_trace_in(pool, pf, code_rows + pb.code_row, xt_table + (size_t)pb.xt_row * DCP_XT_STRIDE, pb.L);
   float const *tables = dcp_global<float const>((uintptr_t)arena + (uintptr_t)pb.trellis);
   // G > 0: through the (up to) G blocks launch `it` of dcp_cost_store_kernel has just written, the highest first
   for (int sub = 0; sub < (G > 0 ? G : 1); ++sub)
@@ -527,16 +343,8 @@ __global__ __launch_bounds__(64) void dcp_traceback_kernel(
     in.cells = in.sp + (size_t)dcp_block_slots(pb.L, B) * DCP_SP_STRIDE;
     in.row_base = b * B;
     in.lo = b > 0 ? b * B + 5 : -1;
-    int const r = dcp_traceback_wave(in, steps + step_off[pb.out], step_off[pb.out + 1] - step_off[pb.out], st);
-    if (r != 0)
-    {
-      if ((threadIdx.x & 63) == 0)
-      {
-        st->status = r > 0 ? 1 : r;
-        nsteps[pb.out] = r;
-      }
-      return;
-    }
+    int const r = dcp_traceback<DcpLanesWave>(in, steps + step_off[pb.out], step_off[pb.out + 1] - step_off[pb.out], st);
+    if (dcp_trace_end(r, st, nsteps + pb.out)) return;
   }
 }
 
@@ -593,28 +401,14 @@ __global__ __launch_bounds__(64 * W, (Q >= 8 ? 2 : 1)) void dcp_path_blocks_kern
     if (threadIdx.x < 64)
     {
       DcpTraceState *st = states + pb.out;
-      DcpTraceIn in;
-      in.K = pf.K;
-      in.Kp = pf.Kp;
-      in.L = pb.L;
+      DcpTraceIn in = dcp_trace_in(pool, pf, codes, xt, pb.L);
       in.sp = tab_sp;
       in.cells = tab_sp + (size_t)slots * DCP_SP_STRIDE;
-      in.rows = pool + pf.rows_off;
-      in.trans = pool + pf.trans_off;
-      in.codes = codes;
-      in.xt = xt;
       in.row_base = block * B;
       in.lo = block > 0 ? block * B + 5 : -1;
-      int const r = dcp_traceback_wave(in, steps + step_off[pb.out], step_off[pb.out + 1] - step_off[pb.out], st);
-      if (threadIdx.x == 0)
-      {
-        walk_over = r != 0;
-        if (r != 0)
-        {
-          st->status = r > 0 ? 1 : r;
-          nsteps[pb.out] = r;
-        }
-      }
+      int const r = dcp_traceback<DcpLanesWave>(in, steps + step_off[pb.out], step_off[pb.out + 1] - step_off[pb.out], st);
+      bool const over = dcp_trace_end(r, st, nsteps + pb.out);
+      if (threadIdx.x == 0) walk_over = over;
     }
     __syncthreads();
     if (walk_over) break; // finished, or given up (a tie the values cannot resolve: the literal pass takes it)
@@ -757,8 +551,7 @@ __global__ void dcp_encode_kernel(unsigned char const *__restrict__ nt, int64_t 
   }
 }
 
-// trellis_unzip on the device (c-core/trellis.c:147-167 with previous_state and
-// emission_size, :51-113): one thread walks one problem's trellis from T at stage L
+// trellis_unzip on the device (dcp_trellis_step, dcp_states.h): one thread walks one problem's trellis from T at stage L
 // back to S at stage 0 and writes the steps, packed as state_id | seqsize << 16, from
 // the END of its buffer backwards, so that they read forwards in path order.
 // nsteps[p] = number of steps, or -1 when the buffer was too small / the trellis is
@@ -776,61 +569,17 @@ __global__ void dcp_unzip_kernel(DcpProfileDev const *__restrict__ profiles, Dcp
   uint16_t const *nodes = reinterpret_cast<uint16_t const *>(xnodes + (L + 1));
   uint32_t *buf = steps + step_off[pb.out];
   int64_t const cap = step_off[pb.out + 1] - step_off[pb.out];
-  enum
-  {
-    ST_M = 0 << 14, ST_I = 1 << 14, ST_D = 2 << 14, ST_X = 3 << 14, // c-core/state.h:9-25
-    ST_S = ST_X | 3, ST_N = ST_X | 4, ST_B = ST_X | 5, ST_E = ST_X | 6, ST_J = ST_X | 7, ST_C = ST_X | 8, ST_T = ST_X | 9,
-  };
   int state = ST_T, stage = L;
   int64_t n = 0;
   bool bad = false;
   while ((state != ST_S || stage) && !bad)
   {
-    int size = 0, prev = 0;
-    if ((state & ST_X) == ST_X)
-    {
-      uint32_t const x = xnodes[stage];
-      if (state == ST_N) { unsigned v = x & 0xF; size = (int)(v % 5) + 1; prev = v / 5 ? ST_N : ST_S; }
-      else if (state == ST_B) { unsigned v = (x >> 4) & 0x3; prev = v == 0 ? ST_S : v == 1 ? ST_N : v == 2 ? ST_E : ST_J; }
-      else if (state == ST_E) { unsigned v = (x >> 6) & 0x7FFF; prev = (v & 1 ? ST_D : ST_M) | (int)(v / 2 + 1); }
-      else if (state == ST_C) { unsigned v = (x >> 21) & 0xF; size = (int)(v % 5) + 1; prev = v / 5 ? ST_C : ST_E; }
-      else if (state == ST_T) { unsigned v = (x >> 25) & 0x1; prev = v ? ST_C : ST_E; }
-      else if (state == ST_J) { unsigned v = (x >> 26) & 0xF; size = (int)(v % 5) + 1; prev = v / 5 ? ST_J : ST_E; }
-      else bad = true;
-    }
-    else
-    {
-      int const idx = (state & 0x3FFF) - 1;
-      if (idx < 0 || idx >= K) { bad = true; break; }
-      uint16_t const w = nodes[(size_t)stage * (size_t)K + (size_t)idx];
-      int const kind = state & ST_X;
-      if (kind == ST_M)
-      {
-        unsigned v = w & 0x1F;
-        size = (int)(v % 5) + 1;
-        unsigned s = v / 5;
-        if (s == 0) prev = ST_B;
-        else if (idx <= 0) bad = true;
-        else prev = (s == 1 ? ST_M : s == 2 ? ST_I : ST_D) | idx;
-      }
-      else if (kind == ST_D)
-      {
-        unsigned v = (w >> 5) & 0x1;
-        if (idx <= 0) bad = true;
-        else prev = (v ? ST_D : ST_M) | idx;
-      }
-      else
-      {
-        unsigned v = (w >> 6) & 0xF;
-        size = (int)(v % 5) + 1;
-        prev = (v / 5 ? ST_I : ST_M) | (idx + 1);
-      }
-    }
-    if (bad || n + 1 >= cap) { bad = true; break; }
-    buf[cap - 1 - n] = (uint32_t)state | ((uint32_t)size << 16);
+    DcpStep const step = dcp_trellis_step(K, xnodes, nodes, state, stage);
+    if (step.prev < 0 || n + 1 >= cap) { bad = true; break; }
+    buf[cap - 1 - n] = (uint32_t)state | ((uint32_t)step.size << 16);
     ++n;
-    state = prev;
-    stage -= size;
+    state = step.prev;
+    stage -= step.size;
     if (stage < 0) bad = true;
   }
   if (!bad && n < cap)

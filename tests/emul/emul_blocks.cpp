@@ -43,16 +43,9 @@ static int path_blocks_qw(float const *pool, DcpProfileDev const &pf, DcpCodeRow
     w.init(pool, pf, codes, xt);
     int const last = B > 0 ? (block + 1) * B + 5 : L;
     w.run(L, out, last < L ? last : L);
-    DcpTraceIn in;
-    in.K = pf.K;
-    in.Kp = pf.Kp;
-    in.L = L;
+    DcpTraceIn in = dcp_trace_in(pool, pf, codes, xt, L);
     in.sp = sp.data();
     in.cells = cells.data();
-    in.rows = pool + pf.rows_off;
-    in.trans = pool + pf.trans_off;
-    in.codes = codes;
-    in.xt = xt;
     in.row_base = block * B;
     in.lo = block > 0 ? block * B + 5 : -1;
     r = dcp_traceback(in, buf, cap, &st);

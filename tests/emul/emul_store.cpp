@@ -5,7 +5,8 @@
 #include "../../deciphon_amd/csrc/viterbi_body.h"
 #include "../../deciphon_amd/csrc/traceback.h"
 
-// ---- fast path pass: cost pass with the DP table stored, then the scalar traceback ----
+// ---- fast path pass: cost pass with the DP table stored, then the traceback that ships (traceback.h), its 64
+// lanes taken one after the other (DcpLanesHost) ----
 template <int Q, int W>
 static void store_q_(float const *pool, DcpProfileDev const &pf, DcpCodeRow const *codes, int L, float const *xt,
                      float *out, float *cells, float *sp)
@@ -42,16 +43,9 @@ extern "C" int emul_cost_store(float const *pool, DcpProfileDev const *pf, DcpCo
 extern "C" int emul_traceback(float const *pool, DcpProfileDev const *pf, DcpCodeRow const *codes, int L,
                               float const *xt, float const *cells, float const *sp, uint32_t *buf, long cap)
 {
-  DcpTraceIn in;
-  in.K = pf->K;
-  in.Kp = pf->Kp;
-  in.L = L;
+  DcpTraceIn in = dcp_trace_in(pool, *pf, codes, xt, L);
   in.sp = sp;
   in.cells = cells;
-  in.rows = pool + pf->rows_off;
-  in.trans = pool + pf->trans_off;
-  in.codes = codes;
-  in.xt = xt;
   return dcp_traceback(in, buf, cap);
 }
 

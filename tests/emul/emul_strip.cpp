@@ -52,16 +52,9 @@ extern "C" int emul_strip_cost(float const *pool, DcpProfileDev const *pf, DcpCo
 extern "C" int emul_replay(float const *pool, DcpProfileDev const *pf, DcpCodeRow const *codes, int L,
                            float const *xt, float const *cells, float const *sp, uint32_t *xnodes, uint16_t *nodes)
 {
-  DcpTraceIn in;
-  in.K = pf->K;
-  in.Kp = pf->Kp;
-  in.L = L;
+  DcpTraceIn in = dcp_trace_in(pool, *pf, codes, xt, L);
   in.sp = sp;
   in.cells = cells;
-  in.rows = pool + pf->rows_off;
-  in.trans = pool + pf->trans_off;
-  in.codes = codes;
-  in.xt = xt;
   std::vector<float> acc((size_t)3 * pf->K);
   xnodes[0] = 0;
   for (int k = 0; k < pf->K; ++k) nodes[k] = 0;
