@@ -332,48 +332,29 @@ template <int W> struct Group
     Dp = r.z;
   }
   // E = min over the waves' minima; could anything entering a wave at its first lane still
-  // lower the D it published?  (one b64 read per wave)
+  // lower the D it published?  (one b64 read per wave)  The slack is 1e-4 of the magnitudes summed, |E| + tdd(w), not
+  // of the sum: match costs may be negative, and E + tdd(w) may cancel (viterbi_body.h, CostWave::row).
   DCP_FN void get_e_could(int par, float &E, bool &could) const
   {
+    static_assert(W <= 8, "the cost kernels run at most 8 wavefronts (DCP_CLASS_TABLE): tddv");
     float const *r = reinterpret_cast<float const *>(rec + par * 17 + 1);
-    if constexpr (W <= 8)
+    float d[W], e[W];
+#pragma unroll
+    for (int w = 0; w < W; ++w)
     {
-      float d[W], e[W];
-#pragma unroll
-      for (int w = 0; w < W; ++w)
-      {
-        float2 const de = *reinterpret_cast<float2 const *>(r + 4 * w + 2);
-        d[w] = de.x;
-        e[w] = de.y;
-      }
-      float m = e[0];
-#pragma unroll
-      for (int w = 1; w < W; ++w) m = __builtin_fminf(m, e[w]);
-      bool any = false;
-#pragma unroll
-      for (int w = 0; w < W; ++w)
-      {
-        float const s = m + tddv[w];
-        any = any || __builtin_fminf(s * 0.9999f, s * 1.0001f) < d[w];
-      }
-      E = m;
-      could = any;
+      float2 const de = *reinterpret_cast<float2 const *>(r + 4 * w + 2);
+      d[w] = de.x;
+      e[w] = de.y;
     }
-    else // 1024-thread workgroups are capped at 128 VGPRs: two passes over LDS instead of 2W registers
-    {
-      float m = r[3];
+    float m = e[0];
 #pragma unroll
-      for (int w = 1; w < W; ++w) m = __builtin_fminf(m, r[4 * w + 3]);
-      bool any = false;
+    for (int w = 1; w < W; ++w) m = __builtin_fminf(m, e[w]);
+    float const am = __builtin_fabsf(m);
+    bool any = false;
 #pragma unroll
-      for (int w = 0; w < W; ++w)
-      {
-        float const s = m + tdd[w];
-        any = any || __builtin_fminf(s * 0.9999f, s * 1.0001f) < r[4 * w + 2];
-      }
-      E = m;
-      could = any;
-    }
+    for (int w = 0; w < W; ++w) any = any || __builtin_fmaf(-1e-4f, am + tddv[w], m + tddv[w]) < d[w];
+    E = m;
+    could = any;
   }
   // ---- StripWave (K > 4096): the same exchange with the previous strip in front of wave 0 ----
   template <int Q> DCP_FN void put_tdd_strip(int s, lf const (&DD)[Q])
@@ -403,12 +384,13 @@ template <int W> struct Group
 #pragma unroll
     for (int w = 1; w < W; ++w) m = __builtin_fminf(m, r[4 * w + 3]);
     float const lo = __builtin_fminf(m, floor_e);
+    float const al = __builtin_fabsf(lo);
     bool any = false;
 #pragma unroll
     for (int w = 0; w < W; ++w)
     {
-      float const v = lo + tdd[16 + s * 16 + w];
-      any = any || __builtin_fminf(v * 0.9999f, v * 1.0001f) < r[4 * w + 2];
+      float const t = tdd[16 + s * 16 + w];
+      any = any || __builtin_fmaf(-1e-4f, al + t, lo + t) < r[4 * w + 2];
     }
     E = m;
     could = any;

@@ -393,6 +393,14 @@ template <int Q, int W, bool STORE = false, int POLICY = DCP_SHAPE_POLICY(Q, W)>
       // order of the fp32 additions) proves it -- every wave evaluates the same test on the
       // same records.  If it fails (profiles whose delete runs are nearly free) the row falls
       // back to the exchange-until-stable protocol below, barriers and all.
+      // The margin: fp32 addition is monotonic and MD, DD >= 0, so what arrives is no less than the chain
+      // fl(..fl(fl(E + DD) + DD)..) over the wave's n <= 511 positions but the first.  Every partial sum lies in
+      // [-|E|, |E| + tdd(w)], so each step rounds by at most 2^-24 (|E| + tdd(w)) and the chain is at least
+      // E + tdd(w) - 511 * 2^-24 (|E| + tdd(w)) = E + tdd(w) - 3.1e-5 (|E| + tdd(w)); the butterfly sum of tdd
+      // (Q + 5 additions deep), the sum s and the product add less than 2e-6 of the same.  The test is therefore
+      // s - 1e-4 (|E| + tdd(w)) >= D_last(w)  (get_e_could), NOT s (1 - 1e-4): match costs may be negative, and
+      // with E = -996, tdd = 998 the chain rounds 5e-3 below s = 2 (tests/test_emul_wave_exchange.py,
+      // test_a_run_that_cancels_what_entered_it).  For E >= 0 the two are the same number.
       int const par = l & 1;
       lf const inf = lf_splat(DCP_INF);
       lf x, Dsh;

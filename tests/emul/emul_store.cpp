@@ -32,6 +32,8 @@ extern "C" int emul_cost_store(float const *pool, DcpProfileDev const *pf, DcpCo
   case 804: store_q_<8, 4>(pool, *pf, codes, L, xt, out, cells, sp); return 0;
   case 601: store_q_<6, 1>(pool, *pf, codes, L, xt, out, cells, sp); return 0;
   case 602: store_q_<6, 2>(pool, *pf, codes, L, xt, out, cells, sp); return 0;
+  case 604: store_q_<6, 4>(pool, *pf, codes, L, xt, out, cells, sp); return 0;
+  case 808: store_q_<8, 8>(pool, *pf, codes, L, xt, out, cells, sp); return 0;
   case 302: store_q_<3, 2>(pool, *pf, codes, L, xt, out, cells, sp); return 0;
   case 304: store_q_<3, 4>(pool, *pf, codes, L, xt, out, cells, sp); return 0;
   case 402: store_q_<4, 2>(pool, *pf, codes, L, xt, out, cells, sp); return 0;

@@ -42,6 +42,7 @@ extern "C" int emul_strip_cost(float const *pool, DcpProfileDev const *pf, DcpCo
   case 202: strip_q<2, 2>(pool, *pf, codes, L, xt, out, ring, cells, sp); return 0;
   case 402: strip_q<4, 2>(pool, *pf, codes, L, xt, out, ring, cells, sp); return 0;
   case 104: strip_q<1, 4>(pool, *pf, codes, L, xt, out, ring, cells, sp); return 0;
+  case 408: strip_q<4, 8>(pool, *pf, codes, L, xt, out, ring, cells, sp); return 0; // the engine's own: strips of 2048
   default: return -1;
   }
 }

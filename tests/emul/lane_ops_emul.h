@@ -111,16 +111,27 @@ template <int W> struct Group
   }
   bool seg_any(lm m) { return wave_any(m); } // extra turns in a converged wave change nothing
   lm seg_first() { lm r; EM_FOR r.v[i_] = (i_ % 64) == 0; return r; }
+  // the sum of a wave's DD but the first, added in the order of lane_ops_gpu.h (put_tdd): every lane its own
+  // positions, then a butterfly over the lanes -- the same fp32 value, so the same rows fall back here and there
+  template <int Q> static float wave_tdd(lf const (&DD)[Q], int w)
+  {
+    float t[64];
+    for (int i = 0; i < 64; ++i)
+    {
+      t[i] = i == 0 ? 0.0f : DD[0].v[64 * w + i];
+      for (int q = 1; q < Q; ++q) t[i] += DD[q].v[64 * w + i];
+    }
+    for (int d = 32; d >= 1; d >>= 1)
+    {
+      float u[64];
+      for (int i = 0; i < 64; ++i) u[i] = t[i] + t[i ^ d];
+      memcpy(t, u, sizeof t);
+    }
+    return t[63];
+  }
   template <int Q> void put_tdd(lf const (&DD)[Q])
   {
-    for (int w = 0; w < W; ++w)
-    {
-      float t = 0.0f;
-      for (int i = 64 * w; i < 64 * w + 64; ++i)
-        for (int q = 0; q < Q; ++q)
-          if (!(i == 64 * w && q == 0)) t += DD[q].v[i];
-      tdd[w] = t;
-    }
+    for (int w = 0; w < W; ++w) tdd[w] = wave_tdd<Q>(DD, w);
   }
   void put_rec(int par, lf m_last, lf i_last, lf d_last, lf m_all)
   {
@@ -149,8 +160,7 @@ template <int W> struct Group
     bool any = false;
     for (int w = 0; w < W; ++w)
     {
-      float const s = m + tdd[w];
-      float const bound = fminf(s * 0.9999f, s * 1.0001f);
+      float const bound = fmaf(-1e-4f, fabsf(m) + tdd[w], m + tdd[w]); // as lane_ops_gpu.h, to the bit
       any = any || bound < rec[par][w].d;
     }
     E = m;
@@ -174,14 +184,7 @@ template <int W> struct Group
   float tdds[64][16];
   template <int Q> void put_tdd_strip(int s, lf const (&DD)[Q])
   {
-    for (int w = 0; w < W; ++w)
-    {
-      float t = 0.0f;
-      for (int i = 64 * w; i < 64 * w + 64; ++i)
-        for (int q = 0; q < Q; ++q)
-          if (!(i == 64 * w && q == 0)) t += DD[q].v[i];
-      tdds[s][w] = t;
-    }
+    for (int w = 0; w < W; ++w) tdds[s][w] = wave_tdd<Q>(DD, w);
   }
   void put_carry(int par, lf m, lf i, lf d) { carry[par] = Rec{m.v[em_lanes - 1], i.v[em_lanes - 1], d.v[em_lanes - 1], INFINITY}; }
   void put_carry_inf(int par) { carry[par] = Rec{INFINITY, INFINITY, INFINITY, INFINITY}; }
@@ -193,8 +196,7 @@ template <int W> struct Group
     bool any = false;
     for (int w = 0; w < W; ++w)
     {
-      float const v = lo + tdds[s][w];
-      any = any || fminf(v * 0.9999f, v * 1.0001f) < rec[par][w].d;
+      any = any || fmaf(-1e-4f, fabsf(lo) + tdds[s][w], lo + tdds[s][w]) < rec[par][w].d;
     }
     E = m;
     could = any;
