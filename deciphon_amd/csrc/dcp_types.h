@@ -103,8 +103,56 @@ DCP_HDI long long dcp_block_table_floats(int L, int Kp, int B)
   return (long long)dcp_block_slots(L, B) * (DCP_SP_STRIDE + 3LL * Kp);
 }
 
+// Checkpoint j, the state after row j * B, exists iff block j does: j * B + 5 < L.  Is the state after row l one?
+DCP_HDI bool dcp_ckpt_after(int L, int B, int l) { return B > 0 && l % B == 0 && l + 5 < L; }
+DCP_HDI int dcp_ckpt_slot(int j) { return j - 1; } // where checkpoint j lies among a window's checkpoints
+
+// Block j of a window as the comment above has it, in rows of the window.  Everything that computes, walks or replays a
+// block -- the kernels, the host and the wave emulator (tests/emul) -- takes these from here and holds no such
+// arithmetic of its own.  B = 0 is the one block that is the whole window.
+struct DcpBlock
+{
+  int row_base; // the row it starts from, j * B: row l lies at slot l - row_base of the table
+  int last;     // the last row it computes: row_base + B + 5, clamped to L
+  int lo;       // the traceback hands over to block j - 1 at the first stage <= lo = row_base + 5; -1 for block 0
+  int first;    // the first row the replay serves (row_replay.h), lo + 1: the traceback's partition; 0 for block 0
+  int ckpt;     // slot of the checkpoint it starts from among the window's checkpoints; -1 for block 0 (from row 0)
+  int slots;    // dcp_block_slots: its table is specials[slots][DCP_SP_STRIDE], then cells[slots][3][Kp]
+};
+DCP_HDI DcpBlock dcp_block(int L, int B, int j)
+{
+  DcpBlock b;
+  b.slots = dcp_block_slots(L, B);
+  b.row_base = j * B;
+  b.last = L - b.row_base < b.slots ? L : b.row_base + b.slots - 1;
+  b.lo = j > 0 ? b.row_base + 5 : -1;
+  b.first = b.lo + 1;
+  b.ckpt = dcp_ckpt_slot(j);
+  return b;
+}
+
+// G blocks of a window are computed side by side into G tables, dcp_block_table_floats apart, the last blocks first:
+// the block that launch `it` gives to table `sub`, negative when the window has none left for it ...
+DCP_HDI int dcp_group_block(int L, int B, int G, int it, int sub) { return dcp_num_blocks(L, B) - 1 - (it * G + sub); }
+// ... and where that table lies behind the first, in floats
+DCP_HDI long long dcp_group_table(int L, int Kp, int B, int sub) { return sub * dcp_block_table_floats(L, Kp, B); }
+
 // rows of the trellis that the replay of one block can serve (row_replay.h): B + 5 and row 0, for block 0
 DCP_HDI int dcp_replay_block_rows(int B) { return B + 6; }
+
+// The replay of launch `it` (row_replay.h): thread r of a window takes row *row of the block in table *sub -- a table's
+// worth of threads per table, the last six of which have no row in a block above block 0.  False: no row for thread r.
+DCP_HDI bool dcp_replay_thread_row(int L, int B, int G, int it, int r, int *sub, DcpBlock *blk, int *row)
+{
+  int const per = dcp_block_slots(L, B);
+  *sub = r / per;
+  if (*sub >= G) return false;
+  int const j = dcp_group_block(L, B, G, it, *sub);
+  if (j < 0) return false;
+  *blk = dcp_block(L, B, j);
+  *row = blk->first + r % per;
+  return *row <= blk->last;
+}
 
 // where the traceback of one window stands between blocks (all zero = not started)
 struct DcpTraceState

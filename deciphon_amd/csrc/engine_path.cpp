@@ -57,6 +57,18 @@ int group_chunk_cap(dcp_hip const *x, size_t per_block, size_t fixed)
   return chunk > fixed + slack + per_block ? (int)std::min<size_t>((chunk - fixed - slack) / per_block, (size_t)INT32_MAX) : 1;
 }
 
+// How many blocks of a window go side by side: what 90 % of the budget holds of them at `one` bytes each beside
+// `fixed`, no more than the window with the most blocks has (`most`) or a chunk takes (`cap`, group_chunk_cap).
+// DECIPHON_HIP_PATH_GROUP overrides.
+int group_size(size_t budget, double fixed, double one, int most, int cap)
+{
+  double const room = 0.9 * (double)budget - fixed;
+  int G = one > 0 && room > one ? (int)std::min<double>(room / one, (double)most) : 1;
+  G = std::min(G, cap);
+  if (char const *e = getenv("DECIPHON_HIP_PATH_GROUP")) G = std::max(atoi(e), 1);
+  return std::max(1, std::min(G, most));
+}
+
 void note_placed(dcp_hip *x) { x->path_table_bytes = std::max(x->path_table_bytes, (int64_t)x->tables.placed); }
 
 // the path pass works on its own bank and streams (see dcp_hip::bank): swapped in for the duration of a call
@@ -216,11 +228,7 @@ int literal_strips(dcp_hip *x, std::vector<dcp_hip_window> const &w, std::vector
       cap = std::min(cap, group_chunk_cap(x, per_block, ckpt_bytes(L, hp.Kp, hp.W, B, true)));
       if (count_blocked) ++x->path_blocked;
     }
-    double const room = 0.9 * (double)budget - fixed;
-    if (one > 0 && room > one) G = (int)std::min<double>(room / one, (double)most);
-    G = std::min(G, cap);
-    if (char const *e = getenv("DECIPHON_HIP_PATH_GROUP")) G = std::max(atoi(e), 1);
-    G = std::max(1, std::min(G, most));
+    G = group_size(budget, fixed, one, most, cap);
   }
   HIP_TRY(x, x->d_aux.reserve(4 * sl.size()), DCP_ENOMEM);
   for (size_t sb = 0; sb < sl.size();)
@@ -272,20 +280,14 @@ int literal_strips(dcp_hip *x, std::vector<dcp_hip_window> const &w, std::vector
     // (null, alt) of the slice's windows go behind the n scores of the pass
     DcpLaunch store = a;
     store.out = a.out + n;
-    if (max_blocks == 0)
+    // the checkpoints of the windows in blocks, then G blocks at a time; a window that keeps its whole table is one
+    // block of the first round
+    int64_t const *d_ckpt = x->d_aux.p + 2 * (size_t)ns;
+    if (max_blocks > 0) HIP_TRY(x, dcp_launch_strip_ckpt(store, d_ckpt, B), DCP_EFUNCUSE);
+    for (int it = 0; it == 0 || it * G < max_blocks; ++it)
     {
-      HIP_TRY(x, dcp_launch_cost_store(DCP_STRIP_CLASS, store, nullptr, 0, 0), DCP_EFUNCUSE);
-      HIP_TRY(x, dcp_launch_replay(a, x->d_aux.p, B, 1, 0, max_rows), DCP_EFUNCUSE);
-    }
-    else
-    {
-      int64_t const *d_ckpt = x->d_aux.p + 2 * (size_t)ns;
-      HIP_TRY(x, dcp_launch_strip_ckpt(store, d_ckpt, B), DCP_EFUNCUSE);
-      for (int it = 0; it * G < max_blocks; ++it)
-      {
-        HIP_TRY(x, dcp_launch_strip_store(store, d_ckpt, B, G, it), DCP_EFUNCUSE);
-        HIP_TRY(x, dcp_launch_replay(a, x->d_aux.p, B, G, it, max_rows), DCP_EFUNCUSE);
-      }
+      HIP_TRY(x, dcp_launch_strip_store(store, d_ckpt, B, G, it), DCP_EFUNCUSE);
+      HIP_TRY(x, dcp_launch_replay(a, x->d_aux.p, B, G, it, max_rows), DCP_EFUNCUSE);
     }
     HIP_TRY(x, hipStreamSynchronize(x->stream), DCP_EFUNCUSE); // aux is read by the copy above; the next slice reuses the tables
     sb = se;
@@ -427,21 +429,16 @@ int path_fast(dcp_hip *x, int b, int e, std::vector<int> &redo)
       if (a.nprob <= 0) continue;
       a.arena = nullptr; // DcpProblem::trellis holds the table's address
       if ((rc = fk.enter(x->cls_branch[c], a))) return rc;
-      if (c == DCP_STRIP_CLASS && strip_blocks == 0) // their tables hold the whole window: one block
+      if (c == DCP_STRIP_CLASS)
       {
-        HIP_TRY(x, dcp_launch_cost_store(c, a, nullptr, 0, 0), DCP_EFUNCUSE);
-        HIP_TRY(x, dcp_launch_traceback(a, x->d_steps.p, x->d_step_off.p, x->d_nsteps.p, x->d_trace.p, 0, 0), DCP_EFUNCUSE);
-      }
-      else if (c == DCP_STRIP_CLASS)
-      {
-        // some go in blocks: their checkpoints, then G blocks at a time; a window that keeps its whole table (no
+        // the checkpoints of those that go in blocks, then G blocks at a time; a window that keeps its whole table (no
         // checkpoint address) is one block of the first round
         int const G = std::max(x->path_group, 1);
-        HIP_TRY(x, dcp_launch_strip_ckpt(a, x->d_ckpt_addr.p, B), DCP_EFUNCUSE);
-        for (int it = 0; it * G < strip_blocks; ++it)
+        if (strip_blocks > 0) HIP_TRY(x, dcp_launch_strip_ckpt(a, x->d_ckpt_addr.p, B), DCP_EFUNCUSE);
+        for (int it = 0; it == 0 || it * G < strip_blocks; ++it)
         {
           HIP_TRY(x, dcp_launch_strip_store(a, x->d_ckpt_addr.p, B, G, it), DCP_EFUNCUSE);
-          HIP_TRY(x, dcp_launch_traceback(a, x->d_steps.p, x->d_step_off.p, x->d_nsteps.p, x->d_trace.p, B, 0, G, it,
+          HIP_TRY(x, dcp_launch_traceback(a, x->d_steps.p, x->d_step_off.p, x->d_nsteps.p, x->d_trace.p, B, G, it,
                                           x->d_ckpt_addr.p),
                   DCP_EFUNCUSE);
         }
@@ -458,8 +455,8 @@ int path_fast(dcp_hip *x, int b, int e, std::vector<int> &redo)
         if (max_blocks > 1) HIP_TRY(x, dcp_launch_cost_ckpt(c, a, x->d_ckpt_addr.p, B), DCP_EFUNCUSE);
         for (int it = 0; it * G < max_blocks; ++it)
         {
-          HIP_TRY(x, dcp_launch_cost_store(c, a, x->d_ckpt_addr.p, B, 0, G, it), DCP_EFUNCUSE);
-          HIP_TRY(x, dcp_launch_traceback(a, x->d_steps.p, x->d_step_off.p, x->d_nsteps.p, x->d_trace.p, B, 0, G, it), DCP_EFUNCUSE);
+          HIP_TRY(x, dcp_launch_cost_store(c, a, x->d_ckpt_addr.p, B, G, it), DCP_EFUNCUSE);
+          HIP_TRY(x, dcp_launch_traceback(a, x->d_steps.p, x->d_step_off.p, x->d_nsteps.p, x->d_trace.p, B, G, it), DCP_EFUNCUSE);
         }
       }
       if ((rc = fk.leave(x->cls_branch[c]))) return rc;
@@ -559,11 +556,7 @@ int path_run(dcp_hip *x, int n, dcp_hip_window const *w)
           cap = std::min(cap, group_chunk_cap(x, block_table_bytes(L, hp.Kp, B), ckpt_bytes(L, hp.Kp, hp.W, B, strip)));
         }
       }
-      double const room = 0.9 * (double)budget - fixed;
-      int G = one > 0 && room > one ? (int)std::min<double>(room / one, (double)most) : 1;
-      G = std::min(G, cap); // (group_chunk_cap: a window's placement stays inside a chunk of a held arena)
-      if (char const *e = getenv("DECIPHON_HIP_PATH_GROUP")) G = std::max(atoi(e), 1);
-      x->path_group = std::max(1, std::min(G, most));
+      x->path_group = group_size(budget, fixed, one, most, cap);
     }
     for (int b = 0; b < n;)
     {

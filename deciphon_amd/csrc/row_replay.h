@@ -156,3 +156,24 @@ DCP_HDI void dcp_replay_row(DcpTraceIn const &in, int l, float *acc, uint32_t *x
   nodes[0] = (uint16_t)(nodes[0] & ~(1u << 5));          // position 0 has no D pointer
   nodes[K - 1] = (uint16_t)(nodes[K - 1] & ~(15u << 6)); // the last position has no I pointer
 }
+
+// Thread r of a window in launch `it` of the groups of G blocks (dcp_types.h: dcp_replay_thread_row), from the window's
+// G tables (the first at `tables`): its row's words into the window's trellis xnodes[L + 1], nodes[(L + 1)][K], with
+// row r of the window's scratch (3 K floats a row).  Returns the row, or -1 when the thread has none.
+DCP_HDI int dcp_replay_thread(DcpTraceIn &in, float const *tables, int B, int G, int it, int r, float *scratch,
+                              uint32_t *xnodes, uint16_t *nodes)
+{
+  int sub, l;
+  DcpBlock blk;
+  if (!dcp_replay_thread_row(in.L, B, G, it, r, &sub, &blk, &l)) return -1;
+  nodes += (size_t)l * in.K;
+  if (l == 0) // before(): every field 0 (c-core/viterbi.c:602-629)
+  {
+    xnodes[0] = 0;
+    for (int k = 0; k < in.K; ++k) nodes[k] = 0;
+    return 0;
+  }
+  dcp_trace_bind(in, tables + dcp_group_table(in.L, in.Kp, B, sub), blk);
+  dcp_replay_row(in, l, scratch + (size_t)r * 3 * in.K, xnodes + l, nodes);
+  return l;
+}

@@ -41,7 +41,7 @@ struct DcpTraceIn
   int row_base = 0, lo = -1;
 };
 
-// A window's side of a DcpTraceIn; the table (sp, cells, row_base) and lo are the caller's to set.
+// A window's side of a DcpTraceIn; the table (sp, cells, row_base) and lo come with a block: dcp_trace_bind.
 DCP_HDI DcpTraceIn dcp_trace_in(float const *pool, DcpProfileDev const &pf, DcpCodeRow const *codes, float const *xt, int L)
 {
   DcpTraceIn in;
@@ -54,6 +54,15 @@ DCP_HDI DcpTraceIn dcp_trace_in(float const *pool, DcpProfileDev const &pf, DcpC
   in.codes = codes;
   in.xt = xt;
   return in;
+}
+
+// `table` holds block blk of the window (dcp_types.h)
+DCP_HDI void dcp_trace_bind(DcpTraceIn &in, float const *table, DcpBlock const &blk)
+{
+  in.sp = table;
+  in.cells = table + (size_t)blk.slots * DCP_SP_STRIDE;
+  in.row_base = blk.row_base;
+  in.lo = blk.lo;
 }
 
 struct DcpLanesHost
@@ -241,4 +250,22 @@ DCP_HDI int dcp_traceback(DcpTraceIn const &in, uint32_t *buf, int64_t cap, DcpT
   if (n >= cap) return DCP_TB_OVERFLOW;
   if (Lanes::leader()) buf[cap - 1 - n] = (uint32_t)state;
   return (int)(n + 1);
+}
+
+// Launch `it` of the groups of G blocks (dcp_types.h): the walk through the blocks that the launch left in the window's
+// G tables (the first at `tables`), the highest first.  Returns what dcp_traceback does: 0 when the walk stands at the
+// lower end of the last of them, or the window had no block in this launch.
+template <class Lanes = DcpLanesHost>
+DCP_HDI int dcp_traceback_group(DcpTraceIn &in, float const *tables, int B, int G, int it, uint32_t *buf, int64_t cap,
+                                DcpTraceState *st)
+{
+  int r = 0;
+  for (int sub = 0; sub < G && r == 0; ++sub)
+  {
+    int const j = dcp_group_block(in.L, B, G, it, sub);
+    if (j < 0) break;
+    dcp_trace_bind(in, tables + dcp_group_table(in.L, in.Kp, B, sub), dcp_block(in.L, B, j));
+    r = dcp_traceback<Lanes>(in, buf, cap, st);
+  }
+  return r;
 }

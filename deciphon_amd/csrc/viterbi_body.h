@@ -155,6 +155,7 @@ template <int Q, int W, bool STORE = false, int POLICY = DCP_SHAPE_POLICY(Q, W)>
   float const *__restrict__ ckpt_in = nullptr;
   int ckpt_every = 0;
   int row_base = 0;
+  static DCP_FN long long ckpt_floats(int Kp) { return dcp_ckpt_floats(Kp, W); } // from one checkpoint to the next
 
   DCP_FN void save_ring(float *__restrict__ to)
   {
@@ -588,8 +589,8 @@ template <int Q, int W, bool STORE = false, int POLICY = DCP_SHAPE_POLICY(Q, W)>
       row<3>(l + 2, Lend);
       row<4>(l + 3, Lend);
       row<0>(l + 4, Lend);
-      if (ckpt_every > 0 && (l + 4) % ckpt_every == 0 && l + 4 + 5 < L) // checkpoint j exists iff j * B < L - 5
-        save_ring(ckpt_out + (size_t)((l + 4) / ckpt_every - 1) * (size_t)dcp_ckpt_floats(tabKp, W));
+      if (dcp_ckpt_after(L, ckpt_every, l + 4))
+        save_ring(ckpt_out + (size_t)dcp_ckpt_slot((l + 4) / ckpt_every) * (size_t)ckpt_floats(tabKp));
     }
     if (l <= Lend) row<1>(l++, Lend);
     if (l <= Lend) row<2>(l++, Lend);
@@ -646,6 +647,7 @@ template <int Q, int W, bool STORE = false> struct StripWave
   float const *__restrict__ ckpt_in = nullptr;
   int ckpt_every = 0;
   int row_base = 0;
+  static DCP_FN long long ckpt_floats(int Kp) { return dcp_strip_ckpt_floats(Kp, W); } // from one checkpoint to the next
 
   enum { KS = 64 * Q * W };
 
@@ -925,8 +927,8 @@ template <int Q, int W, bool STORE = false> struct StripWave
       row<3>(l + 2);
       row<4>(l + 3);
       row<0>(l + 4);
-      if (ckpt_every > 0 && (l + 4) % ckpt_every == 0 && l + 4 + 5 < L) // checkpoint j exists iff j * B < L - 5
-        save_ring(ckpt_out + (size_t)((l + 4) / ckpt_every - 1) * (size_t)dcp_strip_ckpt_floats(Kp, W));
+      if (dcp_ckpt_after(L, ckpt_every, l + 4))
+        save_ring(ckpt_out + (size_t)dcp_ckpt_slot((l + 4) / ckpt_every) * (size_t)ckpt_floats(Kp));
     }
     if (l <= Lend) row<1>(l++);
     if (l <= Lend) row<2>(l++);
@@ -943,6 +945,16 @@ template <int Q, int W, bool STORE = false> struct StripWave
     store_f32_lane0(out + 1, g.lane, T);
   }
 };
+
+// A block of the path pass (dcp_types.h) for a CostWave or StripWave that stores its rows: `table` is the block's own
+// table, `ckpts` the window's checkpoints (not read for block 0).  Before init(); run() then goes to blk.last.
+template <class Wave> DCP_FN void dcp_bind_block(Wave &w, float *table, float const *ckpts, DcpBlock const &blk, int Kp)
+{
+  w.tab_sp = table;
+  w.tab_cells = table + (size_t)blk.slots * DCP_SP_STRIDE;
+  w.row_base = blk.row_base;
+  w.ckpt_in = blk.ckpt >= 0 ? ckpts + (size_t)blk.ckpt * (size_t)Wave::ckpt_floats(Kp) : nullptr;
+}
 
 // =============================================================================
 // Back-pointers.  Pointers depend on the ORDER of the reference's strict-<

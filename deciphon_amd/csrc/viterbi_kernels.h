@@ -52,26 +52,27 @@ hipError_t dcp_launch_unzip(DcpLaunch const &a, uint32_t *steps, int64_t const *
 // traceback of every problem of a.problems (all classes) into steps / nsteps (as dcp_launch_unzip)
 // (in blocks, dcp_types.h: B rows between checkpoints, 0 = whole windows; ckpt_addr[out] = the window's checkpoints)
 hipError_t dcp_launch_cost_ckpt(int cls, DcpLaunch const &a, int64_t const *ckpt_addr, int B);
-// G = 0: block `block` of every window.  G > 0: launch `it` of the groups of G blocks -- block nb - 1 - (it * G + g) of
-// every window, g = 0 .. G - 1, into table g of the window's G block tables (dcp_block_table_floats apart), one
-// workgroup per (window, g); the traceback then walks those blocks, the highest first
-hipError_t dcp_launch_cost_store(int cls, DcpLaunch const &a, int64_t const *ckpt_addr, int B, int block, int G = 0, int it = 0);
+// Launch `it` = 0, 1, .. of the groups of G >= 1 blocks (not the strip class): block dcp_group_block(L, B, G, it, g) of
+// every window that has one, g = 0 .. G - 1, into table g of the window's G block tables (dcp_block_table_floats
+// apart), one workgroup per (window, g); the traceback then walks those blocks, the highest first.  (B = 0, G = 1,
+// it = 0: every window whole.)
+hipError_t dcp_launch_cost_store(int cls, DcpLaunch const &a, int64_t const *ckpt_addr, int B, int G, int it);
 // (ckpt_addr != NULL, strip class: a window with ckpt_addr[out] == 0 keeps its whole table -- one block, B = 0 -- whatever B)
 hipError_t dcp_launch_traceback(DcpLaunch const &a, uint32_t *steps, int64_t const *step_off, int32_t *nsteps,
-                                DcpTraceState *states, int B, int block, int G = 0, int it = 0,
-                                int64_t const *ckpt_addr = nullptr);
-// the strip class in blocks, B > 0 per window: ckpt_addr[out] != 0 = the window's checkpoints (dcp_strip_ckpt_floats
-// each), its G block tables at DcpProblem::trellis; 0 = the window keeps its whole table there and is one block.
-// _ckpt: the checkpoints of the former.  _store: launch `it` of the groups of G blocks of every window (as
-// dcp_launch_cost_store with G > 0; a.arena is not used), to be followed by dcp_launch_traceback(.., B, 0, G, it, ckpt_addr)
+                                DcpTraceState *states, int B, int G, int it, int64_t const *ckpt_addr = nullptr);
+// the strip class, per window: ckpt_addr[out] != 0 = the window's checkpoints (dcp_strip_ckpt_floats each), every B > 0
+// rows, its G block tables at DcpProblem::trellis; 0 = the window keeps its whole table there and is one block, taken
+// in launch 0.  _ckpt: the checkpoints of the former (not needed when there is none).  _store: launch `it` of the groups
+// of G blocks of every window (as dcp_launch_cost_store; a.arena is not used), to be followed by
+// dcp_launch_traceback(.., B, G, it, ckpt_addr) or dcp_launch_replay
 hipError_t dcp_launch_strip_ckpt(DcpLaunch const &a, int64_t const *ckpt_addr, int B);
 hipError_t dcp_launch_strip_store(DcpLaunch const &a, int64_t const *ckpt_addr, int B, int G, int it);
 // the same for every window of a.problems (one class, not the strip class) in ONE launch: a workgroup takes its window
 // through the checkpoints, then block by block through rows + traceback (DcpProblem::trellis = the table's address)
 hipError_t dcp_launch_path_blocks(int cls, DcpLaunch const &a, int64_t const *ckpt_addr, int B, uint32_t *steps,
                                   int64_t const *step_off, int32_t *nsteps, DcpTraceState *states);
-// strip class: the trellis replayed row by row (row_replay.h) from the tables dcp_launch_cost_store (whole) or
-// dcp_launch_strip_store (launch `it` of the groups of G blocks) has just written at DcpProblem::trellis of a.problems.
+// strip class: the trellis replayed row by row (row_replay.h) from the tables dcp_launch_strip_store (launch `it` of the
+// groups of G blocks) has just written at DcpProblem::trellis of a.problems.
 // aux[4][a.nprob], indexed by DcpProblem::out: the window's trellis (device address), its scratch (3 K floats per row:
 // L + 1 rows for a whole table, dcp_replay_block_rows(B) per block table), its checkpoints (0: whole table, as for
 // dcp_launch_traceback) and the slot of a.out its score goes to.  A block serves the rows of the traceback's partition.

@@ -99,14 +99,11 @@ __global__ __launch_bounds__(64 * W, (Q >= 8 ? 2 : 1)) void dcp_cost_ckpt_kernel
   w.run(pb.L, out + 2 * (size_t)pb.out);
 }
 
-// Then, block by block from the last to the first: the rows of block `block` of every window that has one,
-// recomputed from its checkpoint into the window's table -- float specials[slots][8] followed by float
-// cells[slots][3][Kp], slots = rows of a block + 1, row l at slot l - block * B.  B = 0: the whole window is one
-// block and the table holds all its rows (what the trellis replay of the strip class reads).
-// G > 0: G blocks of every window side by side, one workgroup each -- the blocks of a window are independent once its
-// checkpoints exist, and a lone wavefront per window leaves the GPU empty and waits out every row's latency by itself
-// (profiles/r03_scan_pipeline.txt).  Workgroup b takes window b / G and, in launch `it`, its block
-// nb - 1 - (it * G + b % G) (the last blocks first), into table b % G of the window's G tables.
+// Then the blocks (DcpBlock, dcp_types.h) from the last to the first, G of every window side by side, one workgroup
+// each: every block of a window that has one in launch `it`, recomputed from its checkpoint into one of the window's G
+// tables -- the blocks of a window are independent once its checkpoints exist, and a lone wavefront per window leaves
+// the GPU empty and waits out every row's latency by itself (profiles/r03_scan_pipeline.txt).  Workgroup b takes window
+// b / G and table b % G.  B = 0: the whole window is one block and its table holds all its rows.
 template <int Q, int W>
 __global__ __launch_bounds__(64 * W, (Q >= 8 ? 2 : 1)) void dcp_cost_store_kernel(float const *__restrict__ pool,
                                                             DcpProfileDev const *__restrict__ profiles,
@@ -114,61 +111,42 @@ __global__ __launch_bounds__(64 * W, (Q >= 8 ? 2 : 1)) void dcp_cost_store_kerne
                                                             DcpCodeRow const *__restrict__ code_rows,
                                                             float const *__restrict__ xt_table,
                                                             unsigned char *__restrict__ arena,
-                                                            int64_t const *__restrict__ ckpt_addr, int B, int block,
-                                                            int G, int it, float *__restrict__ out, int nprob)
+                                                            int64_t const *__restrict__ ckpt_addr, int B, int G, int it,
+                                                            float *__restrict__ out, int nprob)
 {
-  int p, sub = 0;
-  if (G > 0)
-  {
-    if ((int)blockIdx.x >= nprob * G) return;
-    int const b = dcp_xcd_remap_any((int)blockIdx.x, nprob * G); // (window, block) pairs in eighths: whole windows, mostly
-    p = b / G;
-    sub = b % G;
-  }
-  else
-  {
-    if ((int)blockIdx.x >= nprob) return;
-    p = dcp_xcd_remap_any((int)blockIdx.x, nprob);
-  }
-  DcpProblem const pb = problems[p];
-  if (G > 0) block = dcp_num_blocks(pb.L, B) - 1 - (it * G + sub);
-  if (block < 0 || block >= dcp_num_blocks(pb.L, B)) return;
+  if ((int)blockIdx.x >= nprob * G) return;
+  int const b = dcp_xcd_remap_any((int)blockIdx.x, nprob * G); // (window, block) pairs in eighths: whole windows, mostly
+  int const sub = b % G;
+  DcpProblem const pb = problems[b / G];
+  int const block = dcp_group_block(pb.L, B, G, it, sub);
+  if (block < 0) return;
   DcpProfileDev const pf = profiles[pb.profile];
+  DcpBlock const blk = dcp_block(pb.L, B, block);
   CostWave<Q, W, true> w;
-  int const slots = dcp_block_slots(pb.L, B);
   // integer arithmetic: the engine passes arena = 0 and absolute table addresses in pb.trellis
-  w.tab_sp = dcp_global<float>((uintptr_t)arena + (uintptr_t)pb.trellis) + (size_t)sub * dcp_block_table_floats(pb.L, pf.Kp, B);
-  w.tab_cells = w.tab_sp + (size_t)slots * DCP_SP_STRIDE;
-  w.row_base = block * B;
-  if (block > 0)
-    w.ckpt_in = dcp_global<float const>((uintptr_t)ckpt_addr[pb.out]) + (size_t)(block - 1) * (size_t)dcp_ckpt_floats(pf.Kp, W);
+  dcp_bind_block(w, dcp_global<float>((uintptr_t)arena + (uintptr_t)pb.trellis) + dcp_group_table(pb.L, pf.Kp, B, sub),
+                 dcp_global<float const>((uintptr_t)ckpt_addr[pb.out]), blk, pf.Kp);
   w.init(pool, pf, code_rows + pb.code_row, xt_table + (size_t)pb.xt_row * DCP_XT_STRIDE);
-  int const last = B > 0 ? (block + 1) * B + 5 : pb.L;
-  w.run(pb.L, out + 2 * (size_t)pb.out, last < pb.L ? last : pb.L);
+  w.run(pb.L, out + 2 * (size_t)pb.out, blk.last);
 }
 
 // Profiles beyond 4096 positions: one workgroup walks each row strip by strip (StripWave).
-template <int Q, int W, bool STORE>
+template <int Q, int W>
 __global__ __launch_bounds__(64 * W) void dcp_strip_kernel(float const *__restrict__ pool,
                                                        DcpProfileDev const *__restrict__ profiles,
                                                        DcpProblem const *__restrict__ problems,
                                                        DcpCodeRow const *__restrict__ code_rows,
                                                        float const *__restrict__ xt_table,
-                                                       unsigned char *__restrict__ arena, float *__restrict__ ring,
-                                                       float *__restrict__ out, int nprob)
+                                                       unsigned char *__restrict__ /* arena: no table */,
+                                                       float *__restrict__ ring, float *__restrict__ out, int nprob)
 {
   // the grid is at most DCP_RING_SLOTS workgroups, each owning one ring and taking problems in turn
   for (int p = (int)blockIdx.x; p < nprob; p += (int)gridDim.x)
   {
     DcpProblem const pb = problems[p];
     DcpProfileDev const pf = profiles[pb.profile];
-    StripWave<Q, W, STORE> w;
+    StripWave<Q, W> w;
     w.ring = ring + (size_t)blockIdx.x * DCP_RING_FLOATS;
-    if (STORE)
-    {
-      w.tab_sp = dcp_global<float>((uintptr_t)arena + (uintptr_t)pb.trellis);
-      w.tab_cells = w.tab_sp + (size_t)(pb.L + 1) * DCP_SP_STRIDE;
-    }
     w.init(pool, pf, code_rows + pb.code_row, xt_table + (size_t)pb.xt_row * DCP_XT_STRIDE);
     w.run(pb.L, out + 2 * (size_t)pb.out);
     __syncthreads(); // the next problem re-initialises the LDS records
@@ -203,8 +181,8 @@ __global__ __launch_bounds__(64 * W) void dcp_strip_ckpt_kernel(float const *__r
   }
 }
 
-// ... then launch `it` of the groups of G blocks, as dcp_cost_store_kernel: item i = (window i / G, table i % G), block
-// nb - 1 - (it * G + i % G) of that window.  A workgroup owns one ring and takes items in turn.
+// ... then launch `it` of the groups of G blocks, as dcp_cost_store_kernel: item i = (window i / G, table i % G).  A
+// workgroup owns one ring and takes items in turn.
 template <int Q, int W>
 __global__ __launch_bounds__(64 * W) void dcp_strip_store_kernel(float const *__restrict__ pool,
                                                              DcpProfileDev const *__restrict__ profiles,
@@ -220,20 +198,16 @@ __global__ __launch_bounds__(64 * W) void dcp_strip_store_kernel(float const *__
     DcpProblem const pb = problems[i / G];
     int64_t const ck = ckpt_addr[pb.out];
     int const Bw = ck != 0 ? B : 0;
-    int const nb = dcp_num_blocks(pb.L, Bw);
-    int const block = nb - 1 - (it * G + sub);
+    int const block = dcp_group_block(pb.L, Bw, G, it, sub);
     if (block < 0) continue;
     DcpProfileDev const pf = profiles[pb.profile];
+    DcpBlock const blk = dcp_block(pb.L, Bw, block);
     StripWave<Q, W, true> w;
     w.ring = ring + (size_t)blockIdx.x * DCP_RING_FLOATS;
-    w.tab_sp = dcp_global<float>((uintptr_t)pb.trellis) + (size_t)sub * dcp_block_table_floats(pb.L, pf.Kp, Bw);
-    w.tab_cells = w.tab_sp + (size_t)dcp_block_slots(pb.L, Bw) * DCP_SP_STRIDE;
-    w.row_base = block * Bw;
-    if (block > 0)
-      w.ckpt_in = dcp_global<float const>((uintptr_t)ck) + (size_t)(block - 1) * (size_t)dcp_strip_ckpt_floats(pf.Kp, W);
+    dcp_bind_block(w, dcp_global<float>((uintptr_t)pb.trellis) + dcp_group_table(pb.L, pf.Kp, Bw, sub),
+                   dcp_global<float const>((uintptr_t)ck), blk, pf.Kp);
     w.init(pool, pf, code_rows + pb.code_row, xt_table + (size_t)pb.xt_row * DCP_XT_STRIDE);
-    int const last = Bw > 0 ? (block + 1) * Bw + 5 : pb.L;
-    w.run(pb.L, out + 2 * (size_t)pb.out, last < pb.L ? last : pb.L);
+    w.run(pb.L, out + 2 * (size_t)pb.out, blk.last);
     __syncthreads();
   }
 }
@@ -246,37 +220,14 @@ __device__ void dcp_replay_one(float const *__restrict__ pool, DcpProfileDev con
 {
   int const r = (int)(blockIdx.x * 64u + threadIdx.x);
   int const Bw = aux[2 * (size_t)naux + pb.out] != 0 ? B : 0; // no checkpoints: the whole table, one block
-  int sub = 0, block = 0, l = r;
-  size_t acc_row = (size_t)r;
-  if (Bw > 0)
-  {
-    int const per = dcp_replay_block_rows(Bw);
-    sub = r / per;
-    if (sub >= G) return;
-    block = dcp_num_blocks(pb.L, Bw) - 1 - (it * G + sub);
-    if (block < 0) return;
-    l = (block > 0 ? block * Bw + 6 : 0) + r % per;
-    if (l > (block + 1) * Bw + 5) return;
-  }
-  else if (it > 0)
-    return;
-  if (l > pb.L) return;
   DcpProfileDev const pf = profiles[pb.profile];
+  // trellis of a problem: uint32 xnodes[L+1] then uint16 nodes[(L+1)*K]
   uint32_t *xnodes = dcp_global<uint32_t>((uintptr_t)aux[pb.out]);
-  uint16_t *nodes = reinterpret_cast<uint16_t *>(xnodes + (pb.L + 1)) + (size_t)l * pf.K;
-  if (l == 0) // before(): every field 0 (c-core/viterbi.c:602-629)
-  {
-    xnodes[0] = 0;
-    for (int k = 0; k < pf.K; ++k) nodes[k] = 0;
-    return;
-  }
   DcpTraceIn in = dcp_trace_in(pool, pf, code_rows + pb.code_row, xt_table + (size_t)pb.xt_row * DCP_XT_STRIDE, pb.L);
-  in.sp = dcp_global<float const>((uintptr_t)pb.trellis) + (size_t)sub * dcp_block_table_floats(pb.L, pf.Kp, Bw);
-  in.cells = in.sp + (size_t)dcp_block_slots(pb.L, Bw) * DCP_SP_STRIDE;
-  in.row_base = block * Bw;
-  float *acc = dcp_global<float>((uintptr_t)aux[(size_t)naux + pb.out]) + acc_row * 3 * pf.K;
-  dcp_replay_row(in, l, acc, xnodes + l, nodes);
-  if (l == pb.L) // T of the last row: the score viterbi_path returns (c-core/viterbi.c:585-586,599)
+  int const l = dcp_replay_thread(in, dcp_global<float const>((uintptr_t)pb.trellis), Bw, G, it, r,
+                                  dcp_global<float>((uintptr_t)aux[(size_t)naux + pb.out]), xnodes,
+                                  reinterpret_cast<uint16_t *>(xnodes + (pb.L + 1)));
+  if (l > 0 && l == pb.L) // T of the last row: the score viterbi_path returns (c-core/viterbi.c:585-586,599)
   {
     float const *last = in.sp + (size_t)(l - in.row_base) * DCP_SP_STRIDE;
     out[aux[3 * (size_t)naux + pb.out]] = __builtin_fminf(last[3] + in.xt[DCP_ET], last[4] + in.xt[DCP_CT]);
@@ -321,31 +272,21 @@ __global__ __launch_bounds__(64) void dcp_traceback_kernel(
     float const *__restrict__ pool, DcpProfileDev const *__restrict__ profiles, DcpProblem const *__restrict__ problems,
     DcpCodeRow const *__restrict__ code_rows, float const *__restrict__ xt_table,
     unsigned char const *__restrict__ arena, uint32_t *__restrict__ steps, int64_t const *__restrict__ step_off,
-    int32_t *__restrict__ nsteps, DcpTraceState *__restrict__ states, int B, int block, int G, int it,
+    int32_t *__restrict__ nsteps, DcpTraceState *__restrict__ states, int B, int G, int it,
     int64_t const *__restrict__ ckpt_addr, int nprob)
 {
   int const p = (int)blockIdx.x;
   if (p >= nprob) return;
   DcpProblem const pb = problems[p];
   if (ckpt_addr && ckpt_addr[pb.out] == 0) B = 0; // strip class: this window keeps its whole table (dcp_strip_store_kernel)
-  int const nb = dcp_num_blocks(pb.L, B);
   DcpTraceState *st = states + pb.out;
   if (st->status != 0) return; // finished, or given up, in a later block
   DcpProfileDev const pf = profiles[pb.profile];
   DcpTraceIn in = dcp_trace_in(pool, pf, code_rows + pb.code_row, xt_table + (size_t)pb.xt_row * DCP_XT_STRIDE, pb.L);
-  float const *tables = dcp_global<float const>((uintptr_t)arena + (uintptr_t)pb.trellis);
-  // G > 0: through the (up to) G blocks launch `it` of dcp_cost_store_kernel has just written, the highest first
-  for (int sub = 0; sub < (G > 0 ? G : 1); ++sub)
-  {
-    int const b = G > 0 ? nb - 1 - (it * G + sub) : block;
-    if (b < 0 || b >= nb) return;
-    in.sp = tables + (size_t)sub * dcp_block_table_floats(pb.L, pf.Kp, B);
-    in.cells = in.sp + (size_t)dcp_block_slots(pb.L, B) * DCP_SP_STRIDE;
-    in.row_base = b * B;
-    in.lo = b > 0 ? b * B + 5 : -1;
-    int const r = dcp_traceback<DcpLanesWave>(in, steps + step_off[pb.out], step_off[pb.out + 1] - step_off[pb.out], st);
-    if (dcp_trace_end(r, st, nsteps + pb.out)) return;
-  }
+  // through the (up to) G blocks that launch `it` of the store kernel has just written, the highest first
+  int const r = dcp_traceback_group<DcpLanesWave>(in, dcp_global<float const>((uintptr_t)arena + (uintptr_t)pb.trellis), B, G, it,
+                                                  steps + step_off[pb.out], step_off[pb.out + 1] - step_off[pb.out], st);
+  dcp_trace_end(r, st, nsteps + pb.out);
 }
 
 // The fast path pass of ONE window from start to end in one workgroup (what dcp_cost_ckpt_kernel, then per block
@@ -380,21 +321,17 @@ __global__ __launch_bounds__(64 * W, (Q >= 8 ? 2 : 1)) void dcp_path_blocks_kern
     wave_priority<3>();
     w.run(pb.L, out + 2 * (size_t)pb.out);
   }
-  int const slots = dcp_block_slots(pb.L, B);
-  float *tab_sp = dcp_global<float>((uintptr_t)pb.trellis);
+  float *table = dcp_global<float>((uintptr_t)pb.trellis);
   for (int block = nb - 1; block >= 0; --block)
   {
+    DcpBlock const blk = dcp_block(pb.L, B, block);
     __syncthreads(); // the checkpoints are written; the walk through the block above has left the table
     {
       CostWave<Q, W, true> w;
-      w.tab_sp = tab_sp;
-      w.tab_cells = tab_sp + (size_t)slots * DCP_SP_STRIDE;
-      w.row_base = block * B;
-      if (block > 0) w.ckpt_in = ckpt + (size_t)(block - 1) * (size_t)dcp_ckpt_floats(pf.Kp, W);
+      dcp_bind_block(w, table, ckpt, blk, pf.Kp);
       w.init(pool, pf, codes, xt);
       wave_priority<3>();
-      int const last = B > 0 ? (block + 1) * B + 5 : pb.L;
-      w.run(pb.L, out + 2 * (size_t)pb.out, last < pb.L ? last : pb.L);
+      w.run(pb.L, out + 2 * (size_t)pb.out, blk.last);
     }
     __threadfence_block();
     __syncthreads();
@@ -402,10 +339,7 @@ __global__ __launch_bounds__(64 * W, (Q >= 8 ? 2 : 1)) void dcp_path_blocks_kern
     {
       DcpTraceState *st = states + pb.out;
       DcpTraceIn in = dcp_trace_in(pool, pf, codes, xt, pb.L);
-      in.sp = tab_sp;
-      in.cells = tab_sp + (size_t)slots * DCP_SP_STRIDE;
-      in.row_base = block * B;
-      in.lo = block > 0 ? block * B + 5 : -1;
+      dcp_trace_bind(in, table, blk);
       int const r = dcp_traceback<DcpLanesWave>(in, steps + step_off[pb.out], step_off[pb.out + 1] - step_off[pb.out], st);
       bool const over = dcp_trace_end(r, st, nsteps + pb.out);
       if (threadIdx.x == 0) walk_over = over;
@@ -710,11 +644,11 @@ template <class F> static hipError_t with_class(int cls, F f)
 static_assert(0 DCP_CLASS_TABLE(X) == DCP_STRIP_CLASS, "one row of DCP_CLASS_TABLE per class below the strip class");
 #undef X
 
-template <bool STORE> static hipError_t launch_strip(DcpLaunch const &a)
+static hipError_t launch_strip(DcpLaunch const &a)
 {
   if (!a.ring) return hipErrorInvalidValue;
   unsigned const grid = (unsigned)(a.nprob < DCP_RING_SLOTS ? a.nprob : DCP_RING_SLOTS);
-  hipLaunchKernelGGL((dcp_strip_kernel<4, 8, STORE>), dim3(grid), dim3(512), 0, a.stream, a.pool,
+  hipLaunchKernelGGL((dcp_strip_kernel<4, 8>), dim3(grid), dim3(512), 0, a.stream, a.pool,
                      a.profiles, a.problems, a.code_rows, a.xt_table, a.arena, a.ring, a.out, a.nprob);
   return hipGetLastError();
 }
@@ -746,7 +680,7 @@ void dcp_class_shape(int cls, int *Q, int *W)
 hipError_t dcp_launch_cost(int cls, DcpLaunch const &a)
 {
   if (a.nprob <= 0) return hipSuccess;
-  if (cls == DCP_STRIP_CLASS) return launch_strip<false>(a);
+  if (cls == DCP_STRIP_CLASS) return launch_strip(a);
   return with_class(cls, [&](auto cost, auto) { return launch_cost_qw<decltype(cost)::Q, decltype(cost)::W>(a); });
 }
 
@@ -771,16 +705,15 @@ hipError_t dcp_launch_cost_narrow(int cls, DcpLaunch const &a)
   }
 }
 
-hipError_t dcp_launch_cost_store(int cls, DcpLaunch const &a, int64_t const *ckpt_addr, int B, int block, int G, int it)
+hipError_t dcp_launch_cost_store(int cls, DcpLaunch const &a, int64_t const *ckpt_addr, int B, int G, int it)
 {
   if (a.nprob <= 0) return hipSuccess;
-  // whole tables here; in blocks: dcp_launch_strip_store
-  if (cls == DCP_STRIP_CLASS) return B == 0 && block == 0 && G == 0 ? launch_strip<true>(a) : hipErrorInvalidValue;
-  return with_class(cls, [&](auto cost, auto) {
+  if (!ckpt_addr || B < 0 || B % 5 || G < 1 || it < 0) return hipErrorInvalidValue;
+  return with_class(cls, [&](auto cost, auto) { // (the strip class: dcp_launch_strip_store)
     using C = decltype(cost);
-    hipLaunchKernelGGL((dcp_cost_store_kernel<C::Q, C::W>), dim3((unsigned)a.nprob * (unsigned)(G > 0 ? G : 1)), dim3(64 * C::W),
-                       0, a.stream, a.pool, a.profiles, a.problems, a.code_rows, a.xt_table, a.arena, ckpt_addr, B, block, G,
-                       it, a.out, a.nprob);
+    hipLaunchKernelGGL((dcp_cost_store_kernel<C::Q, C::W>), dim3((unsigned)a.nprob * (unsigned)G), dim3(64 * C::W), 0,
+                       a.stream, a.pool, a.profiles, a.problems, a.code_rows, a.xt_table, a.arena, ckpt_addr, B, G, it, a.out,
+                       a.nprob);
     return hipGetLastError();
   });
 }
@@ -822,7 +755,7 @@ hipError_t dcp_launch_strip_ckpt(DcpLaunch const &a, int64_t const *ckpt_addr, i
 hipError_t dcp_launch_strip_store(DcpLaunch const &a, int64_t const *ckpt_addr, int B, int G, int it)
 {
   if (a.nprob <= 0) return hipSuccess;
-  if (!a.ring || !ckpt_addr || B <= 0 || B % 5 || G < 1 || it < 0) return hipErrorInvalidValue;
+  if (!a.ring || !ckpt_addr || B < 0 || B % 5 || G < 1 || it < 0) return hipErrorInvalidValue;
   long long const items = (long long)a.nprob * G;
   unsigned const grid = (unsigned)(items < DCP_RING_SLOTS ? items : DCP_RING_SLOTS);
   hipLaunchKernelGGL((dcp_strip_store_kernel<4, 8>), dim3(grid), dim3(512), 0, a.stream, a.pool, a.profiles, a.problems,
@@ -831,11 +764,12 @@ hipError_t dcp_launch_strip_store(DcpLaunch const &a, int64_t const *ckpt_addr, 
 }
 
 hipError_t dcp_launch_traceback(DcpLaunch const &a, uint32_t *steps, int64_t const *step_off, int32_t *nsteps,
-                                DcpTraceState *states, int B, int block, int G, int it, int64_t const *ckpt_addr)
+                                DcpTraceState *states, int B, int G, int it, int64_t const *ckpt_addr)
 {
   if (a.nprob <= 0) return hipSuccess;
+  if (G < 1 || it < 0) return hipErrorInvalidValue;
   hipLaunchKernelGGL(dcp_traceback_kernel, dim3((unsigned)a.nprob), dim3(64), 0, a.stream, a.pool, a.profiles, a.problems,
-                     a.code_rows, a.xt_table, a.arena, steps, step_off, nsteps, states, B, block, G, it, ckpt_addr, a.nprob);
+                     a.code_rows, a.xt_table, a.arena, steps, step_off, nsteps, states, B, G, it, ckpt_addr, a.nprob);
   return hipGetLastError();
 }
 

@@ -2,7 +2,7 @@
 # its own beside libdcp_emul.so (make -f strip_blocks.mk).
 HERE := $(dir $(abspath $(lastword $(MAKEFILE_LIST))))
 CSRC := $(HERE)../../deciphon_amd/csrc
-HDRS := $(HERE)lane_ops_emul.h $(CSRC)/viterbi_body.h $(CSRC)/traceback.h $(CSRC)/row_replay.h $(CSRC)/dcp_types.h $(CSRC)/dcp_states.h
+HDRS := $(HERE)lane_ops_emul.h $(HERE)block_walk.h $(CSRC)/viterbi_body.h $(CSRC)/traceback.h $(CSRC)/row_replay.h $(CSRC)/dcp_types.h $(CSRC)/dcp_states.h
 CXXFLAGS := -std=c++17 -O2 -fPIC -ffp-contract=off -Wall -Wno-unknown-pragmas -Wno-maybe-uninitialized
 
 all: $(HERE)libdcp_emul_strip_blocks.so

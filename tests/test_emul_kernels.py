@@ -363,10 +363,12 @@ def test_fast_path_pass_in_blocks(em, orc):
     """The DP table a block at a time (dcp_types.h): checkpoints of the folded ring every B rows, every block
     recomputed from its checkpoint into a table of B + 6 rows (never-written slots hold NaN), the traceback
     resumed from block to block -- the same steps as trellis_unzip on the oracle's trellis, for windows of one
-    to a dozen blocks, block boundaries in and beside insert, delete and special-state runs."""
+    to a dozen blocks, block boundaries in and beside insert, delete and special-state runs.  The blocks are taken as
+    the engine takes them: G at a time, side by side in G tables."""
     em.emul_path_blocks.restype = C.c_int
     rng = np.random.default_rng(41)
     multi = ties = 0
+    seen = set()
     for it in range(160):
         K = int(rng.choice([3, 17, 64, 65, 100, 173, 241, 256, 300, 400, 600, 1000]))
         prof = synth_profile(rng, K, None, [0, 0.05][it % 2])
@@ -374,6 +376,8 @@ def test_fast_path_pass_in_blocks(em, orc):
             prof.trans[7, 1:] = np.float32(0.01)
             prof.trans[3, 1:] = np.float32(0.02)
         B = [5, 10, 15, 20, 0][it % 5]
+        G = [1, 2, 3][it % 3]
+        seen.add((B, G))
         L = int(rng.integers(1, 70))
         seq = random_seq(rng, L)
         xt = orc.xtrans(max(L // 3, 1), it % 2, (it // 2) % 2)
@@ -384,9 +388,9 @@ def test_fast_path_pass_in_blocks(em, orc):
         cap = 2 * L + 2 * K + 64
         buf = np.zeros(cap, np.uint32)
         score = C.c_float(0)
-        n = em.emul_path_blocks(_vp(pool), C.byref(pd), _vp(rows), L, _vp(xt16), B, _vp(buf), C.c_long(cap), C.byref(score))
+        n = em.emul_path_blocks(_vp(pool), C.byref(pd), _vp(rows), L, _vp(xt16), B, G, _vp(buf), C.c_long(cap), C.byref(score))
         s_o, xo, no = orc.path(prof, xt, seq)
-        assert bits(score.value) == bits(s_o), (it, K, L, B)
+        assert bits(score.value) == bits(s_o), (it, K, L, B, G)
         if not np.isfinite(s_o):
             continue
         if n == -2:  # an exact tie the values cannot resolve (the literal pass takes over): rare with these tables
@@ -398,3 +402,4 @@ def test_fast_path_pass_in_blocks(em, orc):
         assert np.array_equal(w & 0xFFFF, ids.astype(np.uint32)) and np.array_equal(w >> 16, sizes.astype(np.uint32)), (it, K, L, B)
         multi += B > 0 and L > B + 5
     assert multi > 60 and ties < 8
+    assert seen == {(B, G) for B in (5, 10, 15, 20, 0) for G in (1, 2, 3)}

@@ -71,8 +71,8 @@ def test_short_windows_stored_rows_and_blocks(em, orc):
                 cap = 2 * L + 2 * K + 64
                 buf = np.zeros(cap, np.uint32)
                 score = C.c_float(0)
-                n = em.emul_path_blocks(_vp(pool), C.byref(pd), _vp(code_rows(seq)), L, _vp(xt16), B, _vp(buf), C.c_long(cap),
-                                        C.byref(score))
+                n = em.emul_path_blocks(_vp(pool), C.byref(pd), _vp(code_rows(seq)), L, _vp(xt16), B, 1 + B // 5, _vp(buf),
+                                        C.c_long(cap), C.byref(score))
                 assert bits(score.value) == bits(s_o), (K, L, B)
                 if n == -2 or not np.isfinite(s_o):  # an exact tie the values cannot resolve: the literal pass takes it
                     continue
@@ -141,7 +141,7 @@ def test_junk_at_position_zero_single_wave_shapes(em, orc):
             cap = 2 * L + 2 * K + 64
             buf = np.zeros(cap, np.uint32)
             score = C.c_float(0)
-            n = em.emul_path_blocks(_vp(pool), C.byref(pd), _vp(code_rows(seq)), L, _vp(xt16), 10, _vp(buf), C.c_long(cap),
+            n = em.emul_path_blocks(_vp(pool), C.byref(pd), _vp(code_rows(seq)), L, _vp(xt16), 10, 2, _vp(buf), C.c_long(cap),
                                     C.byref(score))
             walks.append((bits(score.value), n, buf[cap - n:].tobytes() if n > 0 else b""))
             if K <= 256:  # the literal pass: every trellis word

@@ -14,6 +14,7 @@ from dcp_testlib import ROOT, bits, code_rows, pack_profile, random_seq, synth_p
 
 SHAPES = [(1, 1, 3), (2, 1, 2), (1, 2, 3), (2, 2, 2), (4, 2, 2), (1, 4, 2), (1, 1, 5), (2, 2, 3)]  # (Q, W, strips)
 BLOCKS = [5, 10, 15, 20, 0]
+GROUPS = [1, 2, 3]
 
 
 @pytest.fixture(scope="module")
@@ -44,6 +45,7 @@ def _case(rng, orc, it, quant):
         prof.trans[7, 1:] = np.float32(0.01)
         prof.trans[3, 1:] = np.float32(0.02)
     B = BLOCKS[it % len(BLOCKS)]
+    G = GROUPS[it % len(GROUPS)]  # blocks side by side, as the engine takes them
     L = int(rng.integers(20, 71))
     seq = random_seq(rng, L)
     mode = (it // len(SHAPES)) % 4  # all four (multi_hits, hmmer3_compat) modes
@@ -53,7 +55,7 @@ def _case(rng, orc, it, quant):
     pool, pd = pack_profile(prof, Q, W, S)
     xt16 = np.zeros(16, np.float32)
     xt16[:13] = xt
-    return prof, seq, xt, pool, pd, code_rows(seq), xt16, B, L, K, ((Q, W, S), mode, it % 4 == 0, B)
+    return prof, seq, xt, pool, pd, code_rows(seq), xt16, B, G, L, K, ((Q, W, S), mode, it % 4 == 0, B)
 
 
 def test_strip_path_in_blocks(emsb, orc):
@@ -62,14 +64,15 @@ def test_strip_path_in_blocks(emsb, orc):
     rng = np.random.default_rng(77)
     N = 128
     multi = ties = 0
-    seen = set()
+    seen, groups = set(), set()
     for it in range(N):
-        prof, seq, xt, pool, pd, rows, xt16, B, L, K, what = _case(rng, orc, it, None)
+        prof, seq, xt, pool, pd, rows, xt16, B, G, L, K, what = _case(rng, orc, it, None)
         seen.add(what)
+        groups.add((B, G))
         cap = 2 * L + 2 * K + 64
         buf = np.zeros(cap, np.uint32)
         score = C.c_float(0)
-        n = emsb.emul_strip_path_blocks(_vp(pool), C.byref(pd), _vp(rows), L, _vp(xt16), B, _vp(buf), C.c_long(cap),
+        n = emsb.emul_strip_path_blocks(_vp(pool), C.byref(pd), _vp(rows), L, _vp(xt16), B, G, _vp(buf), C.c_long(cap),
                                         C.byref(score))
         assert bits(score.value) == bits(orc.cost(prof, xt, seq)), (it, K, L, B)
         if n == -2:
@@ -87,6 +90,7 @@ def test_strip_path_in_blocks(emsb, orc):
     assert {(s, m) for s, m, _, _ in seen} == {(s, m) for s in SHAPES for m in range(4)}
     assert {s for s, _, d, _ in seen if d} == set(SHAPES) and {m for _, m, d, _ in seen if d} == set(range(4))
     assert {(s, b) for s, _, _, b in seen} == {(s, b) for s in SHAPES for b in BLOCKS}
+    assert groups == {(b, g) for b in BLOCKS for g in GROUPS}
 
 
 def test_strip_trellis_replayed_in_blocks(emsb, orc):
@@ -94,13 +98,15 @@ def test_strip_trellis_replayed_in_blocks(emsb, orc):
     block equals the oracle's.  No case is skipped."""
     rng = np.random.default_rng(78)
     multi = 0
+    groups = set()
     for it in range(120):
         quant = [1.0, 4.0][it % 2]
-        prof, seq, xt, pool, pd, rows, xt16, B, L, K, _ = _case(rng, orc, it, quant)
+        prof, seq, xt, pool, pd, rows, xt16, B, G, L, K, _ = _case(rng, orc, it, quant)
+        groups.add((B, G))
         xn = np.full(L + 1, 0xFFFFFFFF, np.uint32)
         nd = np.full((L + 1) * K, 0xFFFF, np.uint16)
         score = C.c_float(0)
-        assert emsb.emul_strip_replay_blocks(_vp(pool), C.byref(pd), _vp(rows), L, _vp(xt16), B, _vp(xn), _vp(nd),
+        assert emsb.emul_strip_replay_blocks(_vp(pool), C.byref(pd), _vp(rows), L, _vp(xt16), B, G, _vp(xn), _vp(nd),
                                              C.byref(score)) == 0
         s_o, xo, no = orc.path(prof, xt, seq)
         assert bits(score.value) == bits(s_o), (it, K, L, B)
@@ -108,3 +114,4 @@ def test_strip_trellis_replayed_in_blocks(emsb, orc):
         assert np.array_equal(nd, no), (it, K, L, B, quant)
         multi += B > 0 and L > B + 5
     assert multi > 60
+    assert groups == {(b, g) for b in BLOCKS for g in GROUPS}
