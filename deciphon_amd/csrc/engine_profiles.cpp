@@ -1,5 +1,6 @@
 // engine_profiles.cpp -- the engine's profiles: add, load, commit, clear, and the cost-order staging.
 #include "engine_internal.h"
+#include "parallel_for.h"
 
 extern "C" {
 
@@ -239,38 +240,28 @@ int dcp_hip_load_dcp(struct dcp_hip *x, char const *path, int first, int count)
       return fail(x, DCP_EFUNCUSE, "staging copy failed");
     }
     float *buf = stage[b];
-    // plain threads, joined per chunk: no runtime is left spinning next to the HIP callbacks
-    std::atomic<int> next_protein{i0}, bad{0};
-    auto work = [&]() {
-      DcpProtein p;
-      for (int i = next_protein.fetch_add(1); i < i1; i = next_protein.fetch_add(1))
+    std::atomic<int> bad{0};
+    // (p: every thread's own copy, reused from protein to protein)
+    dcp_parallel_for((size_t)(i1 - i0), 16, 1, 1, [&, p = DcpProtein()](size_t k) mutable {
+      int const i = i0 + (int)k;
+      int r = db.read_protein(first + i, p);
+      if (r || p.core_size != hps[(size_t)i].K)
       {
-        int r = db.read_protein(first + i, p);
-        if (r || p.core_size != hps[(size_t)i].K)
-        {
-          int expected = 0;
-          bad.compare_exchange_strong(expected, r ? r : DCP_EFDATA);
-          continue;
-        }
-        float *rows = buf + (off[(size_t)i] - off[(size_t)i0]);
-        float *trans = rows + (size_t)DCP_TABLE_SIZE * ((size_t)hps[(size_t)i].Kp + DCP_ROW_HDR);
-        dcp_setup_profile(p.core_size, hps[(size_t)i].Kp, p.trans.data(), p.emission.data(), p.BMk.data(),
-                          p.null_emission.data(), p.bg_emission.data(), trans, rows);
-        if (!delete_costs_ok(trans, p.core_size, hps[(size_t)i].Kp))
-        {
-          int expected = 0;
-          bad.compare_exchange_strong(expected, DCP_EFDATA); // a positive delete log-probability
-        }
-        stage_cost_order(hps[(size_t)i], rows);
+        int expected = 0;
+        bad.compare_exchange_strong(expected, r ? r : DCP_EFDATA);
+        return;
       }
-    };
-    {
-      unsigned nthreads = std::min<unsigned>({std::max(1u, std::thread::hardware_concurrency()), 16u, (unsigned)(i1 - i0)});
-      std::vector<std::thread> pool;
-      for (unsigned t = 1; t < nthreads; ++t) pool.emplace_back(work);
-      work();
-      for (std::thread &t : pool) t.join();
-    }
+      float *rows = buf + (off[(size_t)i] - off[(size_t)i0]);
+      float *trans = rows + (size_t)DCP_TABLE_SIZE * ((size_t)hps[(size_t)i].Kp + DCP_ROW_HDR);
+      dcp_setup_profile(p.core_size, hps[(size_t)i].Kp, p.trans.data(), p.emission.data(), p.BMk.data(),
+                        p.null_emission.data(), p.bg_emission.data(), trans, rows);
+      if (!delete_costs_ok(trans, p.core_size, hps[(size_t)i].Kp))
+      {
+        int expected = 0;
+        bad.compare_exchange_strong(expected, DCP_EFDATA); // a positive delete log-probability
+      }
+      stage_cost_order(hps[(size_t)i], rows);
+    });
     if (bad)
     {
       cleanup();

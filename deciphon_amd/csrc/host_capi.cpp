@@ -1,8 +1,9 @@
-// host_capi.cpp -- C ABI of include/deciphon_host.h over dcp_db / host_logic.
+// host_capi.cpp -- C ABI of include/deciphon_host.h over dcp_db / host_logic / scan_walk.
 #include "../../include/deciphon_host.h"
 #include "dcp_db.h"
 #include "dcp_errors.h"
 #include "host_logic.h"
+#include "scan_walk.h"
 
 #include <string.h>
 #include <string>
@@ -11,6 +12,11 @@
 struct dcp_db
 {
   DcpDbReader reader;
+};
+
+struct dcp_scan_walk
+{
+  DcpScanWalk walk;
 };
 
 extern "C" {
@@ -175,6 +181,68 @@ int dcp_trellis_unzip(int K, int L, uint32_t const *xnodes, uint16_t const *node
   memcpy(seqsizes, sizes.data(), sizes.size() * sizeof(int32_t));
   return 0;
 }
+
+struct dcp_scan_walk *dcp_scan_walk_new(int nprof, int32_t const *core_sizes, int nreads, int32_t const *read_lengths)
+{
+  if (nprof < 0 || nreads < 0 || (nprof && !core_sizes) || (nreads && !read_lengths)) return nullptr;
+  return new dcp_scan_walk{DcpScanWalk(nprof, core_sizes, nreads, read_lengths)};
+}
+
+void dcp_scan_walk_del(struct dcp_scan_walk *x) { delete x; }
+
+int dcp_scan_walk_chunk_windows(struct dcp_scan_walk *x, int32_t const c[4], int64_t windows, struct dcp_hip_window *wins,
+                                int64_t *base)
+{
+  if (!x || !c || windows < 0 || (windows && !wins) || !base) return DCP_EFUNCUSE;
+  return x->walk.chunk_windows(DcpChunk{c[0], c[1], c[2], c[3], windows}, wins, base);
+}
+
+int dcp_scan_walk_chunk_scored(struct dcp_scan_walk *x, int32_t const c[4], int64_t const *base, int nh,
+                               int32_t const *hit_index, float const *lrts)
+{
+  if (!x || !c || !base || nh < 0 || (nh && (!hit_index || !lrts))) return DCP_EFUNCUSE;
+  x->walk.chunk_scored(DcpChunk{c[0], c[1], c[2], c[3], 0}, base, nh, hit_index, lrts);
+  return 0;
+}
+
+int dcp_scan_walk_all_pairs(struct dcp_scan_walk *x)
+{
+  if (!x) return DCP_EFUNCUSE;
+  x->walk.all_pairs();
+  return 0;
+}
+
+int64_t dcp_scan_walk_waiting(struct dcp_scan_walk const *x, int which)
+{
+  return !x ? 0 : (int64_t)(which ? x->walk.path_waiting() : x->walk.cost_waiting());
+}
+
+int64_t dcp_scan_walk_take(struct dcp_scan_walk *x, int which, struct dcp_hip_window const **wins)
+{
+  if (!x || !wins) return 0;
+  std::vector<dcp_hip_window> const &w = which ? x->walk.take_path_batch() : x->walk.take_cost_round();
+  *wins = w.data();
+  return (int64_t)w.size();
+}
+
+int dcp_scan_walk_cost_scored(struct dcp_scan_walk *x, int nh, int32_t const *hit_index, float const *lrts)
+{
+  if (!x || nh < 0 || (nh && (!hit_index || !lrts))) return DCP_EFUNCUSE;
+  x->walk.cost_scored(nh, hit_index, lrts);
+  return 0;
+}
+
+int64_t dcp_scan_walk_path_walked(struct dcp_scan_walk *x, uint8_t const *is_hit, int32_t const *last_hit_pos,
+                                  struct dcp_walk_hit const **hits)
+{
+  if (!x || !is_hit || !last_hit_pos || !hits) return 0;
+  std::vector<dcp_walk_hit> const &h = x->walk.path_walked(is_hit, last_hit_pos);
+  *hits = h.data();
+  return (int64_t)h.size();
+}
+
+int64_t dcp_scan_walk_windows(struct dcp_scan_walk const *x) { return x ? (int64_t)x->walk.windows_walked() : 0; }
+int64_t dcp_scan_walk_take_queued(struct dcp_scan_walk *x) { return x ? (int64_t)x->walk.take_queued() : 0; }
 
 int dcp_path_hit(int nsteps, int32_t const *state_ids, int32_t const *seqsizes, int32_t hit[5])
 {

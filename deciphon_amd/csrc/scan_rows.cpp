@@ -1,0 +1,220 @@
+// scan_rows.cpp -- see scan_rows.h
+#include "scan_rows.h"
+#include "dcp_errors.h"
+#include "parallel_for.h"
+#include <algorithm>
+#include <stdio.h>
+
+namespace
+{
+
+// product_thread_add_match + write_match (c-core/product_thread.c:40-79,112-148) without HMMER: every step of the
+// hit as "<nucleotides>,<state>,<codon>,<amino>", the last two from decoder_decode / imm_gencode_decode
+// (c-core/match.c:66-89, c-core/decoder.c:38-58) for the emitting states.  *rc receives DCP_EDECODON when a step
+// cannot be decoded (the reference fails the scan there).
+std::string format_row(dcp_batch::Seq const &seq, int window, int wstart, int wstop, DcpHit const &hit,
+                       char const *accession, char const *abc, float lrt, uint32_t const *steps,
+                       DcpDecoder const &dec, std::atomic<int> *rc)
+{
+  // a step: state id in the low 16 bits, emission length above (dcp_hip_path_steps_packed)
+  auto step_id = [&](int i) { return (int)(steps[i] & 0xffffu); };
+  auto step_size = [&](int i) { return (int)(steps[i] >> 16); };
+  char const *sym = seq.has_u ? "ACGU" : "ACGT";
+  char head[256];
+  snprintf(head, sizeof head, "%ld\t%d\t%d\t%d\t%d\t%d\t%d\t%s\t%s\t%.1f\tnan\t", seq.id, window, wstart, wstop, 0,
+           hit.hit_start, hit.hit_stop, accession, abc, (double)lrt);
+  std::string out = head;
+  out.reserve(out.size() + (size_t)(hit.end_step - hit.begin_step) * 12);
+  int pos = 0;
+  for (int i = 0; i < hit.begin_step; ++i) pos += step_size(i);
+  for (int i = hit.begin_step; i < hit.end_step; ++i)
+  {
+    if (i > hit.begin_step) out += ';';
+    char name[8];
+    int const n = step_size(i), id = step_id(i);
+    dcp_state_name(id, name);
+    out.append(seq.text, (size_t)(wstart + pos), (size_t)n);
+    out += ',';
+    out += name;
+    out += ',';
+    if (!dcp_state_is_mute(id))
+    {
+      // insert states decode against the background, match states against their node, N / J / C against the
+      // null model (c-core/decoder.c:43-49)
+      int const kind = id >> 14, k = (id & 0x3FFF) - 1;
+      size_t const entry = kind == 1 ? 1 : kind == 0 ? 2 + (size_t)k : 0;
+      uint8_t codon[3] = {0, 0, 0};
+      bool ok = !(kind <= 1 && (k < 0 || k > dec.core_size)) && n >= 1 && n <= 5;
+      if (ok)
+      {
+        // the code of the n-mer (imm_eseq's indexing: SURVEY 8a row S) keys the decoder's memo
+        static unsigned const code_off[6] = {0, 0, 4, 20, 84, 340};
+        unsigned code = 0;
+        for (int t = 0; t < n; ++t) code = code * 4 + seq.nt[(size_t)(wstart + pos + t)];
+        std::atomic<uint8_t> &slot = dec.memo[entry * DCP_TABLE_SIZE + code_off[n] + code];
+        uint8_t m = slot.load(std::memory_order_relaxed);
+        if (m == 0xFF)
+        {
+          bool const found = dcp_decode_codon_prob((double)dec.epsilon, dec.base.data() + 4 * entry, dec.prior.data() + 64 * entry,
+                                                   seq.nt.data() + wstart + pos, n, codon);
+          m = found ? (uint8_t)(codon[0] * 16 + codon[1] * 4 + codon[2]) : (uint8_t)0xFE;
+          slot.store(m, std::memory_order_relaxed);
+        }
+        ok = m != 0xFE;
+        codon[0] = (uint8_t)(m >> 4);
+        codon[1] = (uint8_t)((m >> 2) & 3);
+        codon[2] = (uint8_t)(m & 3);
+      }
+      char const amino = ok ? dcp_gencode_amino(dec.gencode, codon) : 0;
+      if (!ok || !amino)
+      {
+        int expected = 0;
+        rc->compare_exchange_strong(expected, !ok ? DCP_EDECODON : DCP_EGENCODEID);
+      }
+      else
+      {
+        out += sym[codon[0]];
+        out += sym[codon[1]];
+        out += sym[codon[2]];
+        out += ',';
+        out += amino;
+      }
+      if (!ok || !amino) out += ',';
+    }
+    else
+      out += ',';
+    pos += n;
+  }
+  return out;
+}
+
+} // namespace
+
+DcpScanRows::DcpScanRows(dcp_hip const *eng, DcpDbReader const *db, int index_offset, char const *abc,
+                         dcp_batch const *batch)
+    : eng_(eng), db_(db), index_offset_(index_offset), abc_(abc), batch_(batch),
+      decoders_((size_t)std::max(dcp_hip_num_profiles(eng), 0))
+{
+}
+
+void DcpScanRows::fill(LazyDecoder &ld, int profile) const
+{
+  std::call_once(ld.once, [&]() { ld.rc = db_->read_decoder(index_offset_ + profile, ld.dec); });
+}
+
+void DcpScanRows::warm_decoders(std::vector<dcp_hip_window> const &wins)
+{
+  std::vector<std::pair<int, std::shared_ptr<LazyDecoder>>> warm;
+  for (dcp_hip_window const &w : wins)
+  {
+    std::shared_ptr<LazyDecoder> &d = decoders_[(size_t)w.profile];
+    if (d) continue;
+    d = std::make_shared<LazyDecoder>();
+    warm.emplace_back(w.profile, d);
+  }
+  if (!warm.empty())
+    threads_.emplace_back([this, warm = std::move(warm)]() {
+      dcp_parallel_for(warm.size(), 16, 4, 1, [&](size_t k) { fill(*warm[k].second, warm[k].first); });
+    });
+}
+
+int DcpScanRows::spans(size_t n, std::vector<uint8_t> &is_hit, std::vector<int32_t> &last_hit_pos)
+{
+  // a few threads: 6 M steps to walk for the headline's 2301 hits
+  found_.assign(n, Job());
+  is_hit.assign(n, 0);
+  last_hit_pos.assign(n, -1);
+  std::atomic<int> steps_rc{0};
+  dcp_parallel_for(n, 8, 64, 16, [&](size_t i) {
+    Job &j = found_[i];
+    if (int const src = dcp_hip_path_steps_packed(eng_, (int)i, &j.steps, &j.nsteps))
+    {
+      int expected = 0;
+      steps_rc.compare_exchange_strong(expected, src);
+      return;
+    }
+    is_hit[i] = dcp_find_hit_packed(j.steps, j.nsteps, j.hit) ? 1 : 0;
+    last_hit_pos[i] = j.hit.last_hit_pos;
+  });
+  return steps_rc;
+}
+
+void DcpScanRows::format(std::vector<dcp_walk_hit> const &hits)
+{
+  if (hits.empty()) return;
+  std::vector<Job> jobs;
+  jobs.reserve(hits.size());
+  for (dcp_walk_hit const &h : hits)
+  {
+    Job &j = found_[(size_t)h.batch_index];
+    j.at = h;
+    std::shared_ptr<LazyDecoder> &d = decoders_[(size_t)h.profile];
+    if (!d) d = std::make_shared<LazyDecoder>();
+    j.dec = d;
+    jobs.push_back(std::move(j));
+  }
+  formatted_.emplace_back(jobs.size());
+  std::vector<Row> *out = &formatted_.back();
+  std::promise<void> copied;
+  steps_copied_ = copied.get_future();
+  // up to 16 host threads: a row is a few thousand short appends
+  threads_.emplace_back([this, out, jobs = std::move(jobs), copied = std::move(copied)]() mutable {
+    // the steps out of the engine's buffers first: the scan's next path pass waits for that, not for the rows
+    dcp_parallel_for(jobs.size(), 16, 8, 1, [&](size_t k) {
+      Job &j = jobs[k];
+      j.owned.assign(j.steps, j.steps + j.nsteps);
+      j.steps = j.owned.data();
+    });
+    copied.set_value();
+    dcp_parallel_for(jobs.size(), 16, 8, 1, [&](size_t k) {
+      Job const &j = jobs[k];
+      LazyDecoder &ld = *j.dec;
+      fill(ld, j.at.profile); // decoder_setup, c-core/decoder.c:21-36, once per profile
+      if (ld.rc)
+      {
+        int expected = 0;
+        decode_rc_.compare_exchange_strong(expected, ld.rc);
+        return;
+      }
+      (*out)[k] = Row{j.at.profile, j.at.seq, j.at.window,
+                      format_row(batch_->seqs[(size_t)j.at.seq], j.at.window, j.at.start, j.at.stop, j.hit,
+                                 dcp_hip_profile_accession(eng_, j.at.profile), abc_.c_str(), j.at.lrt, j.steps,
+                                 ld.dec, &decode_rc_)};
+    });
+  });
+}
+
+void DcpScanRows::release_decoders(int first, int last)
+{
+  for (int p = first; p < last; ++p) decoders_[(size_t)p].reset();
+}
+
+int DcpScanRows::join()
+{
+  for (std::thread &t : threads_) t.join();
+  threads_.clear();
+  return decode_rc_;
+}
+
+int DcpScanRows::write(std::string const &file, std::vector<std::string> &products)
+{
+  std::vector<Row> rows;
+  for (std::vector<Row> &part : formatted_)
+    for (Row &r : part) rows.push_back(std::move(r));
+  std::stable_sort(rows.begin(), rows.end(), [](Row const &a, Row const &b) {
+    if (a.profile != b.profile) return a.profile < b.profile;
+    if (a.seq != b.seq) return a.seq < b.seq;
+    return a.window < b.window;
+  });
+  FILE *fp = fopen(file.c_str(), "wb");
+  if (!fp) return DCP_EFOPEN;
+  bool ok = fputs("sequence\twindow\twindow_start\twindow_stop\thit\thit_start\thit_stop\tprofile\tabc\tlrt\tevalue\tmatch\n",
+                  fp) >= 0;
+  products.reserve(rows.size());
+  for (Row &r : rows)
+  {
+    ok = ok && fwrite(r.text.data(), 1, r.text.size(), fp) == r.text.size() && fputc('\n', fp) != EOF;
+    products.push_back(std::move(r.text));
+  }
+  return fclose(fp) != 0 || !ok ? DCP_EWRITEPROD : 0;
+}

@@ -1,0 +1,97 @@
+// scan_rows.h -- from the walked paths of a scan to products.tsv: replaces the products.tsv writer (c-core/product.c,
+// product_thread.c) and the quasi-codon decoding of the match column (c-core/decoder.c, match.c), minus HMMER (the
+// evalue column is "nan" and HMMER's row filter does not run).
+#pragma once
+#include "../../include/deciphon_hip.h"
+#include "../../include/deciphon_host.h"
+#include "dcp_db.h"
+#include "host_logic.h"
+#include <atomic>
+#include <deque>
+#include <future>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+struct dcp_batch
+{
+  struct Seq
+  {
+    long id;
+    std::string name;
+    std::string text;        // uppercased + disambiguated (what dcp_batch_add stores, c-core/sequence.c:15-45)
+    std::vector<uint8_t> nt; // indices 0..3
+    bool has_t = false, has_u = false;
+  };
+  std::vector<Seq> seqs;
+};
+
+// The rows of one dcp_scan_run.  Per path batch, in this order: warm_decoders, wait_steps_copied, dcp_hip_path, spans,
+// format.  Its threads read the batch's sequences, the scan's database and the engine -- the profiles' accessions, and
+// the step buffers of the last dcp_hip_path until they hold copies (wait_steps_copied) -- so it is declared after all
+// of them; its destructor joins the threads.
+class DcpScanRows
+{
+public:
+  DcpScanRows(dcp_hip const *eng, DcpDbReader const *db, int index_offset, char const *abc, dcp_batch const *batch);
+  ~DcpScanRows() { join(); }
+  // decoder_setup (c-core/decoder.c:21-36) for the profiles of this batch -- reading a profile's distributions out of
+  // the database and exponentiating them (a fraction of a millisecond, times hundreds of profiles with hits) -- by host
+  // threads WHILE the GPU walks the paths; the formatters find them ready
+  void warm_decoders(std::vector<dcp_hip_window> const &wins);
+  // until the formatters of the batch before hold copies of its steps: dcp_hip_path overwrites the engine's
+  void wait_steps_copied()
+  {
+    if (steps_copied_.valid()) steps_copied_.get();
+  }
+  // the hit spans of the n paths (c-core/thread.c:130-166): whether each holds a hit, and its last_hit_pos
+  int spans(size_t n, std::vector<uint8_t> &is_hit, std::vector<int32_t> &last_hit_pos);
+  // the rows of these hits of the batch, formatted off the calling thread while the GPU goes on
+  void format(std::vector<dcp_walk_hit> const &hits);
+  // the decoders of profiles [first, last) go (a memo of (K + 3) * 1364 bytes each; the formatter jobs hold their own
+  // references, and a profile that hits again makes a new one)
+  void release_decoders(int first, int last);
+  // joins the formatters; 0, or the first error of quasi-codon decoding (c-core/match.c:66-89 fails the scan the same way)
+  int join();
+  // product_close (c-core/product.c:34-88): rows in profile, read, window order, to `file` and to `products`
+  int write(std::string const &file, std::vector<std::string> &products);
+
+private:
+  // a decoder is handed out empty and filled by whichever thread needs it first
+  struct LazyDecoder
+  {
+    std::once_flag once;
+    int rc = 0;
+    DcpDecoder dec;
+  };
+  struct Row
+  {
+    int profile, seq, window;
+    std::string text;
+  };
+  struct Job
+  {
+    dcp_walk_hit at;
+    DcpHit hit;
+    // the path: first where the engine holds it (dcp_hip_path_steps_packed), then a copy of the job's own
+    uint32_t const *steps = nullptr;
+    int32_t nsteps = 0;
+    std::vector<uint32_t> owned;
+    std::shared_ptr<LazyDecoder> dec;
+  };
+  void fill(LazyDecoder &ld, int profile) const;
+
+  dcp_hip const *eng_;
+  DcpDbReader const *db_;
+  int index_offset_;
+  std::string abc_;
+  dcp_batch const *batch_;
+  std::vector<std::shared_ptr<LazyDecoder>> decoders_; // by local profile
+  std::vector<Job> found_;                             // of the batch between spans and format
+  std::deque<std::vector<Row>> formatted_;             // one per batch; a deque: its formatter writes into the element
+  std::future<void> steps_copied_;                     // of the last batch with hits
+  std::atomic<int> decode_rc_{0};
+  std::vector<std::thread> threads_;
+};

@@ -47,6 +47,21 @@ def _lib():
     L.dcp_cost_order_map.argtypes = [i32, i32, vp]
     L.dcp_scan_plan_chunks.argtypes = [i32, vp, i32, vp, C.c_double, C.c_double, C.c_int64, C.c_int64, i32, vp, vp,
                                        C.POINTER(i32)]
+    L.dcp_scan_walk_new.argtypes = [i32, vp, i32, vp]
+    L.dcp_scan_walk_new.restype = vp
+    L.dcp_scan_walk_del.argtypes = [vp]
+    L.dcp_scan_walk_del.restype = None
+    L.dcp_scan_walk_chunk_windows.argtypes = [vp, vp, C.c_int64, vp, vp]
+    L.dcp_scan_walk_chunk_scored.argtypes = [vp, vp, vp, i32, vp, vp]
+    L.dcp_scan_walk_all_pairs.argtypes = [vp]
+    L.dcp_scan_walk_waiting.argtypes = [vp, i32]
+    L.dcp_scan_walk_take.argtypes = [vp, i32, C.POINTER(vp)]
+    L.dcp_scan_walk_cost_scored.argtypes = [vp, i32, vp, vp]
+    L.dcp_scan_walk_path_walked.argtypes = [vp, vp, vp, C.POINTER(vp)]
+    L.dcp_scan_walk_windows.argtypes = [vp]
+    L.dcp_scan_walk_take_queued.argtypes = [vp]
+    for f in ("waiting", "take", "path_walked", "windows", "take_queued"):
+        getattr(L, "dcp_scan_walk_" + f).restype = C.c_int64
     L.dcp_window_setup.argtypes = [C.POINTER(_Window), i32, i32]
     L.dcp_window_setup.restype = None
     L.dcp_window_next.argtypes = [C.POINTER(_Window)]
@@ -279,6 +294,87 @@ def plan_chunks(core_sizes, read_lengths, first_cells: float, later_cells: float
         if rc:
             raise HipError(rc)
         return chunks[: n.value].copy(), windows[: n.value].copy()
+
+
+WALK_HIT = np.dtype([("batch_index", "i4"), ("profile", "i4"), ("seq", "i4"), ("window", "i4"), ("start", "i4"),
+                     ("stop", "i4"), ("lrt", "f4")])  # struct dcp_walk_hit
+
+
+class ScanWalk:
+    """dcp_scan_run's window walk without a GPU (include/deciphon_host.h dcp_scan_walk_*; the rules at
+    csrc/scan_walk.h).  Windows are int32[n][4] = (profile, read, start, stop)."""
+
+    COST, PATH = 0, 1
+
+    def __init__(self, core_sizes, read_lengths):
+        self.lib = _lib()
+        K = np.ascontiguousarray(core_sizes, np.int32)
+        R = np.ascontiguousarray(read_lengths, np.int32)
+        self.h = self.lib.dcp_scan_walk_new(len(K), K.ctypes.data_as(C.c_void_p), len(R), R.ctypes.data_as(C.c_void_p))
+        if not self.h:
+            raise HipError(1)
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            self.lib.dcp_scan_walk_del(self.h)
+            self.h = None
+
+    def chunk_windows(self, chunk, windows: int):
+        """-> (wins int32[windows][4], base int64[pairs + 1]) of chunk (p0, p1, s0, s1)."""
+        c = np.ascontiguousarray(chunk, np.int32)
+        wins = np.zeros((int(windows), 4), np.int32)
+        base = np.zeros((int(c[1]) - int(c[0])) * (int(c[3]) - int(c[2])) + 1, np.int64)
+        rc = self.lib.dcp_scan_walk_chunk_windows(self.h, c.ctypes.data_as(C.c_void_p), int(windows),
+                                                  wins.ctypes.data_as(C.c_void_p), base.ctypes.data_as(C.c_void_p))
+        if rc:
+            raise HipError(rc)
+        return wins, base
+
+    def chunk_scored(self, chunk, base, hit_index, lrts) -> None:
+        c = np.ascontiguousarray(chunk, np.int32)
+        b = np.ascontiguousarray(base, np.int64)
+        hi = np.ascontiguousarray(hit_index, np.int32)
+        lr = np.ascontiguousarray(lrts, np.float32)
+        rc = self.lib.dcp_scan_walk_chunk_scored(self.h, c.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p),
+                                                 len(hi), hi.ctypes.data_as(C.c_void_p), lr.ctypes.data_as(C.c_void_p))
+        if rc:
+            raise HipError(rc)
+
+    def all_pairs(self) -> None:
+        self.lib.dcp_scan_walk_all_pairs(self.h)
+
+    def waiting(self, which: int) -> int:
+        return int(self.lib.dcp_scan_walk_waiting(self.h, which))
+
+    def take(self, which: int) -> np.ndarray:
+        p = C.c_void_p()
+        n = int(self.lib.dcp_scan_walk_take(self.h, which, C.byref(p)))
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int32)), (n, 4)).copy() if n else np.zeros((0, 4), np.int32)
+
+    def cost_scored(self, hit_index, lrts) -> None:
+        hi = np.ascontiguousarray(hit_index, np.int32)
+        lr = np.ascontiguousarray(lrts, np.float32)
+        rc = self.lib.dcp_scan_walk_cost_scored(self.h, len(hi), hi.ctypes.data_as(C.c_void_p),
+                                                lr.ctypes.data_as(C.c_void_p))
+        if rc:
+            raise HipError(rc)
+
+    def path_walked(self, is_hit, last_hit_pos) -> np.ndarray:
+        """-> the hits (WALK_HIT records) as they stand before their pairs move on."""
+        ih = np.ascontiguousarray(is_hit, np.uint8)
+        lp = np.ascontiguousarray(last_hit_pos, np.int32)
+        p = C.c_void_p()
+        n = int(self.lib.dcp_scan_walk_path_walked(self.h, ih.ctypes.data_as(C.c_void_p), lp.ctypes.data_as(C.c_void_p),
+                                                   C.byref(p)))
+        if not n:
+            return np.zeros(0, WALK_HIT)
+        return np.frombuffer(C.string_at(p, n * WALK_HIT.itemsize), WALK_HIT).copy()
+
+    def windows(self) -> int:
+        return int(self.lib.dcp_scan_walk_windows(self.h))
+
+    def take_queued(self) -> int:
+        return int(self.lib.dcp_scan_walk_take_queued(self.h))
 
 
 def unzip(K: int, L: int, xnodes: np.ndarray, nodes: np.ndarray):

@@ -96,6 +96,40 @@ int dcp_scan_plan_chunks(int nprof, int32_t const *core_sizes, int nreads, int32
 #define DCP_SCAN_CHUNK_PAIRS (1 << 21)
 #define DCP_SCAN_CHUNK_WINDOWS (4 << 20)
 
+/* ---- the window walk of dcp_scan_run (csrc/scan_walk.h: the rules), for tests: which windows of which (profile,
+ * read) pairs a scan scores, keeps or scores again, given the verdicts of the cost and path passes.  Windows are
+ * struct dcp_hip_window (include/deciphon_hip.h: int32 profile, seq, start, stop).  A chunk is {p0, p1, s0, s1} and
+ * its window count, as dcp_scan_plan_chunks gives them.  Lists that a call returns belong to the walk and stand until
+ * its next call of the same name. ---- */
+struct dcp_scan_walk;
+struct dcp_hip_window;
+struct dcp_walk_hit /* a hit as dcp_scan_walk_path_walked reports it */
+{
+  int32_t batch_index; /* its window's index in the path batch */
+  int32_t profile, seq, window, start, stop;
+  float lrt;
+};
+struct dcp_scan_walk *dcp_scan_walk_new(int nprof, int32_t const *core_sizes, int nreads, int32_t const *read_lengths);
+void dcp_scan_walk_del(struct dcp_scan_walk *);
+/* wins[windows] and base[pairs + 1] (the first window of each pair, and the total) are filled; DCP_EFUNCUSE when the
+ * chains do not make `windows` windows */
+int dcp_scan_walk_chunk_windows(struct dcp_scan_walk *, int32_t const chunk[4], int64_t windows,
+                                struct dcp_hip_window *wins, int64_t *base);
+/* the nh windows of the chunk that passed the filter, ascending, and their lrt */
+int dcp_scan_walk_chunk_scored(struct dcp_scan_walk *, int32_t const chunk[4], int64_t const *base, int nh,
+                               int32_t const *hit_index, float const *lrts);
+int dcp_scan_walk_all_pairs(struct dcp_scan_walk *); /* nothing speculated */
+/* windows waiting for a cost round (which = 0) or a path pass (1); take: they become the batch, *wins its windows */
+int64_t dcp_scan_walk_waiting(struct dcp_scan_walk const *, int which);
+int64_t dcp_scan_walk_take(struct dcp_scan_walk *, int which, struct dcp_hip_window const **wins);
+int dcp_scan_walk_cost_scored(struct dcp_scan_walk *, int nh, int32_t const *hit_index, float const *lrts);
+/* is_hit[n], last_hit_pos[n] per window of the path batch; returns the number of hits, *hits as they stand before
+ * their pairs move on */
+int64_t dcp_scan_walk_path_walked(struct dcp_scan_walk *, uint8_t const *is_hit, int32_t const *last_hit_pos,
+                                  struct dcp_walk_hit const **hits);
+int64_t dcp_scan_walk_windows(struct dcp_scan_walk const *);  /* walked so far */
+int64_t dcp_scan_walk_take_queued(struct dcp_scan_walk *);    /* queued for a cost round since the last call */
+
 /* ---- window iteration: window_setup / window_next / window_set_last_hit_position
  * (c-core/window.c:7-50) ---- */
 struct dcp_window

@@ -1,6 +1,9 @@
-// host_sanitize.cpp -- TEST INFRASTRUCTURE: the host-side .dcp reader, windows and partitions under ASan + UBSan,
-// on the golden database, on truncated copies and on 200 randomly corrupted copies (must fail cleanly, never fault).
+// host_sanitize.cpp -- TEST INFRASTRUCTURE: the host-side .dcp reader, windows, partitions and one short window walk
+// under ASan + UBSan, on the golden database, on truncated copies and on 200 randomly corrupted copies (must fail
+// cleanly, never fault).
+#include "deciphon_hip.h"
 #include "deciphon_host.h"
+#include <vector>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -28,6 +31,41 @@ int main(int argc, char **argv)
   while (dcp_window_next(&w)) printf("  window %d [%d,%d)\n", w.idx, w.start, w.stop);
   for (int N = 0; N < 30; ++N) for (int P = 1; P < 9; ++P) { long s = 0; for (int i = 0; i < P; ++i) s += dcp_partition_size(N, P, i); if (s != N) { printf("partition bug\n"); return 1; } }
   dcp_db_close(db);
+  {
+    /* a short walk (csrc/scan_walk.h): 2 profiles x 4 reads in one chunk; every third window passes the filter, and
+     * every second path holds a hit that ends in the middle of its window */
+    int32_t const K[2] = {3, 12}, R[4] = {0, 700, 2000, 700}, chunk[4] = {0, 2, 0, 4};
+    int64_t nw = 0;
+    for (int p = 0; p < 2; ++p) for (int s = 0; s < 4; ++s) nw += dcp_window_count(R[s], K[p]);
+    struct dcp_scan_walk *walk = dcp_scan_walk_new(2, K, 4, R);
+    std::vector<dcp_hip_window> wins((size_t)nw);
+    std::vector<int64_t> base(2 * 4 + 1);
+    rc = dcp_scan_walk_chunk_windows(walk, chunk, nw, wins.data(), base.data());
+    if (rc) { printf("walk: chunk_windows rc %d\n", rc); return 1; }
+    std::vector<int32_t> idx;
+    std::vector<float> lrt;
+    for (int64_t i = 0; i < nw; i += 3) { idx.push_back((int32_t)i); lrt.push_back((float)i); }
+    dcp_scan_walk_chunk_scored(walk, chunk, base.data(), (int)idx.size(), idx.data(), lrt.data());
+    long nhits = 0, rounds = 0;
+    while (dcp_scan_walk_waiting(walk, 0) || dcp_scan_walk_waiting(walk, 1))
+    {
+      dcp_hip_window const *w = NULL;
+      dcp_walk_hit const *hits = NULL;
+      int64_t n = dcp_scan_walk_take(walk, 1, &w);
+      std::vector<uint8_t> is_hit((size_t)n);
+      std::vector<int32_t> pos((size_t)n);
+      for (int64_t i = 0; i < n; ++i) { is_hit[(size_t)i] = (w[i].start / 7) % 2; pos[(size_t)i] = (w[i].stop - w[i].start) / 2; }
+      if (n) nhits += (long)dcp_scan_walk_path_walked(walk, is_hit.data(), pos.data(), &hits);
+      n = dcp_scan_walk_take(walk, 0, &w);
+      idx.clear(); lrt.clear();
+      for (int64_t i = 0; i < n; i += 3) { idx.push_back((int32_t)i); lrt.push_back(1.0f); }
+      dcp_scan_walk_cost_scored(walk, (int)idx.size(), idx.data(), lrt.data());
+      if (++rounds > 100000) { printf("walk does not end\n"); return 1; }
+    }
+    printf("walk done: %lld of %lld windows, %ld hits, %lld scored again\n", (long long)dcp_scan_walk_windows(walk),
+           (long long)nw, nhits, (long long)dcp_scan_walk_take_queued(walk));
+    dcp_scan_walk_del(walk);
+  }
   /* truncated and corrupt files must fail cleanly */
   FILE *f = fopen(argv[1], "rb"); fseek(f, 0, SEEK_END); long sz = ftell(f); fseek(f, 0, SEEK_SET);
   char *buf = (char *)malloc(sz); fread(buf, 1, sz, f); fclose(f);
