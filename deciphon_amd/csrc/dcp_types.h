@@ -154,6 +154,51 @@ DCP_HDI bool dcp_replay_thread_row(int L, int B, int G, int it, int r, int *sub,
   return *row <= blk->last;
 }
 
+// ---- which columns of an emission row a lane reads --------------------------------------------------------
+// A profile of K positions is padded with +inf to Kp columns, and a lane whose positions all lie at or beyond K owns
+// nothing: BM, MM, IM and DM are +inf there, so its Mpre is +inf from row 0 on and M = min_t(Mpre + em) is +inf
+// whatever em holds, +inf or not; I, D and E never see em.  Such a lane does not fetch its padding columns.  It reads
+// what the LAST lane that owns a position reads -- a line that lane fetches anyway -- and a lane that owns at least
+// one position reads exactly its own Q columns, the +inf tail of the lane that straddles K included.
+//   DCP_ROW_CANON       one wavefront of 64 lanes x Q positions on the canonical rows, chunk c = floats 4c .. of the
+//                       lane (Q <= 4, and the table-writing kernels: one chunk of Q floats)
+//   DCP_ROW_COST_ORDER  the same on the cost-order copy (cost_rows_off): the clamp holds chunk by chunk
+//   DCP_ROW_PACK        a group of S lanes (viterbi_pack.h): lane 0 is the separator and reads the row's header,
+//                       offset 0; lane e >= 1 owns positions (e - 1) Q ..; the last real lane is the group's own
+enum { DCP_ROW_CANON, DCP_ROW_COST_ORDER, DCP_ROW_PACK };
+#define DCP_ROW_MAX_CHUNKS 3 // (Q + 3) / 4 for Q <= 10 (ten positions per lane: 4 + 4 + 2)
+
+// lanes, of `lanes` that own Q positions each, with at least one position below K
+DCP_HDI int dcp_row_real_lanes(int Q, int lanes, int K)
+{
+  int const n = (K + Q - 1) / Q;
+  return n < 1 ? 1 : n > lanes ? lanes : n;
+}
+// the position-owning lane whose columns position-owning lane `lane` reads
+DCP_HDI uint32_t dcp_row_source_lane(uint32_t real, uint32_t lane) { return lane < real ? lane : real - 1u; }
+DCP_HDI int dcp_row_chunk_width(int Q, int c) { return Q - 4 * c < 4 ? Q - 4 * c : 4; }
+// byte offset inside a row of chunk c of position-owning lane `lane` (lane = 64 w + e beyond one wavefront)
+DCP_HDI uint32_t dcp_row_lane_bytes(int layout, int Q, uint32_t lane, int c)
+{
+  if (layout == DCP_ROW_COST_ORDER) // contiguous spans of 64 lanes x chunk width behind a 128-byte header
+    return (uint32_t)(4 * DCP_COST_ORDER_HDR) + (lane >> 6) * (uint32_t)(256 * Q) + (uint32_t)(1024 * c) +
+           (lane & 63u) * (uint32_t)(4 * dcp_row_chunk_width(Q, c));
+  return (uint32_t)(DCP_ROW_HDR * 4) + lane * (uint32_t)(Q * 4) + (uint32_t)(16 * c);
+}
+// The statement itself: lanes of the shape that own a real position of a profile of K positions, and where lane e
+// (of the wavefront, or of its group of S) reads chunk c of an emission row.  The kernels take the three functions
+// above (CostWave::init, PackWave::init); the host and the tests take this one.
+DCP_HDI int dcp_row_read_lanes(int layout, int Q, int S, int K)
+{
+  return dcp_row_real_lanes(Q, layout == DCP_ROW_PACK ? S - 1 : 64, K);
+}
+DCP_HDI uint32_t dcp_row_read_offset(int layout, int Q, int S, int K, uint32_t e, int c)
+{
+  uint32_t const real = (uint32_t)dcp_row_read_lanes(layout, Q, S, K);
+  if (layout != DCP_ROW_PACK) return dcp_row_lane_bytes(layout, Q, dcp_row_source_lane(real, e), c);
+  return e == 0 ? 0u : dcp_row_lane_bytes(DCP_ROW_CANON, Q, dcp_row_source_lane(real, e - 1u), 0);
+}
+
 // where the traceback of one window stands between blocks (all zero = not started)
 struct DcpTraceState
 {

@@ -2,6 +2,7 @@
 #include "../../include/deciphon_host.h"
 #include "dcp_db.h"
 #include "dcp_errors.h"
+#include "dcp_types.h"
 #include "host_logic.h"
 #include "scan_walk.h"
 
@@ -113,6 +114,18 @@ int dcp_cost_order_map(int Q, int W, int32_t *cols)
   if (Q < 1 || W < 1 || Q * W > 64 || !cols) return 0;
   for (int k = 0; k < 64 * Q * W; ++k) cols[k] = dcp_cost_order_col(Q, W, k);
   return dcp_cost_order_stride(Q, W);
+}
+
+int dcp_row_lane_offsets(int layout, int Q, int S, int K, uint32_t *offsets)
+{
+  bool const pack = layout == DCP_ROW_PACK;
+  if (layout < DCP_ROW_CANON || layout > DCP_ROW_PACK || Q < 1 || Q > 16 || K < 1 || !offsets) return 0;
+  if (pack && S != 4 && S != 8 && S != 16 && S != 32) return 0;
+  int const lanes = pack ? S : 64, chunks = pack ? 1 : (Q + 3) / 4;
+  if (K > (pack ? S - 1 : 64) * Q) return 0;
+  for (int e = 0; e < lanes; ++e)
+    for (int c = 0; c < chunks; ++c) offsets[e * chunks + c] = dcp_row_read_offset(layout, Q, S, K, (uint32_t)e, c);
+  return dcp_row_read_lanes(layout, Q, S, K);
 }
 
 int dcp_partition_bounds_of(int n, int32_t const *core_sizes, int nparts, int balanced, int32_t *first)

@@ -533,7 +533,7 @@ DCP_FN RowSrc rowsrc_make(float const *__restrict__ base, uint32_t bytes)
 }
 
 // byte offset of a lane's Q positions inside a row
-template <int Q> DCP_FN lu row_lane_offset(lu lane) { return lane * (uint32_t)(Q * 4) + (uint32_t)(DCP_ROW_HDR * 4); }
+template <int Q> DCP_FN lu row_lane_offset(lu lane) { return dcp_row_lane_bytes(DCP_ROW_CANON, Q, lane, 0); }
 
 DCP_FN void load_row_hdr(RowSrc const &r, uint32_t soff, float &nil, float &bg)
 {
@@ -620,17 +620,14 @@ template <> DCP_FN void load_row_q<10>(RowSrc const &r, lu voff, uint32_t soff, 
 template <int Q> struct DcpRowChunks
 {
   static constexpr int N = (Q + 3) / 4;
-  static constexpr int width(int c) { return Q - 4 * c < 4 ? Q - 4 * c : 4; }
+  static constexpr int width(int c) { return Q - 4 * c < 4 ? Q - 4 * c : 4; } // dcp_row_chunk_width
 };
 
 template <int Q, int W> DCP_FN void row_chunk_offsets(lu lane, bool ordered, lu (&v)[DcpRowChunks<Q>::N])
 {
-  lu const w = lane >> 6, e = lane & 63u;
 #pragma unroll
   for (int c = 0; c < DcpRowChunks<Q>::N; ++c)
-    v[c] = ordered ? (uint32_t)(4 * DCP_COST_ORDER_HDR) + w * (uint32_t)(256 * Q) + (uint32_t)(1024 * c) +
-                         e * (uint32_t)(4 * DcpRowChunks<Q>::width(c))
-                   : row_lane_offset<Q>(lane) + (uint32_t)(16 * c);
+    v[c] = dcp_row_lane_bytes(ordered ? DCP_ROW_COST_ORDER : DCP_ROW_CANON, Q, lane, c);
 }
 
 template <int Q, int C = 0>

@@ -114,6 +114,9 @@ template <int Q, int TURNS> DCP_FN lf dcp_lazy_turns_carry(lf (&D)[Q], lf const 
 DCP_FN lf lane_shift_up_again(lf &x) { return lane_shift_up(x, 0.0f); }
 #endif
 
+// dcp_row_source_lane (dcp_types.h) in the lane vocabulary: of `real` lanes that own a position, the one lane reads as
+DCP_FN lu row_source_lane(lu lane, int real) { return lminu(lane, lu_splat((uint32_t)real - 1u)); }
+
 // STORE = true additionally writes every row's final values to a DP table in HBM
 // (cells[l][{M,I,D}][Kp] and specials[l][8] = N,B,J,E,C) for the traceback of
 // traceback.h -- the fast path pass.
@@ -243,6 +246,12 @@ template <int Q, int W, bool STORE = false, int POLICY = DCP_SHAPE_POLICY(Q, W)>
     int const Kp = pf.Kp;
     stride_bytes = (uint32_t)(Kp + DCP_ROW_HDR) * 4u;
     int64_t rows_off = pf.rows_off;
+    // the lane whose columns this one reads (dcp_types.h, "which columns of an emission row a lane reads"): a single
+    // wave's lanes beyond the profile's K positions -- the K of the profile, whatever table a narrow kernel runs on --
+    // read with the last lane that owns one.  (W > 1: every lane its own; the lane offsets carry the wave index.
+    // The table-writing kernels too: their stores take the lane's own offset, which the loads share with them -- a
+    // second one is a register more in dcp_path_blocks_kernel.)
+    lu const src = W == 1 && !STORE ? row_source_lane(lane, dcp_row_real_lanes(Q, 64, pf.K)) : lane;
 #ifdef DCP_COST_ORDER
     if constexpr (ORDERED)
     {
@@ -252,11 +261,11 @@ template <int Q, int W, bool STORE = false, int POLICY = DCP_SHAPE_POLICY(Q, W)>
         rows_off = pf.cost_rows_off;
         stride_bytes = 4u * (uint32_t)(DCP_COST_ORDER_HDR + 64 * Q * W); // dcp_cost_order_stride
       }
-      row_chunk_offsets<Q, W>(lane, copy, voffc);
+      row_chunk_offsets<Q, W>(src, copy, voffc);
     }
 #endif
     rows = rowsrc_make(pool + rows_off, (uint32_t)DCP_TABLE_SIZE * stride_bytes);
-    voff = row_lane_offset<Q>(lane);
+    voff = row_lane_offset<Q>(src);
     codes = code_rows;
     float const *__restrict__ trans = pool + pf.trans_off;
     load_q<Q>(trans + DCP_BM * Kp, lane, BM);

@@ -417,10 +417,11 @@ __global__ __launch_bounds__(64 * WG) void dcp_cost_pack_lds_kernel(float const 
   DcpProfileDev const pf = profiles[packs[grp.x].profile];
   float const *__restrict__ rows = pool + pf.rows_off;
   int const stride = pf.Kp + DCP_ROW_HDR;
+  int const used = pf.K + DCP_ROW_HDR; // the columns behind it are the +inf padding: not fetched
   for (int i = (int)threadIdx.x; i < NR * RL; i += 64 * WG)
   {
     int const c = i / RL, j = i - c * RL;
-    table[i] = j < stride ? rows[(size_t)c * stride + j] : __builtin_inff();
+    table[i] = j < used ? rows[(size_t)c * stride + j] : __builtin_inff();
   }
   __syncthreads();
   int const wave = (int)(threadIdx.x >> 6);

@@ -170,8 +170,11 @@ template <int Q, int S, int TURNS = dcp_lazy_turns(Q), int NLDS = 0, bool LATE =
     // padded arrays (+inf) and reads the header of every emission row (byte offset 0)
     lm const sep = lequ(e, lu_splat(0));
     lu const col = lselu(sep, lu_splat((uint32_t)(Kp - Q)), (e - lu_splat(1)) * (uint32_t)Q);
+    // ... but of the emission rows a lane beyond the profile's K positions reads what the group's last lane that owns
+    // one reads (dcp_types.h, "which columns of an emission row a lane reads": its Mpre is +inf whatever it adds)
+    lu const rcol = row_source_lane(e - lu_splat(1), dcp_row_real_lanes(Q, S - 1, pf.K)) * (uint32_t)Q;
     src = packsrc_make(pool + pf.rows_off, Kp, code_rows, ncode_rows,
-                       lselu(sep, lu_splat(0), (col + (uint32_t)DCP_ROW_HDR) * 4u));
+                       lselu(sep, lu_splat(0), (rcol + (uint32_t)DCP_ROW_HDR) * 4u));
     lds_off = lselu(sep, lu_splat(0), col + (uint32_t)DCP_ROW_HDR);
     float const *__restrict__ trans = pool + pf.trans_off;
     lf BM[Q], MM[Q], MI[Q], IM[Q], II[Q], DM[Q];

@@ -45,6 +45,7 @@ def _lib():
     L.dcp_window_count.argtypes = [C.c_int64, i32]
     L.dcp_window_count.restype = C.c_int64
     L.dcp_cost_order_map.argtypes = [i32, i32, vp]
+    L.dcp_row_lane_offsets.argtypes = [i32, i32, i32, i32, vp]
     L.dcp_scan_plan_chunks.argtypes = [i32, vp, i32, vp, C.c_double, C.c_double, C.c_int64, C.c_int64, i32, vp, vp,
                                        C.POINTER(i32)]
     L.dcp_scan_walk_new.argtypes = [i32, vp, i32, vp]
@@ -272,6 +273,22 @@ def cost_order_map(Q: int, W: int):
     if stride <= 0:
         raise ValueError(f"no cost-order map for Q={Q}, W={W}")
     return cols, stride
+
+
+ROW_CANON, ROW_COST_ORDER, ROW_PACK = 0, 1, 2
+
+
+def row_lane_offsets(layout: int, Q: int, S: int, K: int):
+    """(lanes that own a position below K, offsets uint32[lanes][chunks]): the byte offset inside an emission row
+    that every lane of a cost kernel reads each chunk of its Q floats from, for a profile of K positions
+    (csrc/dcp_types.h dcp_row_read_offset).  layout: ROW_CANON / ROW_COST_ORDER (64 lanes, chunks of four floats)
+    or ROW_PACK (one group of S lanes, the separator first, one chunk)."""
+    lanes, chunks = (S, 1) if layout == ROW_PACK else (64, (Q + 3) // 4)
+    off = np.zeros((max(lanes, 1), max(chunks, 1)), np.uint32)
+    real = int(_lib().dcp_row_lane_offsets(int(layout), int(Q), int(S), int(K), off.ctypes.data_as(C.c_void_p)))
+    if real <= 0:
+        raise ValueError(f"no cost kernel of layout {layout}, Q={Q}, S={S} takes K={K}")
+    return real, off
 
 
 def plan_chunks(core_sizes, read_lengths, first_cells: float, later_cells: float, max_pairs: int, max_windows: int):

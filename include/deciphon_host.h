@@ -81,6 +81,15 @@ int64_t dcp_window_count(int64_t seq_size, int core_size);
  * first column (behind the row's 32-float header), and the function returns the floats of one copy row (0 and
  * nothing written for Q < 1, W < 1 or Q*W > 64). */
 int dcp_cost_order_map(int Q, int W, int32_t *cols);
+/* Which columns of an emission row the lanes of a cost kernel read for a profile of K positions (csrc/dcp_types.h
+ * dcp_row_read_offset: a lane with no position below K reads with the last lane that has one).  layout 0: one
+ * wavefront of 64 lanes x Q positions on the canonical rows; 1: the same on the cost-order copy; 2: one group of S
+ * lanes x Q positions of a packed kernel, lane 0 its separator.  offsets[e * chunks + c] receives the byte offset
+ * inside a row of chunk c of lane e -- chunks = (Q + 3) / 4 chunks of up to four floats for layouts 0 and 1, one
+ * chunk of Q floats for layout 2 -- for the 64 (layout 2: S) lanes.  Returns the lanes that own at least one
+ * position below K (layout 2: the separator not counted), or 0 with nothing written for a shape no kernel has
+ * (Q < 1, Q > 16, K < 1, K beyond the shape's positions, S not 4, 8, 16 or 32). */
+int dcp_row_lane_offsets(int layout, int Q, int S, int K, uint32_t *offsets);
 /* How dcp_scan_run cuts profiles x reads into cost batches (csrc/host_logic.h dcp_plan_chunks: the rules).
  * dcp_scan_run plans with first_cells = DCP_SCAN_FIRST_CHUNK_CELLS, later_cells = unlimited (both
  * DECIPHON_HIP_CHUNK_CELLS when that is set), max_pairs = DCP_SCAN_CHUNK_PAIRS and max_windows =
