@@ -26,6 +26,7 @@
 #include <errno.h>
 #include <limits.h>
 #include <math.h>
+#include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -47,7 +48,7 @@ struct dcp_scan
   int num_proteins = 0;   // of this partition
   int index_offset = 0;   // global index of local profile 0 (workload_index, c-core/workload.c:95)
   std::string abc_name = "dna";
-  std::vector<std::string> products;
+  std::unique_ptr<DcpProductRuns> runs; // the rows of the last dcp_scan_run (dcp_scan_product), until the next one
   double timing[DCP_SCAN_TIMING_VALUES] = {0}; // dcp_scan_last_timing
   std::unique_ptr<DcpDbReader> db; // stays mapped: the rows read the distributions of the profiles with hits from it
 };
@@ -174,6 +175,9 @@ struct Knobs
   double chunk_cells = 0;   // DECIPHON_HIP_CHUNK_CELLS: cells per chunk (experiments)
   double chunk_windows = 0; // DECIPHON_HIP_CHUNK_WINDOWS: windows per chunk
   size_t drain_hits = 32768; // DECIPHON_HIP_PATH_DRAIN_HITS: see dcp_scan_run
+  // DECIPHON_HIP_PRODUCT_MB: the row text a scan holds before it sorts it into a run file (csrc/product_runs.h); 0:
+  // every path batch is a run.  The default keeps the rows of some 30000 hits in memory, as every scan did before.
+  double product_mb = 1024;
   bool timing = false;      // DECIPHON_HIP_TIMING=1: phase times of dcp_scan_run on stderr
   Knobs()
   {
@@ -182,6 +186,7 @@ struct Knobs
     if (char const *e = getenv("DECIPHON_HIP_CHUNK_CELLS")) chunk_cells = atof(e);
     if (char const *e = getenv("DECIPHON_HIP_CHUNK_WINDOWS")) chunk_windows = atof(e);
     if (char const *e = getenv("DECIPHON_HIP_PATH_DRAIN_HITS")) drain_hits = (size_t)std::max(atol(e), 0L);
+    if (char const *e = getenv("DECIPHON_HIP_PRODUCT_MB")) product_mb = atof(e);
     timing = getenv("DECIPHON_HIP_TIMING") != nullptr;
   }
 };
@@ -192,6 +197,17 @@ struct InFlight
   int chunk;
   std::vector<dcp_hip_window> wins;
   std::vector<int64_t> base; // DcpScanWalk::chunk_windows
+};
+
+// a scan that fails keeps no rows and leaves no run file (declared before the rows: their threads end first)
+struct DropRuns
+{
+  dcp_scan *x;
+  bool keep = false;
+  ~DropRuns()
+  {
+    if (!keep) x->runs.reset();
+  }
 };
 
 // whatever happens, no batch stays outstanding on the engine
@@ -354,7 +370,7 @@ int dcp_scan_run(struct dcp_scan *x, struct dcp_batch *batch, char const *produc
   if (!x->eng) return raise(DCP_EFUNCUSE, __func__, "dcp_scan_setup has not succeeded");
   x->done_proteins = 0;
   x->interrupted = false;
-  x->products.clear();
+  x->runs.reset();
   int rc = 0;
   Phase ph;
   Knobs const knobs;
@@ -403,7 +419,11 @@ int dcp_scan_run(struct dcp_scan *x, struct dcp_batch *batch, char const *produc
       return raise(DCP_EFUNCUSE, __func__, "a chunk holds more than INT_MAX windows: lower DECIPHON_HIP_CHUNK_WINDOWS");
 
   DcpScanWalk walk(nprof, K.data(), nseq, len.data());
-  DcpScanRows rows(x->eng, x->db.get(), x->index_offset, x->abc_name.c_str(), batch); // (after all that its threads read)
+  // (bytes below 2^63; what atof makes of no number is 0)
+  int64_t const budget = knobs.product_mb >= 1.0e12 ? INT64_MAX : knobs.product_mb > 0 ? (int64_t)(knobs.product_mb * 1048576.0) : 0;
+  x->runs.reset(new DcpProductRuns(product_dir, budget));
+  DropRuns drop{x};
+  DcpScanRows rows(x->eng, x->db.get(), x->index_offset, x->abc_name.c_str(), batch, x->runs.get()); // (after all that its threads read)
   Run r{x, walk, rows, ph};
   if (knobs.speculate)
   {
@@ -479,7 +499,8 @@ int dcp_scan_run(struct dcp_scan *x, struct dcp_batch *batch, char const *produc
 
   if ((rc = rows.join())) return raise(rc, __func__);
   ph.rows += ph.lap();
-  if ((rc = rows.write(file, x->products))) return raise(rc, __func__, file.c_str());
+  if ((rc = rows.write(file))) return raise(rc, __func__, file.c_str());
+  drop.keep = true;
   ph.write += ph.lap();
   {
     // (the progress callbacks of a batch are made while the GPU scores it: they count as cost pass)
@@ -509,7 +530,16 @@ int dcp_scan_progress(struct dcp_scan const *x)
   return (100 * x->done_proteins.load()) / x->num_proteins; // c-core/scan.c:224-227
 }
 
-long dcp_scan_num_products(struct dcp_scan const *x) { return x ? (long)x->products.size() : 0; }
+long dcp_scan_num_products(struct dcp_scan const *x) { return x && x->runs ? x->runs->num_rows() : 0; }
+
+int dcp_scan_product_stats(struct dcp_scan const *x, int64_t *out, int n)
+{
+  if (!x || (n > 0 && !out)) return 0;
+  int64_t v[DCP_SCAN_PRODUCT_STATS_VALUES] = {0, 0, 0, 0};
+  if (x->runs) x->runs->stats(v);
+  for (int i = 0; i < n && i < DCP_SCAN_PRODUCT_STATS_VALUES; ++i) out[i] = v[i];
+  return DCP_SCAN_PRODUCT_STATS_VALUES;
+}
 
 int dcp_scan_last_timing(struct dcp_scan const *x, double *out, int n)
 {
@@ -520,8 +550,7 @@ int dcp_scan_last_timing(struct dcp_scan const *x, double *out, int n)
 
 char const *dcp_scan_product(struct dcp_scan const *x, long i)
 {
-  if (!x || i < 0 || i >= (long)x->products.size()) return nullptr;
-  return x->products[(size_t)i].c_str();
+  return x && x->runs ? x->runs->row(i) : nullptr;
 }
 
 struct dcp_batch *dcp_batch_new(void) { return new (std::nothrow) dcp_batch; }

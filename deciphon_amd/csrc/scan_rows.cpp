@@ -91,8 +91,8 @@ std::string format_row(dcp_batch::Seq const &seq, int window, int wstart, int ws
 } // namespace
 
 DcpScanRows::DcpScanRows(dcp_hip const *eng, DcpDbReader const *db, int index_offset, char const *abc,
-                         dcp_batch const *batch)
-    : eng_(eng), db_(db), index_offset_(index_offset), abc_(abc), batch_(batch),
+                         dcp_batch const *batch, DcpProductRuns *runs)
+    : eng_(eng), db_(db), index_offset_(index_offset), abc_(abc), batch_(batch), runs_(runs),
       decoders_((size_t)std::max(dcp_hip_num_profiles(eng), 0))
 {
 }
@@ -153,12 +153,11 @@ void DcpScanRows::format(std::vector<dcp_walk_hit> const &hits)
     j.dec = d;
     jobs.push_back(std::move(j));
   }
-  formatted_.emplace_back(jobs.size());
-  std::vector<Row> *out = &formatted_.back();
+  int64_t const serial = batches_++ << 32;
   std::promise<void> copied;
   steps_copied_ = copied.get_future();
   // up to 16 host threads: a row is a few thousand short appends
-  threads_.emplace_back([this, out, jobs = std::move(jobs), copied = std::move(copied)]() mutable {
+  threads_.emplace_back([this, serial, jobs = std::move(jobs), copied = std::move(copied)]() mutable {
     // the steps out of the engine's buffers first: the scan's next path pass waits for that, not for the rows
     dcp_parallel_for(jobs.size(), 16, 8, 1, [&](size_t k) {
       Job &j = jobs[k];
@@ -166,6 +165,7 @@ void DcpScanRows::format(std::vector<dcp_walk_hit> const &hits)
       j.steps = j.owned.data();
     });
     copied.set_value();
+    std::vector<DcpProductRuns::Row> out(jobs.size());
     dcp_parallel_for(jobs.size(), 16, 8, 1, [&](size_t k) {
       Job const &j = jobs[k];
       LazyDecoder &ld = *j.dec;
@@ -176,11 +176,17 @@ void DcpScanRows::format(std::vector<dcp_walk_hit> const &hits)
         decode_rc_.compare_exchange_strong(expected, ld.rc);
         return;
       }
-      (*out)[k] = Row{j.at.profile, j.at.seq, j.at.window,
-                      format_row(batch_->seqs[(size_t)j.at.seq], j.at.window, j.at.start, j.at.stop, j.hit,
-                                 dcp_hip_profile_accession(eng_, j.at.profile), abc_.c_str(), j.at.lrt, j.steps,
-                                 ld.dec, &decode_rc_)};
+      out[k] = DcpProductRuns::Row{j.at.profile, j.at.seq, j.at.window, serial + (int64_t)k,
+                                   format_row(batch_->seqs[(size_t)j.at.seq], j.at.window, j.at.start, j.at.stop, j.hit,
+                                              dcp_hip_profile_accession(eng_, j.at.profile), abc_.c_str(), j.at.lrt,
+                                              j.steps, ld.dec, &decode_rc_)};
     });
+    if (decode_rc_) return; // (the scan fails: its rows are not written)
+    if (int const rc = runs_->add(std::move(out)))
+    {
+      int expected = 0;
+      decode_rc_.compare_exchange_strong(expected, rc);
+    }
   });
 }
 
@@ -194,27 +200,4 @@ int DcpScanRows::join()
   for (std::thread &t : threads_) t.join();
   threads_.clear();
   return decode_rc_;
-}
-
-int DcpScanRows::write(std::string const &file, std::vector<std::string> &products)
-{
-  std::vector<Row> rows;
-  for (std::vector<Row> &part : formatted_)
-    for (Row &r : part) rows.push_back(std::move(r));
-  std::stable_sort(rows.begin(), rows.end(), [](Row const &a, Row const &b) {
-    if (a.profile != b.profile) return a.profile < b.profile;
-    if (a.seq != b.seq) return a.seq < b.seq;
-    return a.window < b.window;
-  });
-  FILE *fp = fopen(file.c_str(), "wb");
-  if (!fp) return DCP_EFOPEN;
-  bool ok = fputs("sequence\twindow\twindow_start\twindow_stop\thit\thit_start\thit_stop\tprofile\tabc\tlrt\tevalue\tmatch\n",
-                  fp) >= 0;
-  products.reserve(rows.size());
-  for (Row &r : rows)
-  {
-    ok = ok && fwrite(r.text.data(), 1, r.text.size(), fp) == r.text.size() && fputc('\n', fp) != EOF;
-    products.push_back(std::move(r.text));
-  }
-  return fclose(fp) != 0 || !ok ? DCP_EWRITEPROD : 0;
 }

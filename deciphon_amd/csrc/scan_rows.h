@@ -6,8 +6,8 @@
 #include "../../include/deciphon_host.h"
 #include "dcp_db.h"
 #include "host_logic.h"
+#include "product_runs.h"
 #include <atomic>
-#include <deque>
 #include <future>
 #include <memory>
 #include <mutex>
@@ -30,12 +30,13 @@ struct dcp_batch
 
 // The rows of one dcp_scan_run.  Per path batch, in this order: warm_decoders, wait_steps_copied, dcp_hip_path, spans,
 // format.  Its threads read the batch's sequences, the scan's database and the engine -- the profiles' accessions, and
-// the step buffers of the last dcp_hip_path until they hold copies (wait_steps_copied) -- so it is declared after all
-// of them; its destructor joins the threads.
+// the step buffers of the last dcp_hip_path until they hold copies (wait_steps_copied) -- and hand their rows to
+// `runs`, so it is declared after all of them; its destructor joins the threads.
 class DcpScanRows
 {
 public:
-  DcpScanRows(dcp_hip const *eng, DcpDbReader const *db, int index_offset, char const *abc, dcp_batch const *batch);
+  DcpScanRows(dcp_hip const *eng, DcpDbReader const *db, int index_offset, char const *abc, dcp_batch const *batch,
+              DcpProductRuns *runs);
   ~DcpScanRows() { join(); }
   // decoder_setup (c-core/decoder.c:21-36) for the profiles of this batch -- reading a profile's distributions out of
   // the database and exponentiating them (a fraction of a millisecond, times hundreds of profiles with hits) -- by host
@@ -48,15 +49,18 @@ public:
   }
   // the hit spans of the n paths (c-core/thread.c:130-166): whether each holds a hit, and its last_hit_pos
   int spans(size_t n, std::vector<uint8_t> &is_hit, std::vector<int32_t> &last_hit_pos);
-  // the rows of these hits of the batch, formatted off the calling thread while the GPU goes on
+  // the rows of these hits of the batch, formatted off the calling thread while the GPU goes on and handed to `runs`
+  // by the formatter (which also writes them to a run file when they are beyond the budget: never this thread).  A
+  // row's serial -- batch number, then index in the batch -- is fixed here, whichever formatter finishes first.
   void format(std::vector<dcp_walk_hit> const &hits);
   // the decoders of profiles [first, last) go (a memo of (K + 3) * 1364 bytes each; the formatter jobs hold their own
   // references, and a profile that hits again makes a new one)
   void release_decoders(int first, int last);
-  // joins the formatters; 0, or the first error of quasi-codon decoding (c-core/match.c:66-89 fails the scan the same way)
+  // joins the formatters; 0, or the first error of quasi-codon decoding (c-core/match.c:66-89 fails the scan the same
+  // way) or of handing rows to `runs`
   int join();
-  // product_close (c-core/product.c:34-88): rows in profile, read, window order, to `file` and to `products`
-  int write(std::string const &file, std::vector<std::string> &products);
+  // product_close (c-core/product.c:34-88): rows in profile, read, window order, to `file`; they stay in `runs`
+  int write(std::string const &file) { return runs_->close(file); }
 
 private:
   // a decoder is handed out empty and filled by whichever thread needs it first
@@ -65,11 +69,6 @@ private:
     std::once_flag once;
     int rc = 0;
     DcpDecoder dec;
-  };
-  struct Row
-  {
-    int profile, seq, window;
-    std::string text;
   };
   struct Job
   {
@@ -88,9 +87,10 @@ private:
   int index_offset_;
   std::string abc_;
   dcp_batch const *batch_;
+  DcpProductRuns *runs_;
+  int64_t batches_ = 0;                                // with hits, so far
   std::vector<std::shared_ptr<LazyDecoder>> decoders_; // by local profile
   std::vector<Job> found_;                             // of the batch between spans and format
-  std::deque<std::vector<Row>> formatted_;             // one per batch; a deque: its formatter writes into the element
   std::future<void> steps_copied_;                     // of the last batch with hits
   std::atomic<int> decode_rc_{0};
   std::vector<std::thread> threads_;

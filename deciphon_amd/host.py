@@ -63,6 +63,17 @@ def _lib():
     L.dcp_scan_walk_take_queued.argtypes = [vp]
     for f in ("waiting", "take", "path_walked", "windows", "take_queued"):
         getattr(L, "dcp_scan_walk_" + f).restype = C.c_int64
+    L.dcp_product_runs_new.argtypes = [C.c_char_p, C.c_int64]
+    L.dcp_product_runs_new.restype = vp
+    L.dcp_product_runs_del.argtypes = [vp]
+    L.dcp_product_runs_del.restype = None
+    L.dcp_product_runs_add.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.dcp_product_runs_close.argtypes = [vp, C.c_char_p]
+    L.dcp_product_runs_num_rows.argtypes = [vp]
+    L.dcp_product_runs_num_rows.restype = C.c_long
+    L.dcp_product_runs_row.argtypes = [vp, C.c_long]
+    L.dcp_product_runs_row.restype = C.c_char_p
+    L.dcp_product_runs_stats.argtypes = [vp, vp]
     L.dcp_window_setup.argtypes = [C.POINTER(_Window), i32, i32]
     L.dcp_window_setup.restype = None
     L.dcp_window_next.argtypes = [C.POINTER(_Window)]
@@ -392,6 +403,58 @@ class ScanWalk:
 
     def take_queued(self) -> int:
         return int(self.lib.dcp_scan_walk_take_queued(self.h))
+
+
+PRODUCT_STATS = ("rows", "runs", "peak_bytes", "file_bytes")
+
+
+class ProductRuns:
+    """The product rows of a scan in bounded memory, without a GPU (include/deciphon_host.h dcp_product_runs_*; the
+    rules at csrc/product_runs.h): rows added in any order come out sorted by (profile, seq, window), equal keys in
+    the order they were added, through sorted run files in `directory` once more than `budget_bytes` of text are held."""
+
+    def __init__(self, directory, budget_bytes: int):
+        self.lib = _lib()
+        self.h = self.lib.dcp_product_runs_new(os.fsencode(directory), int(budget_bytes))
+        if not self.h:
+            raise HipError(8)
+
+    def add(self, profile, seq, window, texts) -> None:
+        """One call of add: rows (profile[i], seq[i], window[i], texts[i]), texts as bytes."""
+        p, s, w = (np.ascontiguousarray(a, np.int32) for a in (profile, seq, window))
+        assert len(p) == len(s) == len(w) == len(texts)
+        t = (C.c_char_p * len(texts))(*texts)
+        if rc := self.lib.dcp_product_runs_add(self.h, len(texts), p.ctypes.data_as(C.c_void_p),
+                                               s.ctypes.data_as(C.c_void_p), w.ctypes.data_as(C.c_void_p), t):
+            raise HipError(rc)
+
+    def close(self, file) -> None:
+        if rc := self.lib.dcp_product_runs_close(self.h, os.fsencode(file)):
+            raise HipError(rc)
+
+    def __len__(self):
+        return int(self.lib.dcp_product_runs_num_rows(self.h))
+
+    def row(self, i: int):
+        """Row i of the closed file as bytes, without its newline; None out of range."""
+        return self.lib.dcp_product_runs_row(self.h, int(i))
+
+    def stats(self) -> dict:
+        out = np.zeros(4, np.int64)
+        n = self.lib.dcp_product_runs_stats(self.h, out.ctypes.data_as(C.c_void_p))
+        assert n == len(PRODUCT_STATS)
+        return {k: int(v) for k, v in zip(PRODUCT_STATS, out)}
+
+    def free(self) -> None:
+        if getattr(self, "h", None):
+            self.lib.dcp_product_runs_del(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 def unzip(K: int, L: int, xnodes: np.ndarray, nodes: np.ndarray):

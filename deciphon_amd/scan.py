@@ -36,6 +36,7 @@ def _lib():
     L.dcp_scan_product.argtypes = [vp, C.c_long]
     L.dcp_scan_product.restype = C.c_char_p
     L.dcp_scan_last_timing.argtypes = [vp, C.POINTER(C.c_double), i32]
+    L.dcp_scan_product_stats.argtypes = [vp, C.POINTER(C.c_int64), i32]
     L.dcp_batch_new.restype = vp
     L.dcp_batch_del.argtypes = [vp]
     L.dcp_batch_del.restype = None
@@ -141,6 +142,15 @@ class Scan:
         n = self._lib.dcp_scan_last_timing(self._cscan, buf, len(keys))
         assert n == len(keys)
         return {k: (int(buf[i]) if i >= 7 else float(buf[i])) for i, k in enumerate(keys)}
+
+    def product_stats(self) -> dict:
+        """How the last run held its product rows (dcp_scan_product_stats): rows, run files written (0: every row
+        stayed in memory), the most bytes of row text held at once, and the bytes of products.tsv."""
+        keys = ("rows", "runs", "peak_bytes", "file_bytes")
+        buf = (C.c_int64 * len(keys))()
+        n = self._lib.dcp_scan_product_stats(self._cscan, buf, len(keys))
+        assert n == len(keys)
+        return {k: int(buf[i]) for i, k in enumerate(keys)}
 
     def interrupt(self):
         self.interrupted = True

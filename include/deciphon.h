@@ -23,6 +23,7 @@
 #define DECIPHON_AMD_DECIPHON_H
 
 #include <stdbool.h>
+#include <stdint.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -160,9 +161,18 @@ int dcp_scan_setup_partition(struct dcp_scan *, char const *dbfile, int device, 
 int dcp_scan_setup_partition_balanced(struct dcp_scan *, char const *dbfile, int device, int index, int nparts,
                                       bool multi_hits, bool hmmer3_compat, void (*callback)(void *), void *userdata);
 int dcp_scan_partition_range(struct dcp_scan const *, int *first, int *count);
-/* Number of product rows the last dcp_scan_run wrote, and row i (without newline). */
+/* Number of product rows the last dcp_scan_run wrote, and row i (without newline).  The pointer stands until the next
+ * dcp_scan_run or dcp_scan_del of that scan.  Once the scan has spilled rows to run files (dcp_scan_product_stats:
+ * runs > 0; DECIPHON_HIP_PRODUCT_MB) it stands only until the next dcp_scan_product on that scan, and
+ * dcp_scan_product is then not to be called from two threads at once. */
 long dcp_scan_num_products(struct dcp_scan const *);
 char const *dcp_scan_product(struct dcp_scan const *, long i);
+/* How the last dcp_scan_run held its product rows (csrc/product_runs.h).  Fills out[0..n) with, in order: the rows,
+ * the sorted run files written to the product directory and removed again (0: every row stayed in memory), the most
+ * bytes of row text held in memory at once, and the bytes of products.tsv.  Returns how many values exist
+ * (DCP_SCAN_PRODUCT_STATS_VALUES). */
+#define DCP_SCAN_PRODUCT_STATS_VALUES 4
+int dcp_scan_product_stats(struct dcp_scan const *, int64_t *out, int n);
 /* Where the wall time of the last dcp_scan_run went (measurement only; SURVEY 8d's wall definition: first H2D of the
  * reads to the last product row on the host).  Fills out[0..n) with, in order: total seconds, reads H2D + encode,
  * window bookkeeping, cost pass + LRT filter, path pass + unzip (the part the cost pass did not cover), row

@@ -139,6 +139,24 @@ int64_t dcp_scan_walk_path_walked(struct dcp_scan_walk *, uint8_t const *is_hit,
 int64_t dcp_scan_walk_windows(struct dcp_scan_walk const *);  /* walked so far */
 int64_t dcp_scan_walk_take_queued(struct dcp_scan_walk *);    /* queued for a cost round since the last call */
 
+/* ---- the product rows of a scan in bounded memory (csrc/product_runs.h: the rules), for tests.  Rows are handed over
+ * in any order and come out sorted by (profile, seq, window), equal keys in the order they were added; once more than
+ * budget_bytes of text are held they go to sorted run files `<dir>/.products.NNN.run`, which close merges into `file`
+ * behind the header line of products.tsv and removes.  add: n rows, text[i] NUL-terminated and without newline; 0,
+ * DCP_EOPENTMP, DCP_EWRITEPROD -- the first error sticks.  close: 0, that error, DCP_EFOPEN or DCP_EWRITEPROD.
+ * row: row i of the closed file without its newline, NULL out of range; once runs were written the pointer stands
+ * until the next row.  stats: rows, runs written, most text bytes held, bytes of `file`; returns 4.  del removes any
+ * run file still there. ---- */
+struct dcp_product_runs;
+struct dcp_product_runs *dcp_product_runs_new(char const *dir, int64_t budget_bytes);
+int dcp_product_runs_add(struct dcp_product_runs *, int n, int32_t const *profile, int32_t const *seq,
+                         int32_t const *window, char const *const *text);
+int dcp_product_runs_close(struct dcp_product_runs *, char const *file);
+long dcp_product_runs_num_rows(struct dcp_product_runs const *);
+char const *dcp_product_runs_row(struct dcp_product_runs *, long i);
+int dcp_product_runs_stats(struct dcp_product_runs const *, int64_t out[4]);
+void dcp_product_runs_del(struct dcp_product_runs *);
+
 /* ---- window iteration: window_setup / window_next / window_set_last_hit_position
  * (c-core/window.c:7-50) ---- */
 struct dcp_window
