@@ -6,6 +6,7 @@
 #include "../../deciphon_amd/csrc/traceback.h"
 
 thread_local long em_fallback_rows = 0;
+thread_local long em_row_range_zeros = 0;
 thread_local long em_votes = 0, em_votes_true = 0;
 
 template <int Q, int W>
@@ -55,6 +56,14 @@ extern "C" long emul_fallback_rows(void)
   return n;
 }
 
+// dwords of emission rows answered by the range rule of load_row_q since the last call (lane_ops_emul.h): the suites
+// assert 0 when they end
+extern "C" long emul_row_range_zeros(void)
+{
+  long const n = em_row_range_zeros;
+  em_row_range_zeros = 0;
+  return n;
+}
 
 // votes of the lazy D->D loops since the last call: out[0] = taken, out[1] = carried (one more turn each)
 extern "C" void emul_votes(long *out)

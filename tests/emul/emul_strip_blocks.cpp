@@ -6,6 +6,7 @@
 
 thread_local long em_votes = 0, em_votes_true = 0;
 thread_local long em_fallback_rows = 0;
+thread_local long em_row_range_zeros = 0;
 
 // f<Q, W>() for the shapes of emul_strip.cpp
 #define STRIP_SHAPES(pf, f, ...) \
@@ -30,4 +31,12 @@ extern "C" int emul_strip_replay_blocks(float const *pool, DcpProfileDev const *
                                         float const *xt, int B, int G, uint32_t *xnodes, uint16_t *nodes, float *score)
 {
   STRIP_SHAPES(pf, em_replay_blocks, pool, *pf, codes, L, xt, B, G, xnodes, nodes, score)
+}
+
+// dwords of emission rows answered by the range rule of load_row_q since the last call (lane_ops_emul.h)
+extern "C" long emul_row_range_zeros(void)
+{
+  long const n = em_row_range_zeros;
+  em_row_range_zeros = 0;
+  return n;
 }

@@ -25,12 +25,22 @@ struct lm { bool v[EM_MAX_LANES]; };
 
 #define EM_FOR for (int i_ = 0; i_ < em_lanes; ++i_)
 
+// min as v_min_f32 has it: the number beside a NaN, and -0 below +0 whatever the operand order.  (fminf of libm
+// returns one of two equal operands by their order, so the sign of a zero minimum depended on which lane came first.)
+inline float em_fminf(float a, float b)
+{
+  if (a != a) return b;
+  if (b != b) return a;
+  if (a == b) return signbit(a) ? a : b;
+  return a < b ? a : b;
+}
+
 inline lf lf_splat(float x) { lf r; EM_FOR r.v[i_] = x; return r; }
 inline lu lu_splat(uint32_t x) { lu r; EM_FOR r.v[i_] = x; return r; }
 inline lf operator+(lf a, lf b) { lf r; EM_FOR r.v[i_] = a.v[i_] + b.v[i_]; return r; }
 inline lf operator+(lf a, float b) { lf r; EM_FOR r.v[i_] = a.v[i_] + b; return r; }
 inline lf operator+(float a, lf b) { lf r; EM_FOR r.v[i_] = a + b.v[i_]; return r; }
-inline lf lmin(lf a, lf b) { lf r; EM_FOR r.v[i_] = fminf(a.v[i_], b.v[i_]); return r; }
+inline lf lmin(lf a, lf b) { lf r; EM_FOR r.v[i_] = em_fminf(a.v[i_], b.v[i_]); return r; }
 inline lf lmin3(lf a, lf b, lf c) { return lmin(lmin(a, b), c); }
 inline lm llt(lf a, lf b) { lm r; EM_FOR r.v[i_] = a.v[i_] < b.v[i_]; return r; }
 inline lm llt_u(lu a, lu b) { lm r; EM_FOR r.v[i_] = a.v[i_] < b.v[i_]; return r; }
@@ -68,7 +78,7 @@ inline lf lane_shift_up_keep(lf x, lf &keep)
 }
 inline lf lf_pin(float x) { return lf_splat(x); }
 
-inline float wave_min(lf v) { float m = v.v[0]; EM_FOR m = fminf(m, v.v[i_]); return m; }
+inline float wave_min(lf v) { float m = v.v[0]; EM_FOR m = em_fminf(m, v.v[i_]); return m; }
 inline uint32_t wave_minu(lu v) { uint32_t m = v.v[0]; EM_FOR m = v.v[i_] < m ? v.v[i_] : m; return m; }
 // votes taken / votes that carried since the last emul_votes() call (diagnostic: extra lazy D->D turns per row)
 extern thread_local long em_votes, em_votes_true;
@@ -88,6 +98,10 @@ enum { GS_M, GS_I, GS_D, GS_E, GS_F, GS_X, GS_T0, GS_T1, GS_X0, GS_X1, GS_SLOTS 
 // rows of the cost pass that took the exchange-until-stable fallback (tests read and reset it)
 template <int Q> struct DcpStashChunk { static constexpr int N = Q % 4 == 0 ? 4 : Q % 2 == 0 ? 2 : 1; }; // as lane_ops_gpu.h
 extern thread_local long em_fallback_rows; // defined in emul.cpp: one counter for every translation unit
+// dwords that load_row_q / load_row_chunks answered with 0 because they lie beyond the resource (the raw-buffer range
+// rule modelled below).  The emulator suites assert that it stays 0: no kernel reads a row past its resource, so what
+// the hardware returns there is relied on by nothing (tests read and reset it; defined beside em_fallback_rows)
+extern thread_local long em_row_range_zeros;
 
 template <int W> struct Group
 {
@@ -111,6 +125,7 @@ template <int W> struct Group
   }
   bool seg_any(lm m) { return wave_any(m); } // extra turns in a converged wave change nothing
   lm seg_first() { lm r; EM_FOR r.v[i_] = (i_ % 64) == 0; return r; }
+  lm last_lane() { lm r; EM_FOR r.v[i_] = (i_ % 64) == 63; return r; }
   // the sum of a wave's DD but the first, added in the order of lane_ops_gpu.h (put_tdd): every lane its own
   // positions, then a butterfly over the lanes -- the same fp32 value, so the same rows fall back here and there
   template <int Q> static float wave_tdd(lf const (&DD)[Q], int w)
@@ -138,7 +153,7 @@ template <int W> struct Group
     for (int w = 0; w < W; ++w)
     {
       float e = m_all.v[64 * w];
-      for (int i = 64 * w; i < 64 * w + 64; ++i) e = fminf(e, m_all.v[i]);
+      for (int i = 64 * w; i < 64 * w + 64; ++i) e = em_fminf(e, m_all.v[i]);
       rec[par][w] = Rec{m_last.v[64 * w + 63], i_last.v[64 * w + 63], d_last.v[64 * w + 63], e};
     }
   }
@@ -156,7 +171,7 @@ template <int W> struct Group
   void get_e_could(int par, float &E, bool &could)
   {
     float m = rec[par][0].e;
-    for (int w = 1; w < W; ++w) m = fminf(m, rec[par][w].e);
+    for (int w = 1; w < W; ++w) m = em_fminf(m, rec[par][w].e);
     bool any = false;
     for (int w = 0; w < W; ++w)
     {
@@ -191,8 +206,8 @@ template <int W> struct Group
   void get_e_could_row(int par, int s, float floor_e, float &E, bool &could)
   {
     float m = rec[par][0].e;
-    for (int w = 1; w < W; ++w) m = fminf(m, rec[par][w].e);
-    float const lo = fminf(m, floor_e);
+    for (int w = 1; w < W; ++w) m = em_fminf(m, rec[par][w].e);
+    float const lo = em_fminf(m, floor_e);
     bool any = false;
     for (int w = 0; w < W; ++w)
     {
@@ -241,7 +256,33 @@ template <int Q> inline void load_row_q(RowSrc const &r, lu voff, uint32_t soff,
     EM_FOR
     {
       uint32_t const at = soff + voff.v[i_] + 4u * (uint32_t)q;
-      out[q].v[i_] = at + 4u <= r.bytes ? *reinterpret_cast<float const *>(r.base + at) : 0.0f; // buffer range check
+      bool const in = at + 4u <= r.bytes; // buffer range check
+      if (!in) ++em_row_range_zeros;
+      out[q].v[i_] = in ? *reinterpret_cast<float const *>(r.base + at) : 0.0f;
+    }
+}
+
+// the same rows chunk by chunk, from the canonical rows or their cost-order copy (lane_ops_gpu.h: the emulated kernels
+// do not define DCP_COST_ORDER and read with load_row_q; tests/lanes compares these with the GPU's)
+template <int Q> struct DcpRowChunks
+{
+  static constexpr int N = (Q + 3) / 4;
+  static constexpr int width(int c) { return Q - 4 * c < 4 ? Q - 4 * c : 4; }
+};
+template <int Q, int W> inline void row_chunk_offsets(lu lane, bool ordered, lu (&v)[DcpRowChunks<Q>::N])
+{
+  for (int c = 0; c < DcpRowChunks<Q>::N; ++c)
+    EM_FOR v[c].v[i_] = dcp_row_lane_bytes(ordered ? DCP_ROW_COST_ORDER : DCP_ROW_CANON, Q, lane.v[i_], c);
+}
+template <int Q> inline void load_row_chunks(RowSrc const &r, lu const (&v)[DcpRowChunks<Q>::N], uint32_t soff, lf (&out)[Q])
+{
+  for (int q = 0; q < Q; ++q)
+    EM_FOR
+    {
+      uint32_t const at = soff + v[q / 4].v[i_] + 4u * (uint32_t)(q % 4);
+      bool const in = at + 4u <= r.bytes;
+      if (!in) ++em_row_range_zeros;
+      out[q].v[i_] = in ? *reinterpret_cast<float const *>(r.base + at) : 0.0f;
     }
 }
 
@@ -310,7 +351,7 @@ template <int S> inline lf group_min(lf v)
   for (int g = 0; g < 64 / S; ++g)
   {
     float m = v.v[g * S];
-    for (int i = g * S; i < g * S + S; ++i) m = fminf(m, v.v[i]);
+    for (int i = g * S; i < g * S + S; ++i) m = em_fminf(m, v.v[i]);
     for (int i = g * S; i < g * S + S; ++i) r.v[i] = m;
   }
   return r;
@@ -323,7 +364,7 @@ inline void add_quad0_x5(lf (&r)[5], lf const (&s)[5], lf const (&e)[5])
 template <int S> inline lf group_min01(lf v)
 {
   lf r;
-  EM_FOR r.v[i_] = fminf(v.v[i_ & ~(S - 1)], v.v[(i_ & ~(S - 1)) + 1]);
+  EM_FOR r.v[i_] = em_fminf(v.v[i_ & ~(S - 1)], v.v[(i_ & ~(S - 1)) + 1]);
   return r;
 }
 

@@ -19,7 +19,12 @@ from test_emul_kernels import PACK_SHAPES, _vp, run_pack, run_path
 @pytest.fixture(scope="module")
 def em():
     subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tests", "emul")], check=True)
-    return C.CDLL(os.path.join(ROOT, "tests", "emul", "libdcp_emul.so"))
+    lib = C.CDLL(os.path.join(ROOT, "tests", "emul", "libdcp_emul.so"))
+    yield lib
+    # no emulated kernel read a row beyond its resource: nothing relies on what the buffer range rule returns there
+    # (lane_ops_emul.h, em_row_range_zeros; DESIGN.md, "the two lane vocabularies")
+    lib.emul_row_range_zeros.restype = C.c_long
+    assert lib.emul_row_range_zeros() == 0
 
 
 def cost_on_shape(em, prof, Q, xt, seq):
