@@ -199,6 +199,42 @@ DCP_HDI uint32_t dcp_row_read_offset(int layout, int Q, int S, int K, uint32_t e
   return e == 0 ? 0u : dcp_row_lane_bytes(DCP_ROW_CANON, Q, dcp_row_source_lane(real, e - 1u), 0);
 }
 
+// ---- which XCD's L2 serves which windows of a cost launch ----------------------------------------------------
+// Workgroups are dealt round-robin over the 8 XCDs, each with its own 4 MiB L2: with the plain blockIdx -> problem
+// mapping the windows of one profile (neighbours in the profile-sorted list) land on all eight L2s, and every L2 holds
+// the table of every profile in flight.  The eighths give XCD x the x-th contiguous eighth of the list instead (the
+// bijective form for any n), so an L2 sees an eighth of the profiles.  A speed choice only: nothing depends on where a
+// workgroup runs.
+#define DCP_NUM_XCDS 8
+#define DCP_XCD_L2_BYTES (4LL << 20)
+DCP_HDI int dcp_xcd_eighths_entry(int b, int n)
+{
+  int const q = n >> 3, r = n & 7, x = b & 7;
+  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (b >> 3);
+}
+enum { DCP_PLACE_AUTO = -1, DCP_PLACE_PLAIN = 0, DCP_PLACE_EIGHTHS = 1 };
+// tables that meet in one L2 when `resident` workgroups, neighbours in a list of `windows_per_profile` windows of
+// each of `nprofiles` profiles, run beside each other: the run of a list that long touches that many profiles
+DCP_HDI long long dcp_xcd_tables_in_l2(long long resident, int windows_per_profile, int nprofiles)
+{
+  long long const t = resident / windows_per_profile + 1;
+  return t < nprofiles ? t : nprofiles;
+}
+// The rule, per launch of a cost kernel whose list is in profile order (a window's time depends on L alone there, so
+// the eighths are even in time): `workgroups` windows, `windows_per_profile` of them on average per profile,
+// `table_bytes` of emission rows per profile that the kernel reads, `resident_per_xcd` workgroups that one XCD holds
+// at the occupancy the kernel was compiled for.  In plain order the resident workgroups of the whole chip are one run
+// of the list and every L2 serves all its tables; in eighths an L2 serves the tables of its own XCD's run.  Eighths
+// when the former do not fit an L2 and the latter are fewer.
+DCP_HDI int dcp_xcd_placement(int workgroups, int windows_per_profile, long long table_bytes, int resident_per_xcd)
+{
+  if (workgroups < 1 || windows_per_profile < 1 || resident_per_xcd < 1) return DCP_PLACE_PLAIN;
+  int const nprofiles = (workgroups + windows_per_profile - 1) / windows_per_profile;
+  long long const plain = dcp_xcd_tables_in_l2((long long)DCP_NUM_XCDS * resident_per_xcd, windows_per_profile, nprofiles);
+  long long const eighths = dcp_xcd_tables_in_l2(resident_per_xcd, windows_per_profile, nprofiles);
+  return plain * table_bytes > DCP_XCD_L2_BYTES && eighths < plain ? DCP_PLACE_EIGHTHS : DCP_PLACE_PLAIN;
+}
+
 // where the traceback of one window stands between blocks (all zero = not started)
 struct DcpTraceState
 {

@@ -253,11 +253,14 @@ int stage(dcp_hip *x, int n, dcp_hip_window const *w, ArenaKind arena_kind, Stag
   for (int c = 0; c < DCP_NUM_CLASSES; ++c)
   {
     st.c_begin[c] = i;
+    st.c_profiles[c][0] = st.c_profiles[c][1] = 0;
+    // (the list is in profile order inside either part: a profile is one run of it)
+    auto const starts_run = [&](int j) { return j == st.c_begin[c] || st.problems[(size_t)j].profile != st.problems[(size_t)j - 1].profile; };
     while (i < nu && x->profiles[(size_t)st.problems[(size_t)i].profile].cls == c &&
            x->profiles[(size_t)st.problems[(size_t)i].profile].narrow)
-      ++i;
+      st.c_profiles[c][0] += starts_run(i), ++i;
     st.c_wide[c] = i;
-    while (i < nu && x->profiles[(size_t)st.problems[(size_t)i].profile].cls == c) ++i;
+    while (i < nu && x->profiles[(size_t)st.problems[(size_t)i].profile].cls == c) st.c_profiles[c][1] += starts_run(i), ++i;
   }
   st.c_begin[DCP_NUM_CLASSES] = i;
   if (i != nu) return fail(x, DCP_ELARGECORESIZE, "profile outside every kernel class");
@@ -338,6 +341,15 @@ int launch_cost_all(dcp_hip *x, StagedPlan const &st, hipStream_t origin, int re
   for (int s = 0; s < DCP_NUM_PACK_SHAPES; ++s) kernels += st.pk_begin[s + 1] > st.pk_begin[s];
   char const *narrow_env = getenv("DECIPHON_HIP_NARROW");
   bool const narrow = !(narrow_env && narrow_env[0] == '0');
+  // DECIPHON_HIP_XCD_PLACEMENT=plain | eighths: every class's cost kernel that way (measurements, tests); auto, or
+  // not set: dcp_xcd_placement decides per launch
+  int placement = DCP_PLACE_AUTO;
+  if (char const *e = getenv("DECIPHON_HIP_XCD_PLACEMENT"))
+  {
+    if (!strcmp(e, "plain")) placement = DCP_PLACE_PLAIN;
+    else if (!strcmp(e, "eighths")) placement = DCP_PLACE_EIGHTHS;
+    else if (strcmp(e, "auto")) return fail(x, DCP_EFUNCUSE, "DECIPHON_HIP_XCD_PLACEMENT is not plain, eighths or auto");
+  }
   for (int c = 4; narrow && c < DCP_NUM_CLASSES; ++c) kernels += st.c_wide[c] > st.c_begin[c];
   // x->stream joins the kernels only after the last launch (Fork::join): a wait is a barrier in x->stream's hardware
   // queue, and a stream that shares that queue would start its kernel behind every barrier issued before
@@ -355,6 +367,7 @@ int launch_cost_all(dcp_hip *x, StagedPlan const &st, hipStream_t origin, int re
     DcpLaunch b = launch_args(x, st, c);
     if (b.nprob <= 0) continue;
     if ((rc = fk.enter(x->cls_branch[c], b))) return rc;
+    b.placement = placement;
     // the windows that fit with one position per lane less (dcp_class_narrow_limit) lead the class's list and have
     // their own kernel, on its own stream.  DECIPHON_HIP_NARROW=0: the class's kernel for all (tests compare).
     int const nn = narrow ? st.c_wide[c] - st.c_begin[c] : 0;
@@ -362,6 +375,7 @@ int launch_cost_all(dcp_hip *x, StagedPlan const &st, hipStream_t origin, int re
     {
       DcpLaunch n = b;
       n.nprob = nn;
+      n.windows_per_profile = nn / st.c_profiles[c][0];
       if ((rc = fk.enter(x->narrow_branch[c], n))) return rc;
       for (int r = 0; r < reps; ++r) HIP_TRY(x, dcp_launch_cost_narrow(c, n), DCP_EFUNCUSE);
       if ((rc = fk.leave(x->narrow_branch[c]))) return rc;
@@ -369,7 +383,12 @@ int launch_cost_all(dcp_hip *x, StagedPlan const &st, hipStream_t origin, int re
       b.nprob -= nn;
     }
     if (b.nprob > 0)
+    {
+      // all of the class's windows in one launch (no narrow kernel, or none wanted): both parts' profiles
+      int const np = st.c_profiles[c][1] + (nn > 0 ? 0 : st.c_profiles[c][0]);
+      b.windows_per_profile = b.nprob / np;
       for (int r = 0; r < reps; ++r) HIP_TRY(x, dcp_launch_cost(c, b), DCP_EFUNCUSE);
+    }
     if ((rc = fk.leave(x->cls_branch[c]))) return rc;
   }
   if (fused)

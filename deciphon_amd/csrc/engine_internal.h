@@ -195,6 +195,7 @@ struct StagedPlan
 {
   int c_begin[DCP_NUM_CLASSES + 1] = {0}; // problems of class c are [c_begin[c], c_begin[c+1])
   int c_wide[DCP_NUM_CLASSES] = {0};      // ... the narrow profiles' first: [c_begin[c], c_wide[c])
+  int c_profiles[DCP_NUM_CLASSES][2] = {{0}}; // profiles with a window among the narrow ones, and among the rest
   int pk_begin[DCP_NUM_PACK_SHAPES + 1] = {0};
   int pg_begin[DCP_NUM_PACK_SHAPES + 1] = {0};
   double cells = 0;

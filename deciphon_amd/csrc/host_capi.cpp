@@ -128,6 +128,13 @@ int dcp_row_lane_offsets(int layout, int Q, int S, int K, uint32_t *offsets)
   return dcp_row_read_lanes(layout, Q, S, K);
 }
 
+int dcp_xcd_eighths_entry_of(int b, int n) { return b < 0 || b >= n ? -1 : dcp_xcd_eighths_entry(b, n); }
+
+int dcp_xcd_placement_of(int workgroups, int windows_per_profile, int64_t table_bytes, int resident_per_xcd)
+{
+  return dcp_xcd_placement(workgroups, windows_per_profile, (long long)table_bytes, resident_per_xcd);
+}
+
 int dcp_partition_bounds_of(int n, int32_t const *core_sizes, int nparts, int balanced, int32_t *first)
 {
   if (n < 0 || !first || (balanced && n > 0 && !core_sizes)) return DCP_EFUNCUSE;

@@ -36,6 +36,11 @@ struct DcpLaunch
   float *ring = nullptr;         // device: strip class only, DCP_RING_SLOTS x DCP_RING_FLOATS
   int nprob;
   hipStream_t stream;
+  // cost pass of a class (dcp_launch_cost, dcp_launch_cost_narrow): which windows share an XCD's L2 (dcp_types.h).
+  // DCP_PLACE_AUTO: dcp_xcd_placement decides from windows_per_profile, the mean over the profiles of `problems`
+  // (0: not known, the plain order); DCP_PLACE_PLAIN / DCP_PLACE_EIGHTHS: as told.  The other launches do not read them.
+  int windows_per_profile = 0;
+  int placement = DCP_PLACE_AUTO;
 };
 
 hipError_t dcp_launch_cost(int cls, DcpLaunch const &a);

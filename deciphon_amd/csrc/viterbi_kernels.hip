@@ -22,22 +22,14 @@ template <class T> __device__ __forceinline__ T *dcp_global(uintptr_t address)
   return (T *)(__attribute__((address_space(1))) T *)address;
 }
 
-// Workgroups are dealt round-robin over the 8 XCDs, each with its own 4 MiB L2 (MI355X_MICROARCH.md, Workgroup
-// dispatch): with the plain blockIdx -> problem mapping the windows of one profile (neighbours in the sorted
-// problem list) land on all eight L2s and every L2 holds the tables of every profile in flight.  This gives
-// XCD x the x-th contiguous eighth of the list instead (the bijective form for any grid size), so an L2 sees
-// an eighth of the profiles.  A speed choice only: nothing depends on where a workgroup runs.
-__device__ __forceinline__ int dcp_xcd_remap_any(int b, int n)
-{
-  int const q = n >> 3, r = n & 7, x = b & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (b >> 3);
-}
-__device__ __forceinline__ int dcp_xcd_remap(int b, int n)
-{
-  // a launch of about one generation of wavefronts keeps the plain order: there the eighths would be uneven in
-  // time (windows of different profiles take different time) with nothing left to even them out
-  return n < 16384 ? b : dcp_xcd_remap_any(b, n);
-}
+// Which list entry a workgroup takes (dcp_types.h, "which XCD's L2 serves which windows"): dcp_xcd_eighths_entry, under
+// the names the kernels have always used.  The cost kernels of a class take the eighths or the plain order as the host
+// decided for the launch (DcpLaunch::placement, dcp_xcd_placement).
+__device__ __forceinline__ int dcp_xcd_remap_any(int b, int n) { return dcp_xcd_eighths_entry(b, n); }
+// The fused kernel and the packs: a launch of about one generation of wavefronts keeps the plain order.  Their lists
+// are not even in time (the fused kernel's windows belong to profiles of different classes, a shape's packs go
+// longest first inside a profile), and in a small launch nothing is left to even the eighths out.
+__device__ __forceinline__ int dcp_xcd_remap(int b, int n) { return n < 16384 ? b : dcp_xcd_remap_any(b, n); }
 // The path pass's kernels take the eighths whatever the size of the launch: all their wavefronts are resident at once
 // (nothing to even out), and what they wait for is memory -- the 2301 hit windows of the headline scan fetch 140 GB of
 // emission rows and write 66 GB of tables in 50 ms (scripts/pmc_path.sh).  With the windows of a profile on one XCD
@@ -62,14 +54,14 @@ __global__ __launch_bounds__(64 * W, WAVES) void dcp_cost_kernel(float const *__
                                                       DcpProblem const *__restrict__ problems,
                                                       DcpCodeRow const *__restrict__ code_rows,
                                                       float const *__restrict__ xt_table,
-                                                      float *__restrict__ out, int nprob)
+                                                      float *__restrict__ out, int nprob, int eighths)
 {
   if ((int)blockIdx.x >= nprob) return;
 #ifdef DCP_EXP_LDSPAD // timing experiment (profiles/r02_exp_*): LDS nobody uses holds the wavefronts per SIMD down
   __shared__ float pad[DCP_EXP_LDSPAD / 4];
   if (nprob < 0) out[0] = pad[threadIdx.x];
 #endif
-  int const p = dcp_xcd_remap((int)blockIdx.x, nprob);
+  int const p = eighths ? dcp_xcd_remap_any((int)blockIdx.x, nprob) : (int)blockIdx.x;
   DcpProblem const pb = problems[p];
   DcpProfileDev const pf = profiles[pb.profile];
   CostWave<Q, W, false, POLICY> w;
@@ -595,11 +587,41 @@ hipError_t dcp_launch_unzip(DcpLaunch const &a, uint32_t *steps, int64_t const *
   return hipGetLastError();
 }
 
+// Workgroups of dcp_cost_kernel<Q, W> that one XCD holds at the occupancy the kernel was compiled for (asked of the
+// runtime once per kernel and device: registers and LDS decide it, not the launch bounds alone)
+template <int Q, int W, int POLICY, int WAVES> static hipError_t cost_resident_per_xcd(int *resident)
+{
+  static thread_local int cached_dev = -1, cached = 0;
+  int dev = 0, per_cu = 0, cus = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  if (dev != cached_dev)
+  {
+    if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dcp_cost_kernel<Q, W, POLICY, WAVES>, 64 * W, 0)) != hipSuccess)
+      return e;
+    if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
+    cached = per_cu * cus / DCP_NUM_XCDS;
+    cached_dev = dev;
+  }
+  *resident = cached;
+  return hipSuccess;
+}
+
 template <int Q, int W, int POLICY = DCP_COST_POLICY(Q, W), int WAVES = DCP_COST_WAVES(Q, W)>
 static hipError_t launch_cost_qw(DcpLaunch const &a)
 {
+  int place = a.placement;
+  if (place == DCP_PLACE_AUTO)
+  {
+    // the rows the kernel reads: the first 64 Q W columns behind the header, of each of the 1364 codes
+    long long const table_bytes = (long long)DCP_TABLE_SIZE * (64 * Q * W + DCP_ROW_HDR) * 4;
+    int resident = 0;
+    hipError_t const e = cost_resident_per_xcd<Q, W, POLICY, WAVES>(&resident);
+    if (e != hipSuccess) return e;
+    place = dcp_xcd_placement(a.nprob, a.windows_per_profile, table_bytes, resident);
+  }
   hipLaunchKernelGGL((dcp_cost_kernel<Q, W, POLICY, WAVES>), dim3((unsigned)a.nprob), dim3(64 * W), 0, a.stream, a.pool,
-                     a.profiles, a.problems, a.code_rows, a.xt_table, a.out, a.nprob);
+                     a.profiles, a.problems, a.code_rows, a.xt_table, a.out, a.nprob, place == DCP_PLACE_EIGHTHS ? 1 : 0);
   return hipGetLastError();
 }
 

@@ -302,6 +302,28 @@ def row_lane_offsets(layout: int, Q: int, S: int, K: int):
     return real, off
 
 
+def xcd_eighths_entry(b: int, n: int) -> int:
+    """the entry of a list of n that workgroup b of a cost launch takes under the eighths (csrc/dcp_types.h
+    dcp_xcd_eighths_entry): XCD b % 8 walks the (b % 8)-th contiguous eighth of the list"""
+    L = _lib()
+    L.dcp_xcd_eighths_entry_of.argtypes = [C.c_int, C.c_int]
+    e = int(L.dcp_xcd_eighths_entry_of(int(b), int(n)))
+    if e < 0:
+        raise ValueError(f"no workgroup {b} in a launch of {n}")
+    return e
+
+
+PLACE_PLAIN, PLACE_EIGHTHS = 0, 1
+
+
+def xcd_placement(workgroups: int, windows_per_profile: int, table_bytes: int, resident_per_xcd: int) -> int:
+    """PLACE_PLAIN or PLACE_EIGHTHS: what a cost launch of that many windows in profile order does when nothing
+    forces it (csrc/dcp_types.h dcp_xcd_placement)"""
+    L = _lib()
+    L.dcp_xcd_placement_of.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int]
+    return int(L.dcp_xcd_placement_of(int(workgroups), int(windows_per_profile), int(table_bytes), int(resident_per_xcd)))
+
+
 def plan_chunks(core_sizes, read_lengths, first_cells: float, later_cells: float, max_pairs: int, max_windows: int):
     """dcp_scan_run's cost batches: (chunks int32[n][4] = (p0, p1, s0, s1), windows int64[n]) -- profiles [p0, p1)
     x reads [s0, s1) -- for profiles and reads of these sizes (csrc/host_logic.h dcp_plan_chunks)."""

@@ -90,6 +90,13 @@ int dcp_cost_order_map(int Q, int W, int32_t *cols);
  * position below K (layout 2: the separator not counted), or 0 with nothing written for a shape no kernel has
  * (Q < 1, Q > 16, K < 1, K beyond the shape's positions, S not 4, 8, 16 or 32). */
 int dcp_row_lane_offsets(int layout, int Q, int S, int K, uint32_t *offsets);
+/* Which windows of a cost launch share an XCD's L2 (csrc/dcp_types.h).  dcp_xcd_eighths_entry_of: the entry of a list
+ * of n that workgroup b takes when XCD x = b % 8 is given the x-th contiguous eighth of the list (-1 unless
+ * 0 <= b < n).  dcp_xcd_placement_of: the rule itself, 1 = eighths, 0 = the plain order, for a launch of `workgroups`
+ * windows in profile order, windows_per_profile of them per profile, table_bytes of emission rows per profile, on a
+ * kernel of which one XCD holds resident_per_xcd workgroups. */
+int dcp_xcd_eighths_entry_of(int b, int n);
+int dcp_xcd_placement_of(int workgroups, int windows_per_profile, int64_t table_bytes, int resident_per_xcd);
 /* How dcp_scan_run cuts profiles x reads into cost batches (csrc/host_logic.h dcp_plan_chunks: the rules).
  * dcp_scan_run plans with first_cells = DCP_SCAN_FIRST_CHUNK_CELLS, later_cells = unlimited (both
  * DECIPHON_HIP_CHUNK_CELLS when that is set), max_pairs = DCP_SCAN_CHUNK_PAIRS and max_windows =

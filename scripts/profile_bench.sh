@@ -1,6 +1,7 @@
 #!/bin/bash
 # Runs on the GPU box (via gpurun): rocprofv3 kernel trace + separate PMC passes of bench.py.
 # Usage: scripts/profile_bench.sh <tag> [bench args...]; results land in gpurun_out/<tag>/
+# PROFILE_PASSES="1 3 4": only those of the PMC passes below (default: all six); the kernel trace always runs.
 set -u
 TAG=${1:-prof}; shift || true
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}
@@ -17,7 +18,8 @@ for PMC in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_ANY SQ_ACTIVE_
            "FETCH_SIZE" "WRITE_SIZE" \
            "TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum TCP_PENDING_STALL_CYCLES_sum TCP_TA_TCP_STATE_READ_sum"; do
   i=$((i+1))
-  timeout -k 10 300 rocprofv3 --pmc $PMC --output-format csv -d "$OUT/pmc$i" -- python3 "$ROOT/bench.py" $ARGS > "$OUT/pmc$i.log" 2>&1 || echo "pmc pass $i failed" >> "$OUT/errors.log"
+  case " ${PROFILE_PASSES:-1 2 3 4 5 6} " in *" $i "*) ;; *) continue ;; esac
+  timeout -k 10 300 rocprofv3 --pmc $PMC --output-format csv -d "$OUT/pmc$i" -- python3 "$ROOT/bench.py" $ARGS > "$OUT/pmc$i.log" 2>&1 || { echo "pmc pass $i failed" >> "$OUT/errors.log"; exit 1; } # nothing more on the GPU behind a pass that failed
 done
 python3 "$ROOT/scripts/summarize_prof.py" "$OUT" > "$OUT/summary.txt" 2>&1
 cat "$OUT/summary.txt"
