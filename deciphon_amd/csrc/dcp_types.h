@@ -48,6 +48,22 @@ struct DcpProfileDev
 };
 #define DCP_COST_SHAPE(Q, W) ((Q) * 256 + (W))
 #define DCP_COST_ORDER_HDR 32 // floats in front of the columns of a cost-order row: { null, bg, 0, 0 }, +inf to 128 bytes
+#ifdef __HIPCC__
+#define DCP_HDI __host__ __device__ inline
+#else
+#define DCP_HDI inline
+#endif
+// where position k of a profile lies among the columns of a cost-order row of shape (Q, W) -- the map itself is
+// described at host_logic.h, "the cost-order copy"; stated here, once, for the host and for the kernel that writes the
+// copy on the device (press_rows.hip)
+DCP_HDI int dcp_cost_order_col(int Q, int W, int k)
+{
+  (void)W;
+  int const g = k / Q, q = k % Q, w = g / 64, e = g % 64, c = q / 4;
+  int const wc = Q - 4 * c < 4 ? Q - 4 * c : 4;
+  return 64 * Q * w + 256 * c + e * wc + (q - 4 * c);
+}
+DCP_HDI int dcp_cost_order_stride(int Q, int W) { return DCP_COST_ORDER_HDR + 64 * Q * W; }
 
 // One (profile x sequence-window) DP problem.
 struct DcpProblem
@@ -79,11 +95,6 @@ struct DcpPack
 // j (block 0 from row 0) over rows j*B + 1 .. min(L, (j+1)*B + 5) into a table of B + 6 rows (row l at slot
 // l - j*B), and the traceback walks the part of the path whose stage lies in (j*B + 5, (j+1)*B + 5] -- every
 // row it reads there, stage - 5 .. stage, is in the block's table -- before handing over to block j - 1.
-#ifdef __HIPCC__
-#define DCP_HDI __host__ __device__ inline
-#else
-#define DCP_HDI inline
-#endif
 #define DCP_CKPT_ROWS_DEFAULT 500
 #define DCP_CKPT_SP 6 // lane rows of specials per checkpoint: Spre[5], X
 DCP_HDI long long dcp_ckpt_floats(int Kp, int W) { return 10LL * Kp + (long long)DCP_CKPT_SP * 64 * W; } // W waves per window

@@ -1,6 +1,11 @@
 // engine_profiles.cpp -- the engine's profiles: add, load, commit, clear, and the cost-order staging.
 #include "engine_internal.h"
+#include "engine_hmm.h"
 #include "parallel_for.h"
+#include "press_batch.h"
+#include "press_rows.h"
+
+#include <limits.h>
 
 extern "C" {
 
@@ -13,6 +18,13 @@ static size_t canonical_floats(int Kp)
 {
   size_t const floats = (size_t)DCP_TABLE_SIZE * ((size_t)Kp + DCP_ROW_HDR) + (size_t)DCP_NUM_TRANS * (size_t)Kp;
   return (floats + 31) & ~(size_t)31;
+}
+
+// the floats of that rounding, behind trans: +inf wherever a profile is staged, so that a pool's words depend on its
+// profiles alone
+static size_t canonical_tables(int Kp)
+{
+  return (size_t)DCP_TABLE_SIZE * ((size_t)Kp + DCP_ROW_HDR) + (size_t)DCP_NUM_TRANS * (size_t)Kp;
 }
 
 static size_t profile_floats(HostProfile const &hp)
@@ -76,15 +88,16 @@ static int describe(dcp_hip *x, int K, char const *accession, HostProfile &hp)
   return 0;
 }
 
-// grows the device pool to `floats`, keeping what is resident
-static int ensure_pool(dcp_hip *x, size_t floats)
+// grows the device pool to `floats`, keeping what is resident (and, during a load that has written behind it, the
+// first `keep` floats)
+static int ensure_pool(dcp_hip *x, size_t floats, size_t keep = 0)
 {
+  keep = std::max(keep, x->pool_used);
   if (floats <= x->d_pool.cap) return 0;
   HIP_TRY(x, hipStreamSynchronize(x->stream), DCP_EFUNCUSE);
   DevBuf<float> bigger;
   HIP_TRY(x, bigger.reserve(std::max(floats, x->d_pool.cap + x->d_pool.cap / 2)), DCP_ENOMEM);
-  if (x->pool_used)
-    HIP_TRY(x, hipMemcpy(bigger.p, x->d_pool.p, x->pool_used * sizeof(float), hipMemcpyDeviceToDevice), DCP_EFUNCUSE);
+  if (keep) HIP_TRY(x, hipMemcpy(bigger.p, x->d_pool.p, keep * sizeof(float), hipMemcpyDeviceToDevice), DCP_EFUNCUSE);
   x->d_pool.release();
   x->d_pool.p = bigger.p;
   x->d_pool.cap = bigger.cap;
@@ -260,6 +273,7 @@ int dcp_hip_load_dcp(struct dcp_hip *x, char const *path, int first, int count)
         int expected = 0;
         bad.compare_exchange_strong(expected, DCP_EFDATA); // a positive delete log-probability
       }
+      std::fill(rows + canonical_tables(hps[(size_t)i].Kp), rows + canonical_floats(hps[(size_t)i].Kp), INFINITY);
       stage_cost_order(hps[(size_t)i], rows);
     });
     if (bad)
@@ -289,6 +303,268 @@ int dcp_hip_load_dcp(struct dcp_hip *x, char const *path, int first, int count)
   }
   x->pool_used += off[(size_t)n];
   ++x->gen;
+  return 0;
+}
+
+} // extern "C"
+
+// ---- from a HMMER3 file: the tables are made on the device and stay there ---------------------------------
+// Profiles are parsed into batches as press does (press_batch.h).  Per batch, queued on the engine's stream: the
+// nodes' distributions and the host-made transitions go up, the emission kernel (press_kernel.hip) writes the
+// node-major tables into a scratch buffer of the slot, and the rows kernel (press_rows.hip) writes every profile's rows,
+// cost-order copy and transitions into its slice of the pool.  Two slots: the host parses batch b + 1 while the GPU
+// works on b.  Nothing comes back, and the profiles are published to the engine only when the whole range is in.
+namespace
+{
+
+struct HmmSlot : DcpPressBatch
+{
+  PinBuf<float> h_in, h_trans;
+  PinBuf<DcpRowsDesc> h_desc;
+  DevBuf<float> d_in, d_em, d_trans;
+  DevBuf<DcpRowsDesc> d_desc;
+  hipEvent_t ev[4] = {}; // before the uploads, after them, after the emission kernel, after the rows kernel
+  bool launched = false;
+  ~HmmSlot()
+  {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
+struct HmmLoad
+{
+  dcp_hip *x;
+  float epsilon;
+  HmmSlot slot[2];
+  PinBuf<float> h_models;            // the null model and the background: two entries in ...
+  DevBuf<float> d_models, d_nullbg;  // ... and their tables, null[1364] then bg[1364]
+  size_t used;                       // floats of the pool written so far, the resident profiles included
+  std::vector<HostProfile> added;
+  bool poison;
+  double t_parse = 0, t_upload = 0, t_emission = 0, t_rows = 0, t_wait = 0, t_grow = 0;
+  int grown = 0; // times the pool was reallocated during the load
+  HmmLoad(dcp_hip *x_, float eps) : x(x_), epsilon(eps), used(x_->pool_used)
+  {
+    char const *e = getenv("DECIPHON_HIP_COST_ORDER");
+    poison = e && strcmp(e, "poison") == 0;
+  }
+  ~HmmLoad() { (void)hipStreamSynchronize(x->stream); } // before the slots' buffers go
+
+  int models(DcpHmmReader const &reader)
+  {
+    HIP_TRY(x, h_models.reserve(2 * DCP_PRESS_IN_STRIDE), DCP_ENOMEM);
+    HIP_TRY(x, d_models.reserve(2 * DCP_PRESS_IN_STRIDE), DCP_ENOMEM);
+    HIP_TRY(x, d_nullbg.reserve(2 * DCP_PRESS_TABLE), DCP_ENOMEM);
+    dcp_press_put_entry(h_models.p, reader.null_dist());
+    dcp_press_put_entry(h_models.p + DCP_PRESS_IN_STRIDE, reader.bg_dist());
+    HIP_TRY(x, hipMemcpyAsync(d_models.p, h_models.p, 2 * DCP_PRESS_IN_STRIDE * sizeof(float), hipMemcpyHostToDevice, x->stream),
+            DCP_EFUNCUSE);
+    if (dcp_press_emission_launch(d_models.p, d_nullbg.p, 2, epsilon, x->stream))
+      return fail(x, DCP_EFUNCUSE, "the emission kernel could not be launched");
+    for (HmmSlot &s : slot)
+      for (hipEvent_t &e : s.ev) HIP_TRY(x, hipEventCreate(&e), DCP_ENOMEM);
+    return 0;
+  }
+
+  // the pool holds `floats`; a reallocation waits for the stream and copies what is written (timed apart)
+  int grow(size_t floats)
+  {
+    if (floats <= x->d_pool.cap) return 0;
+    auto const t0 = std::chrono::steady_clock::now();
+    int const rc = ensure_pool(x, floats, used);
+    t_grow += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    ++grown;
+    return rc;
+  }
+
+  // The pool is sized once, from the lengths the file's LENG lines announce for profiles [first, first + count): the
+  // load then never reallocates, and nothing is held twice.  Only an estimate -- a file whose LENG lines are not one
+  // per profile is not sized by them -- so launch() still grows the pool where it falls short.
+  int presize(DcpHmmReader const &reader, long first, long count)
+  {
+    std::vector<long> const &len = reader.announced_lengths();
+    if ((long)len.size() != reader.count()) return 0;
+    long const last = count < 0 ? (long)len.size() : std::min((long)len.size(), first + count);
+    size_t floats = 0;
+    for (long i = first; i < last; ++i)
+    {
+      HostProfile hp;
+      if (len[(size_t)i] < 1 || len[(size_t)i] >= DCP_MODEL_MAX) return 0; // the load will fail there
+      if (describe(x, (int)len[(size_t)i], nullptr, hp)) return 0;
+      floats += profile_floats(hp);
+    }
+    return floats ? grow(used + floats) : 0;
+  }
+
+  // the slot's batch is through: its buffers are free again
+  int wait(HmmSlot &s)
+  {
+    if (!s.launched) return 0;
+    s.launched = false;
+    auto const t0 = std::chrono::steady_clock::now();
+    HIP_TRY(x, hipEventSynchronize(s.ev[3]), DCP_EFUNCUSE);
+    t_wait += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    float ms[3] = {0, 0, 0};
+    for (int i = 0; i < 3; ++i) HIP_TRY(x, hipEventElapsedTime(&ms[i], s.ev[i], s.ev[i + 1]), DCP_EFUNCUSE);
+    t_upload += ms[0] * 1e-3;
+    t_emission += ms[1] * 1e-3;
+    t_rows += ms[2] * 1e-3;
+    return 0;
+  }
+
+  // describes the profiles of the slot's batch, builds their transitions and queues the batch
+  int launch(HmmSlot &s, DcpHmmSink *sink)
+  {
+    size_t const n = s.profiles.size();
+    std::vector<HostProfile> hps(n);
+    std::vector<size_t> off(n + 1, 0), toff(n + 1, 0);
+    int max_Kp = 0;
+    for (size_t i = 0; i < n; ++i)
+    {
+      if (int rc = describe(x, s.profiles[i].core_size, s.profiles[i].accession.c_str(), hps[i])) return rc;
+      off[i + 1] = off[i] + profile_floats(hps[i]);
+      toff[i + 1] = toff[i] + (canonical_floats(hps[i].Kp) - (size_t)DCP_TABLE_SIZE * ((size_t)hps[i].Kp + DCP_ROW_HDR));
+      max_Kp = std::max(max_Kp, hps[i].Kp);
+    }
+    size_t const entries = (size_t)s.entries;
+    HIP_TRY(x, s.h_in.reserve(entries * DCP_PRESS_IN_STRIDE), DCP_ENOMEM);
+    HIP_TRY(x, s.d_in.reserve(entries * DCP_PRESS_IN_STRIDE), DCP_ENOMEM);
+    HIP_TRY(x, s.d_em.reserve(entries * DCP_PRESS_TABLE), DCP_ENOMEM);
+    HIP_TRY(x, s.h_trans.reserve(toff[n]), DCP_ENOMEM);
+    HIP_TRY(x, s.d_trans.reserve(toff[n]), DCP_ENOMEM);
+    HIP_TRY(x, s.h_desc.reserve(n), DCP_ENOMEM);
+    HIP_TRY(x, s.d_desc.reserve(n), DCP_ENOMEM);
+    s.put_entries(s.h_in.p);
+    for (size_t i = 0; i < n; ++i)
+    {
+      HostProfile &hp = hps[i];
+      DcpHmmProfile const &p = s.profiles[i];
+      float *t = s.h_trans.p + toff[i];
+      std::fill(t, s.h_trans.p + toff[i + 1], INFINITY);
+      dcp_setup_trans(hp.K, hp.Kp, p.trans.data(), p.BMk.data(), t);
+      if (!delete_costs_ok(t, hp.K, hp.Kp)) return fail(x, DCP_EFDATA, "positive (or NaN) delete log-probability in the profile");
+      hp.pool_off = (int64_t)(used + off[i]);
+      DcpRowsDesc &d = s.h_desc.p[i];
+      d.src = s.first[i];
+      d.rows_off = hp.pool_off;
+      d.trans_off = hp.pool_off + (int64_t)DCP_TABLE_SIZE * (hp.Kp + DCP_ROW_HDR);
+      d.trans_src = (int64_t)toff[i];
+      d.copy_off = hp.pool_off + (int64_t)canonical_floats(hp.Kp);
+      d.K = hp.K;
+      d.Kp = hp.Kp;
+      d.stride = hp.Kp + DCP_ROW_HDR;
+      d.trans_floats = (int32_t)(toff[i + 1] - toff[i]);
+      d.cQ = hp.cQ;
+      d.poison = hp.cQ && poison;
+    }
+    if (int rc = grow(used + off[n])) return rc;
+    hipStream_t const q = x->stream;
+    HIP_TRY(x, hipEventRecord(s.ev[0], q), DCP_EFUNCUSE);
+    HIP_TRY(x, hipMemcpyAsync(s.d_in.p, s.h_in.p, entries * DCP_PRESS_IN_STRIDE * sizeof(float), hipMemcpyHostToDevice, q), DCP_EFUNCUSE);
+    HIP_TRY(x, hipMemcpyAsync(s.d_trans.p, s.h_trans.p, toff[n] * sizeof(float), hipMemcpyHostToDevice, q), DCP_EFUNCUSE);
+    HIP_TRY(x, hipMemcpyAsync(s.d_desc.p, s.h_desc.p, n * sizeof(DcpRowsDesc), hipMemcpyHostToDevice, q), DCP_EFUNCUSE);
+    HIP_TRY(x, hipEventRecord(s.ev[1], q), DCP_EFUNCUSE);
+    if (dcp_press_emission_launch(s.d_in.p, s.d_em.p, (int)entries, epsilon, q))
+      return fail(x, DCP_EFUNCUSE, "the emission kernel could not be launched");
+    HIP_TRY(x, hipEventRecord(s.ev[2], q), DCP_EFUNCUSE);
+    if (dcp_press_rows_launch(s.d_em.p, d_nullbg.p, d_nullbg.p + DCP_PRESS_TABLE, s.d_trans.p, s.d_desc.p, (int)n, max_Kp,
+                              x->d_pool.p, q))
+      return fail(x, DCP_EFUNCUSE, "the rows kernel could not be launched");
+    HIP_TRY(x, hipEventRecord(s.ev[3], q), DCP_EFUNCUSE);
+    s.launched = true;
+    used += off[n];
+    if (sink)
+      for (DcpHmmProfile const &p : s.profiles) sink->profile(p);
+    added.insert(added.end(), hps.begin(), hps.end());
+    return 0;
+  }
+};
+
+} // namespace
+
+int dcp_hip_load_hmm_sink(struct dcp_hip *x, char const *hmm, int gencode_id, float epsilon, int first, int count,
+                          DcpHmmSink *sink)
+{
+  if (!x || !hmm) return DCP_EFUNCUSE;
+  if (outstanding_batches(x)) return refuse_outstanding(x);
+  {
+    DcpNucltDist probe;
+    float const zero[20] = {};
+    if (!dcp_setup_nuclt_dist(gencode_id, zero, probe)) return fail(x, DCP_EGENCODEID, "unknown translation table");
+  }
+  if (!(epsilon >= 0.0f && epsilon <= 1.0f)) return fail(x, DCP_EFUNCUSE, "epsilon must lie in [0, 1]");
+  if (FILE *f = fopen(hmm, "rb")) fclose(f);
+  else return fail(x, DCP_EOPENHMM, "cannot open the HMMER3 file");
+  HIP_TRY(x, hipSetDevice(x->device), DCP_EFUNCUSE);
+  DcpHmmReader reader;
+  int rc = reader.open(hmm, gencode_id);
+  if (rc) return fail(x, rc, "cannot read the HMMER3 file");
+  // a `first` out of range is reported after what reading the file reports: everything is then in front of it
+  bool const bad_first = first < 0 || (long)first > reader.count();
+  long skip = bad_first ? LONG_MAX : first, limit = bad_first || count < 0 ? -1 : count;
+
+  HmmLoad load(x, epsilon);
+  if ((rc = load.models(reader))) return rc;
+  if (!bad_first && (rc = load.presize(reader, first, count))) return rc;
+  if (sink) sink->models(reader.null_dist(), reader.bg_dist());
+  DcpPressFeeder feeder;
+  feeder.batch_nodes = dcp_press_batch_nodes();
+  for (int b = 0;; b ^= 1)
+  {
+    HmmSlot &s = load.slot[b];
+    if ((rc = load.wait(s))) break;
+    auto const t0 = std::chrono::steady_clock::now();
+    feeder.fill(reader, s, &skip, &limit);
+    if (!s.profiles.empty()) rc = load.launch(s, sink);
+    load.t_parse += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (rc) break;
+    if (s.rc_after)
+    {
+      rc = fail(x, s.rc_after, "cannot read a profile of the HMMER3 file");
+      break;
+    }
+    if (s.eof_after) break;
+  }
+  for (HmmSlot &s : load.slot)
+    if (int const wrc = load.wait(s))
+      if (!rc) rc = wrc;
+  if (!rc) HIP_TRY(x, hipStreamSynchronize(x->stream), DCP_EFUNCUSE); // (the null and background tables of an empty range)
+  if (!rc && bad_first) rc = fail(x, DCP_EINVALPART, "first profile out of range");
+  if (rc) return rc; // nothing of this load is kept: pool_used and the profiles are what they were
+  if (getenv("DECIPHON_HIP_TIMING"))
+    fprintf(stderr,
+            "dcp_hip_load_hmm: %zu profiles, %.3f GB of tables; parse %.3f s, upload %.6f s, emission kernel %.6f s, "
+            "rows kernel %.6f s, wait %.3f s; pool grown %d times in %.3f s (of parse)\n",
+            load.added.size(), (double)(load.used - x->pool_used) * 4e-9, load.t_parse, load.t_upload, load.t_emission,
+            load.t_rows, load.t_wait, load.grown, load.t_grow);
+  x->profiles.insert(x->profiles.end(), load.added.begin(), load.added.end());
+  x->pool_used = load.used;
+  ++x->gen;
+  return 0;
+}
+
+extern "C" {
+
+int dcp_hip_load_hmm(struct dcp_hip *x, char const *hmm, int gencode_id, float epsilon, int first, int count)
+{
+  return dcp_hip_load_hmm_sink(x, hmm, gencode_id, epsilon, first, count, nullptr);
+}
+
+int64_t dcp_hip_profile_floats(struct dcp_hip const *x, int i)
+{
+  if (!x || i < 0 || i >= (int)x->profiles.size()) return -1;
+  return (int64_t)profile_floats(x->profiles[(size_t)i]);
+}
+
+int dcp_hip_profile_read(struct dcp_hip const *x, int i, float *out, int64_t n)
+{
+  if (!x || !out || i < 0 || i >= (int)x->profiles.size()) return DCP_EFUNCUSE;
+  HostProfile const &hp = x->profiles[(size_t)i];
+  if (n != (int64_t)profile_floats(hp)) return DCP_EFUNCUSE;
+  // (every load has waited for its own copies and kernels before it returned)
+  if (hipSetDevice(x->device) != hipSuccess) return DCP_EFUNCUSE;
+  if (hipMemcpy(out, x->d_pool.p + hp.pool_off, (size_t)n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return DCP_EFUNCUSE;
   return 0;
 }
 

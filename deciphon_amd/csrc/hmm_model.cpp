@@ -155,6 +155,7 @@ void DcpHmmReader::close()
   buf_ = nullptr;
   cap_ = 0;
   count_ = 0;
+  lengths_.clear();
   end_ = false;
 }
 
@@ -173,7 +174,10 @@ int DcpHmmReader::open(char const *path, int gencode_id)
   if (!path || !(fp_ = fopen(path, "rb"))) return DCP_EFOPEN;
   // press.c: count_proteins
   while (line())
+  {
     if (!line_.compare(0, 8, "HMMER3/f")) ++count_;
+    else if (!line_.compare(0, 5, "LENG ")) lengths_.push_back(atol(line_.c_str() + 5));
+  }
   if (ferror(fp_))
   {
     close();

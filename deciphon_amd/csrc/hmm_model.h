@@ -54,6 +54,9 @@ public:
   void close();
   // press.c: count_proteins -- the number of lines that begin with "HMMER3/f", counted at open
   long count() const { return count_; }
+  // what the LENG lines announce, in file order, from the same pass at open: what a caller sizes its buffers by
+  // before the first profile is parsed (an estimate: next() is what validates a profile)
+  std::vector<long> const &announced_lengths() const { return lengths_; }
   // Reads the next profile into `out`.  At the end of the file it returns 0 and end() becomes true.
   int next(DcpHmmProfile &out);
   bool end() const { return end_; }
@@ -70,6 +73,7 @@ private:
   size_t cap_ = 0;
   std::string line_;
   long count_ = 0;
+  std::vector<long> lengths_;
   bool end_ = false;
   int gencode_ = 0;
   float null_lprobs_[20] = {};

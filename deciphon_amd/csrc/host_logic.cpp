@@ -60,6 +60,12 @@ void dcp_xtrans(int seq_size, bool multi_hits, bool hmmer3_compat, float xt[DCP_
 void dcp_setup_profile(int K, int Kp, float const *node_trans, float const *node_emission, float const *BMk,
                        float const *null_lprob, float const *bg_lprob, float *trans, float *rows)
 {
+  dcp_setup_trans(K, Kp, node_trans, BMk, trans);
+  dcp_setup_rows(K, Kp, node_emission, null_lprob, bg_lprob, rows);
+}
+
+void dcp_setup_trans(int K, int Kp, float const *node_trans, float const *BMk, float *trans)
+{
   for (size_t i = 0; i < (size_t)DCP_NUM_TRANS * Kp; ++i) trans[i] = INFINITY; // viterbi_setup fills +inf
   for (int k = 0; k < K; ++k) trans[DCP_BM * Kp + k] = -BMk[k];
   for (int k = 0; k + 1 < K; ++k)
@@ -75,6 +81,10 @@ void dcp_setup_profile(int K, int Kp, float const *node_trans, float const *node
   }
   trans[DCP_MI * Kp + K - 1] = INFINITY;
   trans[DCP_II * Kp + K - 1] = INFINITY;
+}
+
+void dcp_setup_rows(int K, int Kp, float const *node_emission, float const *null_lprob, float const *bg_lprob, float *rows)
+{
   // node-major [k][code] on disk -> code-major [code][k] rows for the kernels
   size_t const stride = (size_t)Kp + DCP_ROW_HDR;
   for (int c = 0; c < DCP_TABLE_SIZE; ++c)
@@ -88,16 +98,6 @@ void dcp_setup_profile(int K, int Kp, float const *node_trans, float const *node
     for (int k = K; k < Kp; ++k) row[k] = INFINITY;
   }
 }
-
-int dcp_cost_order_col(int Q, int W, int k)
-{
-  (void)W;
-  int const g = k / Q, q = k % Q, w = g / 64, e = g % 64, c = q / 4;
-  int const wc = Q - 4 * c < 4 ? Q - 4 * c : 4;
-  return 64 * Q * w + 256 * c + e * wc + (q - 4 * c);
-}
-
-int dcp_cost_order_stride(int Q, int W) { return DCP_COST_ORDER_HDR + 64 * Q * W; }
 
 void dcp_cost_order_rows(int Q, int W, int K, int Kp, float const *rows, float *copy)
 {

@@ -15,6 +15,10 @@ void dcp_xtrans(int seq_size, bool multi_hits, bool hmmer3_compat, float xt[DCP_
 // rows[1364][DCP_ROW_HDR + Kp] = { null, bg, 0, 0, match[0..Kp) }.
 void dcp_setup_profile(int K, int Kp, float const *node_trans, float const *node_emission, float const *BMk,
                        float const *null_lprob, float const *bg_lprob, float *trans, float *rows);
+// its two halves: the transitions (a few KB, always made on the host) and the rows (made on the host from a pressed
+// file, by press_rows.hip on the device from a HMMER3 file -- the same values)
+void dcp_setup_trans(int K, int Kp, float const *node_trans, float const *BMk, float *trans);
+void dcp_setup_rows(int K, int Kp, float const *node_emission, float const *null_lprob, float const *bg_lprob, float *rows);
 
 // ---- the cost-order copy of the emission rows (CostWave, viterbi_body.h) ----
 // The cost kernels of Q >= 5 positions per lane read a lane's Q floats of a row in chunks of four (b128, and a
@@ -25,8 +29,7 @@ void dcp_setup_profile(int K, int Kp, float const *node_trans, float const *node
 // { null, bg, 0, 0 } padded with +inf to 32 floats, then the Kp' = 64*Q*W columns: dcp_cost_order_stride = 32 + Kp'
 // floats, so every row and its column block start on a 128-byte line, and the header sits at the row's offset as in
 // the canonical rows (no extra scalar add per emission length).  Q <= 4 is the identity; no copy for those shapes.
-int dcp_cost_order_col(int Q, int W, int k);
-int dcp_cost_order_stride(int Q, int W);
+// (dcp_cost_order_col and dcp_cost_order_stride themselves: dcp_types.h, shared with the device)
 // copy[1364][dcp_cost_order_stride(Q, W)] from canonical rows[1364][DCP_ROW_HDR + Kp], Kp >= 64*Q*W; the columns
 // are +inf beyond position K
 void dcp_cost_order_rows(int Q, int W, int K, int Kp, float const *rows, float *copy);

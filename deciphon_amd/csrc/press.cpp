@@ -15,6 +15,7 @@
 #include "dcp_errors.h"
 #include "dcp_types.h"
 #include "hmm_model.h"
+#include "press_batch.h"
 #include "press_kernel.h"
 
 #include <hip/hip_runtime.h>
@@ -30,8 +31,6 @@
 #include <sys/stat.h>
 #include <unistd.h>
 #include <vector>
-
-#define DCP_PRESS_BATCH_NODES 16384 // per launch (DECIPHON_HIP_PRESS_BATCH_NODES); a longer profile goes alone
 
 namespace
 {
@@ -128,16 +127,12 @@ int write_all(int fd, void const *data, size_t n)
   return 0;
 }
 
-struct Slot
+struct Slot : DcpPressBatch
 {
-  std::vector<DcpHmmProfile> profiles;
-  std::vector<int64_t> first; // entry of each profile's node 0
-  int64_t entries = 0, cap = 0;
+  int64_t cap = 0;
   float *h_in = nullptr, *h_out = nullptr, *d_in = nullptr, *d_out = nullptr;
   hipEvent_t ev[4] = {}; // before upload, after upload, after the kernel, after the copy-back
   bool launched = false, waited = true;
-  int rc_after = 0;       // the reader's error on the profile after these
-  bool eof_after = false; // the file ends after these
   void release()
   {
     if (h_in) (void)hipHostFree(h_in);
@@ -169,12 +164,10 @@ struct dcp_press
   // GPU
   int device = 0;
   hipStream_t stream = nullptr;
-  int64_t batch_nodes = DCP_PRESS_BATCH_NODES;
+  DcpPressFeeder feeder; // batch by batch out of `reader`
   Slot slots[2];
   int cur = 0;     // the slot next() takes profiles from
   size_t pos = 0;  // next profile of it
-  DcpHmmProfile pending; // parsed, did not fit the batch it was read for
-  bool have_pending = false;
   std::vector<float> null_table, bg_table;
   Pack rec;
   double timing[DCP_PRESS_TIMING_VALUES] = {0};
@@ -216,13 +209,6 @@ int reserve(Slot &s, int64_t n)
   return 0;
 }
 
-void put_entry(float *in, DcpNucltDist const &d)
-{
-  memcpy(in, d.nucltp, sizeof d.nucltp);
-  memcpy(in + 4, d.codonm, sizeof d.codonm);
-  in[129] = in[130] = in[131] = 0.0f;
-}
-
 // uploads the slot's s.entries inputs (already in h_in), computes their tables and copies them back, all queued
 int launch(dcp_press *x, Slot &s)
 {
@@ -260,50 +246,9 @@ int wait(dcp_press *x, Slot &s)
 int fill(dcp_press *x, Slot &s)
 {
   double const t0 = now();
-  s.profiles.clear();
-  s.first.clear();
-  s.entries = 0;
-  s.rc_after = 0;
-  s.eof_after = false;
-  for (;;)
-  {
-    DcpHmmProfile p;
-    if (x->have_pending)
-    {
-      p = std::move(x->pending);
-      x->have_pending = false;
-    }
-    else
-    {
-      int const rc = x->reader.next(p);
-      if (rc)
-      {
-        s.rc_after = rc;
-        break;
-      }
-      if (x->reader.end())
-      {
-        s.eof_after = true;
-        break;
-      }
-    }
-    if (!s.profiles.empty() && s.entries + p.core_size > x->batch_nodes)
-    {
-      x->pending = std::move(p);
-      x->have_pending = true;
-      break;
-    }
-    s.first.push_back(s.entries);
-    s.entries += p.core_size;
-    s.profiles.push_back(std::move(p));
-  }
+  x->feeder.fill(x->reader, s);
   if (int rc = reserve(s, s.entries)) return rc;
-  for (size_t i = 0; i < s.profiles.size(); ++i)
-  {
-    DcpHmmProfile const &p = s.profiles[i];
-    for (int n = 0; n < p.core_size; ++n)
-      put_entry(s.h_in + (size_t)(s.first[i] + n) * DCP_PRESS_IN_STRIDE, p.nodes[(size_t)n]);
-  }
+  s.put_entries(s.h_in);
   x->timing[0] += now() - t0;
   return launch(x, s);
 }
@@ -421,7 +366,7 @@ int release(dcp_press *x, bool keep_db)
   x->tmp_fd = x->db_fd = -1;
   x->tmp_path.clear();
   x->reader.close();
-  x->have_pending = false;
+  x->feeder.have_pending = false;
   x->state = dcp_press::IDLE;
   return rc;
 }
@@ -468,8 +413,7 @@ int dcp_press_open(struct dcp_press *x, char const *hmm, char const *db)
   if (hipGetDeviceProperties(&prop, x->device) != hipSuccess || strncmp(prop.gcnArchName, "gfx950", 6) != 0)
     return raise(DCP_EFUNCUSE, __func__, "the HIP device is not a gfx950");
   if (hipSetDevice(x->device) != hipSuccess) return raise(DCP_EFUNCUSE, __func__, "hipSetDevice failed");
-  x->batch_nodes = DCP_PRESS_BATCH_NODES;
-  if (char const *b = getenv("DECIPHON_HIP_PRESS_BATCH_NODES")) x->batch_nodes = atol(b) > 0 ? atol(b) : 1;
+  x->feeder.batch_nodes = dcp_press_batch_nodes();
 
   for (double &t : x->timing) t = 0;
   x->end = false;
@@ -502,8 +446,8 @@ int dcp_press_open(struct dcp_press *x, char const *hmm, char const *db)
   if (!rc) rc = reserve(s, 2);
   if (!rc)
   {
-    put_entry(s.h_in, x->reader.null_dist());
-    put_entry(s.h_in + DCP_PRESS_IN_STRIDE, x->reader.bg_dist());
+    dcp_press_put_entry(s.h_in, x->reader.null_dist());
+    dcp_press_put_entry(s.h_in + DCP_PRESS_IN_STRIDE, x->reader.bg_dist());
     s.entries = 2;
     rc = launch(x, s);
   }

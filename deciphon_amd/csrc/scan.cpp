@@ -16,6 +16,8 @@
 #include "../../include/deciphon_host.h"
 #include "dcp_db.h"
 #include "dcp_errors.h"
+#include "engine_hmm.h"
+#include "hmm_model.h"
 #include "host_logic.h"
 #include "scan_rows.h"
 #include "scan_walk.h"
@@ -50,7 +52,9 @@ struct dcp_scan
   std::string abc_name = "dna";
   std::unique_ptr<DcpProductRuns> runs; // the rows of the last dcp_scan_run (dcp_scan_product), until the next one
   double timing[DCP_SCAN_TIMING_VALUES] = {0}; // dcp_scan_last_timing
-  std::unique_ptr<DcpDbReader> db; // stays mapped: the rows read the distributions of the profiles with hits from it
+  // the rows read the distributions of the profiles with hits from it: the database, which stays mapped, or what a
+  // load from a HMMER3 file left in memory
+  std::unique_ptr<DcpDecoderSource> db;
 };
 
 namespace
@@ -97,6 +101,37 @@ struct Phase
   }
 };
 
+// a fresh engine on `device`, with HBM set aside for the path pass
+int new_engine(dcp_scan *x, int device)
+{
+  if (x->eng) dcp_hip_del(x->eng);
+  x->eng = dcp_hip_new(device);
+  if (!x->eng) return DCP_EFUNCUSE;
+  x->device = device;
+  {
+    // HBM for the path pass's DP tables, first: VRAM is cleared on allocation, in the background,
+    // and the clearing then overlaps the database load and the first cost pass.  Best effort:
+    // dcp_hip_path allocates what it needs anyway.  16 GB (never more than a quarter of what is free) hold the
+    // tables of ~8000 hit windows of a median profile at once: the path pass of a scan's first hits is then one slice.
+    char const *mb = getenv("DECIPHON_HIP_PATH_BUDGET_MB");
+    (void)dcp_hip_path_reserve(x->eng, mb ? (int64_t)std::max(atol(mb), 1L) << 20 : (int64_t)16 << 30);
+  }
+  return 0;
+}
+
+// the last step of every setup, the profiles resident
+int set_mode(dcp_scan *x, char const *func, bool multi_hits, bool hmmer3_compat, void (*callback)(void *), void *userdata)
+{
+  if (int const rc = dcp_hip_set_mode(x->eng, multi_hits, hmmer3_compat)) return raise(rc, func);
+  x->multi_hits = multi_hits;
+  x->hmmer3_compat = hmmer3_compat;
+  x->callback = callback;
+  x->userdata = userdata;
+  x->interrupted = false;
+  x->done_proteins = 0;
+  return 0;
+}
+
 int setup_common(dcp_scan *x, char const *dbfile, int device, int index, int nparts, bool balanced, bool multi_hits,
                  bool hmmer3_compat, void (*callback)(void *), void *userdata)
 {
@@ -136,34 +171,19 @@ int setup_common(dcp_scan *x, char const *dbfile, int device, int index, int npa
     x->index_offset = first[(size_t)index];
     x->num_proteins = first[(size_t)index + 1] - first[(size_t)index];
   }
-  x->db.reset(new DcpDbReader);
-  if ((rc = x->db->open(dbfile))) return raise(rc, __func__, dbfile);
-  if (x->eng) dcp_hip_del(x->eng);
-  x->eng = dcp_hip_new(device);
-  if (!x->eng) return raise(DCP_EFUNCUSE, __func__, "no usable HIP device (there is no CPU fallback)");
-  x->device = device;
   {
-    // HBM for the path pass's DP tables, first: VRAM is cleared on allocation, in the background,
-    // and the clearing then overlaps the database load and the first cost pass.  Best effort:
-    // dcp_hip_path allocates what it needs anyway.  16 GB (never more than a quarter of what is free) hold the
-    // tables of ~8000 hit windows of a median profile at once: the path pass of a scan's first hits is then one slice.
-    char const *mb = getenv("DECIPHON_HIP_PATH_BUDGET_MB");
-    (void)dcp_hip_path_reserve(x->eng, mb ? (int64_t)std::max(atol(mb), 1L) << 20 : (int64_t)16 << 30);
+    std::unique_ptr<DcpDbDecoders> mapped(new DcpDbDecoders);
+    if ((rc = mapped->db.open(dbfile))) return raise(rc, __func__, dbfile);
+    x->db = std::move(mapped);
   }
+  if ((rc = new_engine(x, device))) return raise(rc, __func__, "no usable HIP device (there is no CPU fallback)");
   if (x->num_proteins > 0)
   {
     if ((rc = dcp_hip_load_dcp(x->eng, dbfile, x->index_offset, x->num_proteins)))
       return raise(rc, __func__, dcp_hip_strerror(x->eng));
     if ((rc = dcp_hip_commit_profiles(x->eng))) return raise(rc, __func__, dcp_hip_strerror(x->eng));
   }
-  if ((rc = dcp_hip_set_mode(x->eng, multi_hits, hmmer3_compat))) return raise(rc, __func__);
-  x->multi_hits = multi_hits;
-  x->hmmer3_compat = hmmer3_compat;
-  x->callback = callback;
-  x->userdata = userdata;
-  x->interrupted = false;
-  x->done_proteins = 0;
-  return 0;
+  return set_mode(x, __func__, multi_hits, hmmer3_compat, callback, userdata);
 }
 
 
@@ -347,6 +367,37 @@ int dcp_scan_setup_partition_balanced(struct dcp_scan *x, char const *dbfile, in
                                       bool multi_hits, bool hmmer3_compat, void (*callback)(void *), void *userdata)
 {
   return setup_common(x, dbfile, device, index, nparts, true, multi_hits, hmmer3_compat, callback, userdata);
+}
+
+int dcp_scan_setup_hmm(struct dcp_scan *x, char const *hmm, int gencode_id, float epsilon, bool multi_hits,
+                       bool hmmer3_compat, void (*callback)(void *), void *userdata)
+{
+  if (!x || !hmm) return raise(DCP_EFUNCUSE, __func__);
+  // the arguments first, in the order of dcp_hip_load_hmm: without a GPU they are still told apart
+  {
+    DcpNucltDist probe;
+    float const zero[20] = {};
+    if (!dcp_setup_nuclt_dist(gencode_id, zero, probe)) return raise(DCP_EGENCODEID, __func__);
+  }
+  if (!(epsilon >= 0.0f && epsilon <= 1.0f)) return raise(DCP_EFUNCUSE, __func__, "epsilon must lie in [0, 1]");
+  if (FILE *f = fopen(hmm, "rb")) fclose(f);
+  else return raise(DCP_EOPENHMM, __func__, hmm);
+  int device = 0;
+  if (char const *d = getenv("DECIPHON_HIP_DEVICE")) device = atoi(d);
+  if (new_engine(x, device)) return raise(DCP_EFUNCUSE, __func__, "no usable HIP device (there is no CPU fallback)");
+  std::unique_ptr<DcpHmmDecoders> kept(new DcpHmmDecoders);
+  kept->gencode = gencode_id;
+  kept->epsilon = epsilon;
+  x->db.reset();
+  x->abc_name = "dna"; // what press writes
+  x->index_offset = 0;
+  x->num_proteins = 0;
+  int rc = dcp_hip_load_hmm_sink(x->eng, hmm, gencode_id, epsilon, 0, -1, kept.get());
+  if (rc) return raise(rc, __func__, dcp_hip_strerror(x->eng)); // (what the sink was shown goes with `kept`)
+  if ((rc = dcp_hip_commit_profiles(x->eng))) return raise(rc, __func__, dcp_hip_strerror(x->eng));
+  x->num_proteins = dcp_hip_num_profiles(x->eng);
+  x->db = std::move(kept);
+  return set_mode(x, __func__, multi_hits, hmmer3_compat, callback, userdata);
 }
 
 int dcp_scan_partition_range(struct dcp_scan const *x, int *first, int *count)

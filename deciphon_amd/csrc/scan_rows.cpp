@@ -4,6 +4,7 @@
 #include "parallel_for.h"
 #include <algorithm>
 #include <stdio.h>
+#include <string.h>
 
 namespace
 {
@@ -90,7 +91,27 @@ std::string format_row(dcp_batch::Seq const &seq, int window, int wstart, int ws
 
 } // namespace
 
-DcpScanRows::DcpScanRows(dcp_hip const *eng, DcpDbReader const *db, int index_offset, char const *abc,
+int DcpHmmDecoders::read_decoder(int i, DcpDecoder &x) const
+{
+  if (i < 0 || (size_t)i >= nodes.size()) return DCP_EINVALPART;
+  std::vector<DcpNucltDist> const &nd = nodes[(size_t)i];
+  size_t const K = nd.size();
+  x.gencode = gencode;
+  x.core_size = (int)K;
+  x.epsilon = epsilon;
+  x.nucltp.resize((K + 3) * 4);
+  x.codonm.resize((K + 3) * 125);
+  for (size_t e = 0; e < K + 3; ++e)
+  {
+    DcpNucltDist const &d = e == 0 ? null : e == 1 ? bg : nd[std::min(e - 2, K - 1)];
+    memcpy(x.nucltp.data() + 4 * e, d.nucltp, sizeof d.nucltp);
+    memcpy(x.codonm.data() + 125 * e, d.codonm, sizeof d.codonm);
+  }
+  x.prepare();
+  return 0;
+}
+
+DcpScanRows::DcpScanRows(dcp_hip const *eng, DcpDecoderSource const *db, int index_offset, char const *abc,
                          dcp_batch const *batch, DcpProductRuns *runs)
     : eng_(eng), db_(db), index_offset_(index_offset), abc_(abc), batch_(batch), runs_(runs),
       decoders_((size_t)std::max(dcp_hip_num_profiles(eng), 0))

@@ -5,6 +5,7 @@
 #include "../../include/deciphon_hip.h"
 #include "../../include/deciphon_host.h"
 #include "dcp_db.h"
+#include "engine_hmm.h"
 #include "host_logic.h"
 #include "product_runs.h"
 #include <atomic>
@@ -28,14 +29,43 @@ struct dcp_batch
   std::vector<Seq> seqs;
 };
 
+// Where the rows take a profile's distributions from: "fill a DcpDecoder for profile i" (global index), entries in the
+// order of the pressed file -- 0 = null, 1 = background, 2 + n = node n, node K repeating node K - 1 -- with the scan's
+// translation table and error rate, prepare()d.  0 or a DCP_E* code; called from several threads at once.
+struct DcpDecoderSource
+{
+  virtual ~DcpDecoderSource() = default;
+  virtual int read_decoder(int i, DcpDecoder &out) const = 0;
+};
+
+// the mapped database of a scan set up from a pressed file
+struct DcpDbDecoders : DcpDecoderSource
+{
+  DcpDbReader db;
+  int read_decoder(int i, DcpDecoder &out) const override { return db.read_decoder(i, out); }
+};
+
+// A scan set up from a HMMER3 file (dcp_scan_setup_hmm) has no file to read them back from: it keeps the fp32 nucltp
+// and codonm of every node, 516 bytes each, as the load shows them (engine_hmm.h).
+struct DcpHmmDecoders : DcpDecoderSource, DcpHmmSink
+{
+  int gencode = 0;
+  float epsilon = 0;
+  DcpNucltDist null{}, bg{};
+  std::vector<std::vector<DcpNucltDist>> nodes; // by profile: [K]
+  void models(DcpNucltDist const &n, DcpNucltDist const &b) override { null = n, bg = b; }
+  void profile(DcpHmmProfile const &p) override { nodes.emplace_back(p.nodes.begin(), p.nodes.begin() + p.core_size); }
+  int read_decoder(int i, DcpDecoder &out) const override;
+};
+
 // The rows of one dcp_scan_run.  Per path batch, in this order: warm_decoders, wait_steps_copied, dcp_hip_path, spans,
-// format.  Its threads read the batch's sequences, the scan's database and the engine -- the profiles' accessions, and
+// format.  Its threads read the batch's sequences, the scan's decoder source and the engine -- the profiles' accessions, and
 // the step buffers of the last dcp_hip_path until they hold copies (wait_steps_copied) -- and hand their rows to
 // `runs`, so it is declared after all of them; its destructor joins the threads.
 class DcpScanRows
 {
 public:
-  DcpScanRows(dcp_hip const *eng, DcpDbReader const *db, int index_offset, char const *abc, dcp_batch const *batch,
+  DcpScanRows(dcp_hip const *eng, DcpDecoderSource const *db, int index_offset, char const *abc, dcp_batch const *batch,
               DcpProductRuns *runs);
   ~DcpScanRows() { join(); }
   // decoder_setup (c-core/decoder.c:21-36) for the profiles of this batch -- reading a profile's distributions out of
@@ -83,7 +113,7 @@ private:
   void fill(LazyDecoder &ld, int profile) const;
 
   dcp_hip const *eng_;
-  DcpDbReader const *db_;
+  DcpDecoderSource const *db_;
   int index_offset_;
   std::string abc_;
   dcp_batch const *batch_;

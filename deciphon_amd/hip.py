@@ -53,6 +53,10 @@ def load_library() -> C.CDLL:
     L.dcp_hip_add_profile.argtypes = [vp, i32, vp, vp, vp, vp, C.POINTER(i32)]
     L.dcp_hip_add_protein.argtypes = [vp, i32, vp, vp, vp, vp, vp, C.POINTER(i32)]
     L.dcp_hip_load_dcp.argtypes = [vp, C.c_char_p, i32, i32]
+    L.dcp_hip_load_hmm.argtypes = [vp, C.c_char_p, i32, C.c_float, i32, i32]
+    L.dcp_hip_profile_floats.argtypes = [vp, i32]
+    L.dcp_hip_profile_floats.restype = C.c_int64
+    L.dcp_hip_profile_read.argtypes = [vp, i32, vp, C.c_int64]
     L.dcp_hip_num_profiles.argtypes = [vp]
     L.dcp_hip_load_chunks.argtypes = [vp]
     L.dcp_hip_pool_bytes.argtypes = [vp]
@@ -183,6 +187,20 @@ class Engine:
 
     def load_dcp(self, path: str, first: int = 0, count: int = -1) -> None:
         self._check(self.lib.dcp_hip_load_dcp(self.h, os.fsencode(path), first, count))
+
+    def load_hmm(self, path: str, gencode: int = 1, epsilon: float = 0.01, first: int = 0, count: int = -1) -> None:
+        """Profiles [first, first + count) of a HMMER3 text file, their emission tables made on the GPU under
+        translation table `gencode` and error rate `epsilon`: the pool load_dcp of the pressed file would leave."""
+        self._check(self.lib.dcp_hip_load_hmm(self.h, os.fsencode(path), int(gencode), float(epsilon), first, count))
+
+    def profile_tables(self, i: int) -> np.ndarray:
+        """Profile i as it lies in the pool (rows | trans | cost-order copy), copied: float32."""
+        n = int(self.lib.dcp_hip_profile_floats(self.h, i))
+        if n < 0:
+            raise IndexError(i)
+        out = np.empty(n, dtype=np.float32)
+        self._check(self.lib.dcp_hip_profile_read(self.h, i, _p(out), n))
+        return out
 
     @property
     def load_chunks(self) -> int:

@@ -26,6 +26,7 @@ def _lib():
     L.dcp_scan_setup.argtypes = [vp, C.c_char_p, i32, i32, C.c_bool, C.c_bool, C.c_bool, _CALLBACK, vp]
     L.dcp_scan_setup_partition.argtypes = [vp, C.c_char_p, i32, i32, i32, C.c_bool, C.c_bool, _CALLBACK, vp]
     L.dcp_scan_setup_partition_balanced.argtypes = L.dcp_scan_setup_partition.argtypes
+    L.dcp_scan_setup_hmm.argtypes = [vp, C.c_char_p, i32, C.c_float, C.c_bool, C.c_bool, _CALLBACK, vp]
     L.dcp_scan_partition_range.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
     L.dcp_scan_run.argtypes = [vp, vp, C.c_char_p]
     L.dcp_scan_interrupt.argtypes = [vp]
@@ -85,7 +86,7 @@ class Scan:
 
     def __init__(self, dbfile, port: int = 0, num_threads: int = 1, multi_hits: bool = True,
                  hmmer3_compat: bool = False, cache: bool = False, partition=None, on_window=None,
-                 balanced: bool = False, progress_callback: bool = True):
+                 balanced: bool = False, progress_callback: bool = True, _hmm=None):
         self._lib = _lib()
         self._cscan = self._lib.dcp_scan_new()
         if not self._cscan:
@@ -105,7 +106,10 @@ class Scan:
         # between windows); progress_callback=False hands it none, as a C caller may (c-core/test_scan.c:36-41)
         self._cb = _CALLBACK(_cb) if progress_callback else C.cast(None, _CALLBACK)
         path = os.fsencode(getattr(dbfile, "path", dbfile))
-        if partition is None:
+        if _hmm is not None:  # from_hmm: (gencode, epsilon)
+            rc = self._lib.dcp_scan_setup_hmm(self._cscan, path, int(_hmm[0]), float(_hmm[1]), multi_hits,
+                                              hmmer3_compat, self._cb, None)
+        elif partition is None:
             rc = self._lib.dcp_scan_setup(self._cscan, path, port, num_threads, multi_hits, hmmer3_compat, cache,
                                           self._cb, None)
         else:
@@ -115,6 +119,15 @@ class Scan:
         if rc:
             self.free()
             raise DeciphonError(rc)
+
+    @classmethod
+    def from_hmm(cls, hmmfile, gencode: int = 1, epsilon: float = 0.01, multi_hits: bool = True,
+                 hmmer3_compat: bool = False, on_window=None, progress_callback: bool = True):
+        """A scan straight from a HMMER3 text file (dcp_scan_setup_hmm, not in the reference): the tables are made
+        on the GPU and stay there, no .dcp is written, and the rows are those of a scan of the file pressed at the
+        same `gencode` and `epsilon`."""
+        return cls(hmmfile, multi_hits=multi_hits, hmmer3_compat=hmmer3_compat, on_window=on_window,
+                   progress_callback=progress_callback, _hmm=(gencode, epsilon))
 
     def run(self, snap, batch: Batch):
         self.interrupted = False

@@ -161,6 +161,13 @@ int dcp_scan_setup_partition(struct dcp_scan *, char const *dbfile, int device, 
 int dcp_scan_setup_partition_balanced(struct dcp_scan *, char const *dbfile, int device, int index, int nparts,
                                       bool multi_hits, bool hmmer3_compat, void (*callback)(void *), void *userdata);
 int dcp_scan_partition_range(struct dcp_scan const *, int *first, int *count);
+/* Not in the reference: dcp_scan_setup from a HMMER3 file instead of a pressed database (device:
+ * DECIPHON_HIP_DEVICE).  Rows are those of a scan of the file dcp_press_* writes from hmm at the same
+ * gencode_id and epsilon.  Nothing is written: the emission tables are made on the GPU and stay there
+ * (dcp_hip_load_hmm, whose error codes these are), and the scan keeps the nucleotide and codon distributions of
+ * every node in host memory (516 bytes per node) for the codons of its rows.  Not partitioned. */
+int dcp_scan_setup_hmm(struct dcp_scan *, char const *hmm, int gencode_id, float epsilon, bool multi_hits,
+                       bool hmmer3_compat, void (*callback)(void *), void *userdata);
 /* Number of product rows the last dcp_scan_run wrote, and row i (without newline).  The pointer stands until the next
  * dcp_scan_run or dcp_scan_del of that scan.  Once the scan has spilled rows to run files (dcp_scan_product_stats:
  * runs > 0; DECIPHON_HIP_PRODUCT_MB) it stands only until the next dcp_scan_product on that scan, and

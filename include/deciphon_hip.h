@@ -59,6 +59,25 @@ int dcp_hip_add_protein(struct dcp_hip *, int K, float const *node_trans, float 
  * end); replaces database_reader_open + protein_reader + protein_iter_next
  * (c-core/database_reader.c:26-80, c-core/protein_reader.c:29-128). */
 int dcp_hip_load_dcp(struct dcp_hip *, char const *path, int first, int count);
+/* Reads profiles [first, first+count) of a HMMER3 text file (count < 0: to the end), builds their models on the host
+ * (hmm_model.cpp), computes their emission tables under translation table gencode_id and error rate epsilon on the
+ * GPU and leaves them in the pool as dcp_hip_load_dcp of the file dcp_press_* would write leaves them.  No file is
+ * written.
+ * As dcp_hip_load_dcp: profiles are appended behind what is resident, accessions kept, dcp_hip_commit_profiles
+ * publishes.  Failures, in this order: NULL arguments DCP_EFUNCUSE; an unknown table DCP_EGENCODEID; epsilon outside
+ * [0, 1] or NaN DCP_EFUNCUSE; a file that cannot be opened DCP_EOPENHMM; then, profile by profile in file order, the
+ * reader's own codes (as dcp_press_next returns them) and DCP_ELARGECORESIZE beyond 16383 -- the file is read as it is
+ * loaded, so of a profile too long and a broken one behind it the first in the file is reported; DCP_EINVALPART for
+ * `first` out of range, once the file has been read; device errors.  The pool is sized once from the file's LENG
+ * lines (and grown where they fall short).  On any
+ * failure no profile is added: dcp_hip_num_profiles and dcp_hip_pool_bytes are what they were.  Profiles in front of
+ * `first` are parsed and skipped; those behind the range are not read.  Batches as press makes them
+ * (DECIPHON_HIP_PRESS_BATCH_NODES); DECIPHON_HIP_TIMING prints the seconds of parsing, upload, the emission kernel,
+ * the rows kernel and waiting to stderr. */
+int dcp_hip_load_hmm(struct dcp_hip *, char const *hmm, int gencode_id, float epsilon, int first, int count);
+/* test hooks: floats profile i occupies in the pool (rows | trans | cost-order copy), and a copy of them */
+int64_t dcp_hip_profile_floats(struct dcp_hip const *, int i);
+int dcp_hip_profile_read(struct dcp_hip const *, int i, float *out, int64_t n);
 /* how many staging chunks the last dcp_hip_load_dcp went through (256 MiB each; DECIPHON_HIP_STAGE_MB
  * shrinks them, never below one profile: a hook for tests of the double-buffered path) */
 int dcp_hip_load_chunks(struct dcp_hip const *);
@@ -96,7 +115,7 @@ void dcp_hip_xtrans(int seq_size, int multi_hits, int hmmer3_compat, float xt[DC
  * A window is the half-open range [start, stop) of sequence `seq` scored against
  * `profile`, i.e. one process_window call (c-core/thread.c:98-128).
  *
- * The inputs: every accepted call of dcp_hip_add_profile, _add_protein, _load_dcp, _commit_profiles,
+ * The inputs: every accepted call of dcp_hip_add_profile, _add_protein, _load_dcp, _load_hmm, _commit_profiles,
  * _clear_profiles, _set_sequences, _set_mode or _set_xtrans_table changes them, even one that sets what was
  * there already (a call refused for outstanding batches or for its arguments changes nothing).  Two things
  * outlive a call and are tied to the inputs they were made from: the staged window list (dcp_hip_stage) and the
@@ -125,7 +144,7 @@ int dcp_hip_cost_hits(struct dcp_hip *, int n, struct dcp_hip_window const *, in
  * _end waits for the OLDEST batch begun and delivers what dcp_hip_cost_hits would have.  Two batches may be
  * outstanding per engine (the second queues behind the first, so the GPU does not drain between them); a third
  * _begin is a DCP_EFUNCUSE.  While batches are outstanding -- in either buffer set, whichever began first -- the
- * engine accepts only _begin, _end, the read-only queries, dcp_hip_path, dcp_hip_path_trellis and
+ * engine accepts only _begin, _end, the read-only queries (dcp_hip_profile_read among them), dcp_hip_path, dcp_hip_path_trellis and
  * dcp_hip_path_reserve (the path pass has buffers and streams of its own); everything else is a DCP_EFUNCUSE, and
  * dcp_hip_clear_profiles does nothing (see there). */
 int dcp_hip_cost_hits_begin(struct dcp_hip *, int n, struct dcp_hip_window const *);
