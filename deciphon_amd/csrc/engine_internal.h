@@ -167,6 +167,11 @@ struct HostProfile
   int cQ = 0, cW = 0;  // shape of the cost kernel its cost-order copy of the rows is for (host_logic.h); 0: no copy
   int64_t pool_off; // floats
   std::string accession;
+  // What dcp_hip_set_epsilon needs of a profile that came by dcp_hip_load_hmm (dcp_hip::d_dist, d_dist_models):
+  int64_t dist = -1;       // entry of its node 0 among the kept distributions; -1: none kept (add_profile, add_protein, load_dcp)
+  int64_t dist_models = 0; // entry of its load's null model among the kept models; the background is the next
+  float epsilon = 0;       // the error rate its rows are at
+  bool poisoned = false;   // DECIPHON_HIP_COST_ORDER=poison at its load: its canonical match columns are 0
 };
 
 struct PathResult
@@ -224,6 +229,11 @@ struct dcp_hip
   size_t pool_used = 0; // floats of d_pool holding profiles
   int load_chunks = 0;  // staging chunks the last dcp_hip_load_dcp went through
   DevBuf<DcpProfileDev> d_profiles;
+  // The inputs of the emission tables of the profiles loaded from HMMER3 files, kept beside the pool for
+  // dcp_hip_set_epsilon: every node's entry (press_kernel.h: DCP_PRESS_IN_STRIDE floats, 528 bytes against the 5456 or
+  // more of its tables), and per load that added profiles the null model's and the background's.  Counted in entries.
+  DevBuf<float> d_dist, d_dist_models;
+  size_t dist_used = 0, dist_models_used = 0;
 
   // sequences
   std::vector<int64_t> seq_off, row_off;

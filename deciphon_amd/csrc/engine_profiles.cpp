@@ -2,7 +2,9 @@
 #include "engine_internal.h"
 #include "engine_hmm.h"
 #include "parallel_for.h"
+#include "../../include/deciphon_host.h"
 #include "press_batch.h"
+#include "press_reemit.h"
 #include "press_rows.h"
 
 #include <limits.h>
@@ -88,22 +90,27 @@ static int describe(dcp_hip *x, int K, char const *accession, HostProfile &hp)
   return 0;
 }
 
+// grows a device buffer to `floats`, keeping its first `keep`: once the stream is idle, a new allocation and a copy
+static int grow_keeping(dcp_hip *x, DevBuf<float> &buf, size_t floats, size_t keep)
+{
+  if (floats <= buf.cap) return 0;
+  HIP_TRY(x, hipStreamSynchronize(x->stream), DCP_EFUNCUSE);
+  DevBuf<float> bigger;
+  HIP_TRY(x, bigger.reserve(std::max(floats, buf.cap + buf.cap / 2)), DCP_ENOMEM);
+  if (keep) HIP_TRY(x, hipMemcpy(bigger.p, buf.p, keep * sizeof(float), hipMemcpyDeviceToDevice), DCP_EFUNCUSE);
+  buf.release();
+  buf.p = bigger.p;
+  buf.cap = bigger.cap;
+  bigger.p = nullptr;
+  bigger.cap = 0;
+  return 0;
+}
+
 // grows the device pool to `floats`, keeping what is resident (and, during a load that has written behind it, the
 // first `keep` floats)
 static int ensure_pool(dcp_hip *x, size_t floats, size_t keep = 0)
 {
-  keep = std::max(keep, x->pool_used);
-  if (floats <= x->d_pool.cap) return 0;
-  HIP_TRY(x, hipStreamSynchronize(x->stream), DCP_EFUNCUSE);
-  DevBuf<float> bigger;
-  HIP_TRY(x, bigger.reserve(std::max(floats, x->d_pool.cap + x->d_pool.cap / 2)), DCP_ENOMEM);
-  if (keep) HIP_TRY(x, hipMemcpy(bigger.p, x->d_pool.p, keep * sizeof(float), hipMemcpyDeviceToDevice), DCP_EFUNCUSE);
-  x->d_pool.release();
-  x->d_pool.p = bigger.p;
-  x->d_pool.cap = bigger.cap;
-  bigger.p = nullptr;
-  bigger.cap = 0;
-  return 0;
+  return grow_keeping(x, x->d_pool, floats, std::max(keep, x->pool_used));
 }
 
 // one profile from a host staging buffer to the end of the pool
@@ -321,7 +328,7 @@ struct HmmSlot : DcpPressBatch
 {
   PinBuf<float> h_in, h_trans;
   PinBuf<DcpRowsDesc> h_desc;
-  DevBuf<float> d_in, d_em, d_trans;
+  DevBuf<float> d_em, d_trans; // (the inputs go up into the engine's kept distributions, dcp_hip::d_dist)
   DevBuf<DcpRowsDesc> d_desc;
   hipEvent_t ev[4] = {}; // before the uploads, after them, after the emission kernel, after the rows kernel
   bool launched = false;
@@ -337,14 +344,19 @@ struct HmmLoad
   dcp_hip *x;
   float epsilon;
   HmmSlot slot[2];
-  PinBuf<float> h_models;            // the null model and the background: two entries in ...
-  DevBuf<float> d_models, d_nullbg;  // ... and their tables, null[1364] then bg[1364]
+  PinBuf<float> h_models;            // the null model and the background: two entries in, behind the engine's kept ones ...
+  DevBuf<float> d_nullbg;            // ... and their tables, null[1364] then bg[1364]
   size_t used;                       // floats of the pool written so far, the resident profiles included
+  // The engine keeps what the emission kernel reads (dcp_hip::d_dist, d_dist_models) for dcp_hip_set_epsilon: the
+  // entries go up behind the kept ones and count as kept only when the whole load is in, as the pool's floats do.
+  size_t dist_used;                  // node entries written so far, the kept ones included
+  size_t const models_at;            // where this load's two model entries lie
   std::vector<HostProfile> added;
   bool poison;
   double t_parse = 0, t_upload = 0, t_emission = 0, t_rows = 0, t_wait = 0, t_grow = 0;
   int grown = 0; // times the pool was reallocated during the load
-  HmmLoad(dcp_hip *x_, float eps) : x(x_), epsilon(eps), used(x_->pool_used)
+  HmmLoad(dcp_hip *x_, float eps)
+      : x(x_), epsilon(eps), used(x_->pool_used), dist_used(x_->dist_used), models_at(x_->dist_models_used)
   {
     char const *e = getenv("DECIPHON_HIP_COST_ORDER");
     poison = e && strcmp(e, "poison") == 0;
@@ -354,17 +366,25 @@ struct HmmLoad
   int models(DcpHmmReader const &reader)
   {
     HIP_TRY(x, h_models.reserve(2 * DCP_PRESS_IN_STRIDE), DCP_ENOMEM);
-    HIP_TRY(x, d_models.reserve(2 * DCP_PRESS_IN_STRIDE), DCP_ENOMEM);
     HIP_TRY(x, d_nullbg.reserve(2 * DCP_PRESS_TABLE), DCP_ENOMEM);
+    if (int rc = grow_keeping(x, x->d_dist_models, (models_at + 2) * DCP_PRESS_IN_STRIDE, models_at * DCP_PRESS_IN_STRIDE))
+      return rc;
+    float *d_models = x->d_dist_models.p + models_at * DCP_PRESS_IN_STRIDE;
     dcp_press_put_entry(h_models.p, reader.null_dist());
     dcp_press_put_entry(h_models.p + DCP_PRESS_IN_STRIDE, reader.bg_dist());
-    HIP_TRY(x, hipMemcpyAsync(d_models.p, h_models.p, 2 * DCP_PRESS_IN_STRIDE * sizeof(float), hipMemcpyHostToDevice, x->stream),
+    HIP_TRY(x, hipMemcpyAsync(d_models, h_models.p, 2 * DCP_PRESS_IN_STRIDE * sizeof(float), hipMemcpyHostToDevice, x->stream),
             DCP_EFUNCUSE);
-    if (dcp_press_emission_launch(d_models.p, d_nullbg.p, 2, epsilon, x->stream))
+    if (dcp_press_emission_launch(d_models, d_nullbg.p, 2, epsilon, x->stream))
       return fail(x, DCP_EFUNCUSE, "the emission kernel could not be launched");
     for (HmmSlot &s : slot)
       for (hipEvent_t &e : s.ev) HIP_TRY(x, hipEventCreate(&e), DCP_ENOMEM);
     return 0;
+  }
+
+  // the kept distributions hold `entries` node entries; a reallocation keeps what is written, as grow() does
+  int grow_dist(size_t entries)
+  {
+    return grow_keeping(x, x->d_dist, entries * DCP_PRESS_IN_STRIDE, dist_used * DCP_PRESS_IN_STRIDE);
   }
 
   // the pool holds `floats`; a reallocation waits for the stream and copies what is written (timed apart)
@@ -386,15 +406,18 @@ struct HmmLoad
     std::vector<long> const &len = reader.announced_lengths();
     if ((long)len.size() != reader.count()) return 0;
     long const last = count < 0 ? (long)len.size() : std::min((long)len.size(), first + count);
-    size_t floats = 0;
+    size_t floats = 0, nodes = 0;
     for (long i = first; i < last; ++i)
     {
       HostProfile hp;
       if (len[(size_t)i] < 1 || len[(size_t)i] >= DCP_MODEL_MAX) return 0; // the load will fail there
       if (describe(x, (int)len[(size_t)i], nullptr, hp)) return 0;
       floats += profile_floats(hp);
+      nodes += (size_t)hp.K;
     }
-    return floats ? grow(used + floats) : 0;
+    if (!floats) return 0;
+    if (int rc = grow(used + floats)) return rc;
+    return grow_dist(dist_used + nodes); // the kept distributions are sized by the same lines
   }
 
   // the slot's batch is through: its buffers are free again
@@ -429,7 +452,6 @@ struct HmmLoad
     }
     size_t const entries = (size_t)s.entries;
     HIP_TRY(x, s.h_in.reserve(entries * DCP_PRESS_IN_STRIDE), DCP_ENOMEM);
-    HIP_TRY(x, s.d_in.reserve(entries * DCP_PRESS_IN_STRIDE), DCP_ENOMEM);
     HIP_TRY(x, s.d_em.reserve(entries * DCP_PRESS_TABLE), DCP_ENOMEM);
     HIP_TRY(x, s.h_trans.reserve(toff[n]), DCP_ENOMEM);
     HIP_TRY(x, s.d_trans.reserve(toff[n]), DCP_ENOMEM);
@@ -457,15 +479,21 @@ struct HmmLoad
       d.trans_floats = (int32_t)(toff[i + 1] - toff[i]);
       d.cQ = hp.cQ;
       d.poison = hp.cQ && poison;
+      hp.dist = (int64_t)dist_used + s.first[i];
+      hp.dist_models = (int64_t)models_at;
+      hp.epsilon = epsilon;
+      hp.poisoned = d.poison != 0;
     }
     if (int rc = grow(used + off[n])) return rc;
+    if (int rc = grow_dist(dist_used + entries)) return rc;
+    float *const d_in = x->d_dist.p + dist_used * DCP_PRESS_IN_STRIDE;
     hipStream_t const q = x->stream;
     HIP_TRY(x, hipEventRecord(s.ev[0], q), DCP_EFUNCUSE);
-    HIP_TRY(x, hipMemcpyAsync(s.d_in.p, s.h_in.p, entries * DCP_PRESS_IN_STRIDE * sizeof(float), hipMemcpyHostToDevice, q), DCP_EFUNCUSE);
+    HIP_TRY(x, hipMemcpyAsync(d_in, s.h_in.p, entries * DCP_PRESS_IN_STRIDE * sizeof(float), hipMemcpyHostToDevice, q), DCP_EFUNCUSE);
     HIP_TRY(x, hipMemcpyAsync(s.d_trans.p, s.h_trans.p, toff[n] * sizeof(float), hipMemcpyHostToDevice, q), DCP_EFUNCUSE);
     HIP_TRY(x, hipMemcpyAsync(s.d_desc.p, s.h_desc.p, n * sizeof(DcpRowsDesc), hipMemcpyHostToDevice, q), DCP_EFUNCUSE);
     HIP_TRY(x, hipEventRecord(s.ev[1], q), DCP_EFUNCUSE);
-    if (dcp_press_emission_launch(s.d_in.p, s.d_em.p, (int)entries, epsilon, q))
+    if (dcp_press_emission_launch(d_in, s.d_em.p, (int)entries, epsilon, q))
       return fail(x, DCP_EFUNCUSE, "the emission kernel could not be launched");
     HIP_TRY(x, hipEventRecord(s.ev[2], q), DCP_EFUNCUSE);
     if (dcp_press_rows_launch(s.d_em.p, d_nullbg.p, d_nullbg.p + DCP_PRESS_TABLE, s.d_trans.p, s.d_desc.p, (int)n, max_Kp,
@@ -474,6 +502,7 @@ struct HmmLoad
     HIP_TRY(x, hipEventRecord(s.ev[3], q), DCP_EFUNCUSE);
     s.launched = true;
     used += off[n];
+    dist_used += entries;
     if (sink)
       for (DcpHmmProfile const &p : s.profiles) sink->profile(p);
     added.insert(added.end(), hps.begin(), hps.end());
@@ -535,11 +564,14 @@ int dcp_hip_load_hmm_sink(struct dcp_hip *x, char const *hmm, int gencode_id, fl
   if (getenv("DECIPHON_HIP_TIMING"))
     fprintf(stderr,
             "dcp_hip_load_hmm: %zu profiles, %.3f GB of tables; parse %.3f s, upload %.6f s, emission kernel %.6f s, "
-            "rows kernel %.6f s, wait %.3f s; pool grown %d times in %.3f s (of parse)\n",
+            "rows kernel %.6f s, wait %.3f s; pool grown %d times in %.3f s (of parse); kept %zu bytes of distributions\n",
             load.added.size(), (double)(load.used - x->pool_used) * 4e-9, load.t_parse, load.t_upload, load.t_emission,
-            load.t_rows, load.t_wait, load.grown, load.t_grow);
+            load.t_rows, load.t_wait, load.grown, load.t_grow,
+            (load.dist_used - x->dist_used + (load.added.empty() ? 0 : 2)) * DCP_PRESS_IN_STRIDE * sizeof(float));
   x->profiles.insert(x->profiles.end(), load.added.begin(), load.added.end());
   x->pool_used = load.used;
+  x->dist_used = load.dist_used;
+  if (!load.added.empty()) x->dist_models_used = load.models_at + 2; // (an empty range keeps no models either)
   ++x->gen;
   return 0;
 }
@@ -549,6 +581,100 @@ extern "C" {
 int dcp_hip_load_hmm(struct dcp_hip *x, char const *hmm, int gencode_id, float epsilon, int first, int count)
 {
   return dcp_hip_load_hmm_sink(x, hmm, gencode_id, epsilon, first, count, nullptr);
+}
+
+// Every profile's rows, cost-order copy and headers again, at `epsilon`, from the kept distributions: the null and
+// background tables of every load by the emission kernel, then one launch of the re-emission kernel (press_reemit.hip)
+// over all (profile, 64 positions) pairs.  The descriptors and the pair list are built here and uploaded: 56 bytes per
+// profile and 8 per pair.
+int dcp_hip_set_epsilon(struct dcp_hip *x, float epsilon)
+{
+  if (!x) return DCP_EFUNCUSE;
+  if (outstanding_batches(x)) return refuse_outstanding(x);
+  if (!(epsilon >= 0.0f && epsilon <= 1.0f)) return fail(x, DCP_EFUNCUSE, "epsilon must lie in [0, 1]");
+  size_t const n = x->profiles.size();
+  for (size_t i = 0; i < n; ++i)
+    if (x->profiles[i].dist < 0)
+    {
+      char msg[128];
+      snprintf(msg, sizeof msg, "profile %zu has no distributions kept: only dcp_hip_load_hmm keeps them", i);
+      return fail(x, DCP_EFUNCUSE, msg);
+    }
+  if (!n) return 0;
+  HIP_TRY(x, hipSetDevice(x->device), DCP_EFUNCUSE);
+
+  std::vector<DcpReemitDesc> desc(n);
+  std::vector<int32_t> Kp(n);
+  size_t nodes = 0, written = 0;
+  for (size_t i = 0; i < n; ++i)
+  {
+    HostProfile const &hp = x->profiles[i];
+    DcpReemitDesc &d = desc[i];
+    d.src = hp.dist;
+    d.rows_off = hp.pool_off;
+    d.copy_off = hp.pool_off + (int64_t)canonical_floats(hp.Kp);
+    d.K = hp.K;
+    d.Kp = Kp[i] = hp.Kp;
+    d.stride = hp.Kp + DCP_ROW_HDR;
+    d.cQ = hp.cQ;
+    d.poison = hp.poisoned;
+    d.null_row = (int32_t)hp.dist_models;
+    d.bg_row = d.null_row + 1;
+    nodes += (size_t)hp.K;
+    written += (size_t)DCP_TABLE_SIZE * ((size_t)d.stride + (hp.cQ ? (size_t)dcp_cost_order_stride(hp.cQ, hp.cW) : 0));
+  }
+  int64_t const pairs = dcp_reemit_tiles((int)n, Kp.data(), nullptr, nullptr, 0);
+  std::vector<int32_t> pair_profile((size_t)pairs), pair_k0((size_t)pairs);
+  (void)dcp_reemit_tiles((int)n, Kp.data(), pair_profile.data(), pair_k0.data(), pairs);
+
+  DevBuf<DcpReemitDesc> d_desc;
+  DevBuf<int32_t> d_pair_profile, d_pair_k0;
+  DevBuf<float> d_tables; // the null and background tables at the new error rate, one row per kept model entry
+  struct Event
+  {
+    hipEvent_t e = nullptr;
+    ~Event()
+    {
+      if (e) (void)hipEventDestroy(e);
+    }
+  } ev[2];
+  HIP_TRY(x, d_desc.reserve(n), DCP_ENOMEM);
+  HIP_TRY(x, d_pair_profile.reserve((size_t)pairs), DCP_ENOMEM);
+  HIP_TRY(x, d_pair_k0.reserve((size_t)pairs), DCP_ENOMEM);
+  HIP_TRY(x, d_tables.reserve(x->dist_models_used * DCP_PRESS_TABLE), DCP_ENOMEM);
+  for (Event &e : ev) HIP_TRY(x, hipEventCreate(&e.e), DCP_ENOMEM);
+  HIP_TRY(x, hipMemcpy(d_desc.p, desc.data(), n * sizeof(DcpReemitDesc), hipMemcpyHostToDevice), DCP_EFUNCUSE);
+  HIP_TRY(x, hipMemcpy(d_pair_profile.p, pair_profile.data(), (size_t)pairs * sizeof(int32_t), hipMemcpyHostToDevice), DCP_EFUNCUSE);
+  HIP_TRY(x, hipMemcpy(d_pair_k0.p, pair_k0.data(), (size_t)pairs * sizeof(int32_t), hipMemcpyHostToDevice), DCP_EFUNCUSE);
+  hipStream_t const q = x->stream;
+  if (dcp_press_emission_launch(x->d_dist_models.p, d_tables.p, (int)x->dist_models_used, epsilon, q))
+    return fail(x, DCP_EFUNCUSE, "the emission kernel could not be launched");
+  HIP_TRY(x, hipEventRecord(ev[0].e, q), DCP_EFUNCUSE);
+  if (dcp_press_reemit_launch(x->d_dist.p, d_tables.p, d_desc.p, d_pair_profile.p, d_pair_k0.p, pairs, epsilon, x->d_pool.p, q))
+    return fail(x, DCP_EFUNCUSE, "the re-emission kernel could not be launched");
+  HIP_TRY(x, hipEventRecord(ev[1].e, q), DCP_EFUNCUSE);
+  HIP_TRY(x, hipStreamSynchronize(q), DCP_EFUNCUSE);
+  if (getenv("DECIPHON_HIP_TIMING"))
+  {
+    float ms = 0;
+    HIP_TRY(x, hipEventElapsedTime(&ms, ev[0].e, ev[1].e), DCP_EFUNCUSE);
+    fprintf(stderr, "dcp_hip_set_epsilon: %zu profiles, %zu nodes, %zu bytes written; re-emission kernel %.6f s\n", n, nodes,
+            written * sizeof(float), ms * 1e-3);
+  }
+  for (HostProfile &hp : x->profiles) hp.epsilon = epsilon;
+  ++x->gen;
+  return 0;
+}
+
+float dcp_hip_profile_epsilon(struct dcp_hip const *x, int i)
+{
+  if (!x || i < 0 || i >= (int)x->profiles.size() || x->profiles[(size_t)i].dist < 0) return NAN;
+  return x->profiles[(size_t)i].epsilon;
+}
+
+int64_t dcp_hip_dist_bytes(struct dcp_hip const *x)
+{
+  return x ? (int64_t)((x->dist_used + x->dist_models_used) * DCP_PRESS_IN_STRIDE * sizeof(float)) : 0;
 }
 
 int64_t dcp_hip_profile_floats(struct dcp_hip const *x, int i)
@@ -629,6 +755,10 @@ void dcp_hip_clear_profiles(struct dcp_hip *x)
   x->pool_used = 0;
   x->profiles.clear();
   x->committed = 0;
+  x->dist_used = x->dist_models_used = 0;
+  (void)hipSetDevice(x->device);
+  x->d_dist.release();
+  x->d_dist_models.release();
 }
 
 } // extern "C"

@@ -128,6 +128,19 @@ int dcp_row_lane_offsets(int layout, int Q, int S, int K, uint32_t *offsets)
   return dcp_row_read_lanes(layout, Q, S, K);
 }
 
+int64_t dcp_reemit_tiles(int n, int32_t const *Kp, int32_t *profile, int32_t *k0, int64_t cap)
+{
+  int64_t count = 0;
+  for (int i = 0; i < n; ++i)
+    for (int32_t k = 0; k < Kp[i]; k += 64, ++count)
+      if (count < cap)
+      {
+        profile[count] = i;
+        k0[count] = k;
+      }
+  return count;
+}
+
 int dcp_xcd_eighths_entry_of(int b, int n) { return b < 0 || b >= n ? -1 : dcp_xcd_eighths_entry(b, n); }
 
 int dcp_xcd_placement_of(int workgroups, int windows_per_profile, int64_t table_bytes, int resident_per_xcd)

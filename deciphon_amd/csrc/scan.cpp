@@ -55,6 +55,7 @@ struct dcp_scan
   // the rows read the distributions of the profiles with hits from it: the database, which stays mapped, or what a
   // load from a HMMER3 file left in memory
   std::unique_ptr<DcpDecoderSource> db;
+  DcpHmmDecoders *hmm = nullptr; // `db`, when dcp_scan_setup_hmm set it: the error rate moves with the tables (dcp_scan_set_epsilon)
 };
 
 namespace
@@ -174,6 +175,7 @@ int setup_common(dcp_scan *x, char const *dbfile, int device, int index, int npa
   {
     std::unique_ptr<DcpDbDecoders> mapped(new DcpDbDecoders);
     if ((rc = mapped->db.open(dbfile))) return raise(rc, __func__, dbfile);
+    x->hmm = nullptr;
     x->db = std::move(mapped);
   }
   if ((rc = new_engine(x, device))) return raise(rc, __func__, "no usable HIP device (there is no CPU fallback)");
@@ -388,6 +390,7 @@ int dcp_scan_setup_hmm(struct dcp_scan *x, char const *hmm, int gencode_id, floa
   std::unique_ptr<DcpHmmDecoders> kept(new DcpHmmDecoders);
   kept->gencode = gencode_id;
   kept->epsilon = epsilon;
+  x->hmm = nullptr;
   x->db.reset();
   x->abc_name = "dna"; // what press writes
   x->index_offset = 0;
@@ -396,8 +399,20 @@ int dcp_scan_setup_hmm(struct dcp_scan *x, char const *hmm, int gencode_id, floa
   if (rc) return raise(rc, __func__, dcp_hip_strerror(x->eng)); // (what the sink was shown goes with `kept`)
   if ((rc = dcp_hip_commit_profiles(x->eng))) return raise(rc, __func__, dcp_hip_strerror(x->eng));
   x->num_proteins = dcp_hip_num_profiles(x->eng);
+  x->hmm = kept.get();
   x->db = std::move(kept);
   return set_mode(x, __func__, multi_hits, hmmer3_compat, callback, userdata);
+}
+
+int dcp_scan_set_epsilon(struct dcp_scan *x, float epsilon)
+{
+  // the arguments first: without a GPU the codes are still told apart
+  if (!x) return raise(DCP_EFUNCUSE, __func__);
+  if (!x->eng || !x->hmm) return raise(DCP_EFUNCUSE, __func__, "the scan was not set up by dcp_scan_setup_hmm");
+  if (!(epsilon >= 0.0f && epsilon <= 1.0f)) return raise(DCP_EFUNCUSE, __func__, "epsilon must lie in [0, 1]");
+  if (int const rc = dcp_hip_set_epsilon(x->eng, epsilon)) return raise(rc, __func__, dcp_hip_strerror(x->eng));
+  x->hmm->epsilon = epsilon; // the codons of the rows are decoded under the tables' error rate (scan_rows.h)
+  return 0;
 }
 
 int dcp_scan_partition_range(struct dcp_scan const *x, int *first, int *count)

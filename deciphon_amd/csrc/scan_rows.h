@@ -50,7 +50,7 @@ struct DcpDbDecoders : DcpDecoderSource
 struct DcpHmmDecoders : DcpDecoderSource, DcpHmmSink
 {
   int gencode = 0;
-  float epsilon = 0;
+  float epsilon = 0; // of the engine's tables: dcp_scan_set_epsilon moves both, between runs (a run's decoders copy it)
   DcpNucltDist null{}, bg{};
   std::vector<std::vector<DcpNucltDist>> nodes; // by profile: [K]
   void models(DcpNucltDist const &n, DcpNucltDist const &b) override { null = n, bg = b; }

@@ -54,6 +54,11 @@ def load_library() -> C.CDLL:
     L.dcp_hip_add_protein.argtypes = [vp, i32, vp, vp, vp, vp, vp, C.POINTER(i32)]
     L.dcp_hip_load_dcp.argtypes = [vp, C.c_char_p, i32, i32]
     L.dcp_hip_load_hmm.argtypes = [vp, C.c_char_p, i32, C.c_float, i32, i32]
+    L.dcp_hip_set_epsilon.argtypes = [vp, C.c_float]
+    L.dcp_hip_profile_epsilon.argtypes = [vp, i32]
+    L.dcp_hip_profile_epsilon.restype = C.c_float
+    L.dcp_hip_dist_bytes.argtypes = [vp]
+    L.dcp_hip_dist_bytes.restype = C.c_int64
     L.dcp_hip_profile_floats.argtypes = [vp, i32]
     L.dcp_hip_profile_floats.restype = C.c_int64
     L.dcp_hip_profile_read.argtypes = [vp, i32, vp, C.c_int64]
@@ -192,6 +197,20 @@ class Engine:
         """Profiles [first, first + count) of a HMMER3 text file, their emission tables made on the GPU under
         translation table `gencode` and error rate `epsilon`: the pool load_dcp of the pressed file would leave."""
         self._check(self.lib.dcp_hip_load_hmm(self.h, os.fsencode(path), int(gencode), float(epsilon), first, count))
+
+    def set_epsilon(self, epsilon: float) -> None:
+        """Every profile again at error rate `epsilon`, on the GPU and in place: the pool load_hmm of the same files
+        would leave at that rate.  Only for engines all of whose profiles came by load_hmm (DCP_EFUNCUSE otherwise)."""
+        self._check(self.lib.dcp_hip_set_epsilon(self.h, float(epsilon)))
+
+    def profile_epsilon(self, i: int) -> float:
+        """The error rate profile i is at; NaN when it did not come by load_hmm."""
+        return float(self.lib.dcp_hip_profile_epsilon(self.h, i))
+
+    @property
+    def dist_bytes(self) -> int:
+        """HBM bytes of the distributions kept beside the pool for set_epsilon."""
+        return int(self.lib.dcp_hip_dist_bytes(self.h))
 
     def profile_tables(self, i: int) -> np.ndarray:
         """Profile i as it lies in the pool (rows | trans | cost-order copy), copied: float32."""

@@ -46,6 +46,8 @@ def _lib():
     L.dcp_window_count.restype = C.c_int64
     L.dcp_cost_order_map.argtypes = [i32, i32, vp]
     L.dcp_row_lane_offsets.argtypes = [i32, i32, i32, i32, vp]
+    L.dcp_reemit_tiles.argtypes = [i32, vp, vp, vp, C.c_int64]
+    L.dcp_reemit_tiles.restype = C.c_int64
     L.dcp_scan_plan_chunks.argtypes = [i32, vp, i32, vp, C.c_double, C.c_double, C.c_int64, C.c_int64, i32, vp, vp,
                                        C.POINTER(i32)]
     L.dcp_scan_walk_new.argtypes = [i32, vp, i32, vp]
@@ -274,6 +276,17 @@ class WindowIter:
 def window_count(seq_size: int, core_size: int) -> int:
     """Windows of the no-hit chain of one (read, profile) pair (what WindowIter walks when nothing hits)."""
     return int(_lib().dcp_window_count(int(seq_size), int(core_size)))
+
+
+def reemit_tiles(Kp, cap: int):
+    """(count, profile int32[cap], k0 int32[cap]): the (profile, k0) workgroup list of Engine.set_epsilon's kernel for
+    profiles of padded lengths Kp (dcp_reemit_tiles); entries beyond min(count, cap) are left at -1."""
+    Kp = np.ascontiguousarray(Kp, np.int32)
+    profile = np.full(cap, -1, np.int32)
+    k0 = np.full(cap, -1, np.int32)
+    count = _lib().dcp_reemit_tiles(len(Kp), Kp.ctypes.data_as(C.c_void_p), profile.ctypes.data_as(C.c_void_p),
+                                    k0.ctypes.data_as(C.c_void_p), int(cap))
+    return int(count), profile, k0
 
 
 def cost_order_map(Q: int, W: int):

@@ -27,6 +27,7 @@ def _lib():
     L.dcp_scan_setup_partition.argtypes = [vp, C.c_char_p, i32, i32, i32, C.c_bool, C.c_bool, _CALLBACK, vp]
     L.dcp_scan_setup_partition_balanced.argtypes = L.dcp_scan_setup_partition.argtypes
     L.dcp_scan_setup_hmm.argtypes = [vp, C.c_char_p, i32, C.c_float, C.c_bool, C.c_bool, _CALLBACK, vp]
+    L.dcp_scan_set_epsilon.argtypes = [vp, C.c_float]
     L.dcp_scan_partition_range.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
     L.dcp_scan_run.argtypes = [vp, vp, C.c_char_p]
     L.dcp_scan_interrupt.argtypes = [vp]
@@ -128,6 +129,12 @@ class Scan:
         same `gencode` and `epsilon`."""
         return cls(hmmfile, multi_hits=multi_hits, hmmer3_compat=hmmer3_compat, on_window=on_window,
                    progress_callback=progress_callback, _hmm=(gencode, epsilon))
+
+    def set_epsilon(self, epsilon: float):
+        """A scan made by from_hmm at another error rate (dcp_scan_set_epsilon): the next run writes the rows of a
+        fresh from_hmm at `epsilon`.  Not while run() is running."""
+        if rc := self._lib.dcp_scan_set_epsilon(self._cscan, float(epsilon)):
+            raise DeciphonError(rc)
 
     def run(self, snap, batch: Batch):
         self.interrupted = False

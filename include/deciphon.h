@@ -168,6 +168,13 @@ int dcp_scan_partition_range(struct dcp_scan const *, int *first, int *count);
  * every node in host memory (516 bytes per node) for the codons of its rows.  Not partitioned. */
 int dcp_scan_setup_hmm(struct dcp_scan *, char const *hmm, int gencode_id, float epsilon, bool multi_hits,
                        bool hmmer3_compat, void (*callback)(void *), void *userdata);
+/* Not in the reference: a scan set up by dcp_scan_setup_hmm at another error rate, without reading the file again
+ * (dcp_hip_set_epsilon: the tables are rewritten on the GPU, in place).  The next dcp_scan_run writes the rows a fresh
+ * dcp_scan_setup_hmm at `epsilon` would, codons and amino acids included.  DCP_EFUNCUSE, with the scan left as it was,
+ * for NULL, for a scan that is not set up or was set up from a pressed file, and for epsilon outside [0, 1] or NaN --
+ * all checked before the GPU is touched.  Not to be called while dcp_scan_run runs on that scan (nothing locks).  The
+ * rows of the last run (dcp_scan_product) stay valid. */
+int dcp_scan_set_epsilon(struct dcp_scan *, float epsilon);
 /* Number of product rows the last dcp_scan_run wrote, and row i (without newline).  The pointer stands until the next
  * dcp_scan_run or dcp_scan_del of that scan.  Once the scan has spilled rows to run files (dcp_scan_product_stats:
  * runs > 0; DECIPHON_HIP_PRODUCT_MB) it stands only until the next dcp_scan_product on that scan, and

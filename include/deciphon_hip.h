@@ -75,6 +75,26 @@ int dcp_hip_load_dcp(struct dcp_hip *, char const *path, int first, int count);
  * (DECIPHON_HIP_PRESS_BATCH_NODES); DECIPHON_HIP_TIMING prints the seconds of parsing, upload, the emission kernel,
  * the rows kernel and waiting to stderr. */
 int dcp_hip_load_hmm(struct dcp_hip *, char const *hmm, int gencode_id, float epsilon, int first, int count);
+/* The profiles that came by dcp_hip_load_hmm again at another error rate, on the GPU and in place.  A load keeps what
+ * its emission tables were made from in HBM beside the pool -- 528 bytes per node (nucltp[4], codonm[125]), against
+ * 5456 or more of tables, and the null model and the background of each load (dcp_hip_dist_bytes: all of it) -- and
+ * this call writes every profile's emission rows, their headers and the cost-order copies again from them: no file
+ * is read and nothing but a list of workgroups goes up.  Afterwards the pool is, word for word, what dcp_hip_load_hmm
+ * of the same files, ranges and translation tables leaves at `epsilon`; the transitions do not depend on the error
+ * rate and are not touched.  Offsets and sizes stay, so nothing needs committing again.  It runs on the engine's
+ * stream and returns when the tables are written.
+ * Failures, in this order, each leaving the pool and every query as they were: NULL DCP_EFUNCUSE; cost batches
+ * outstanding DCP_EFUNCUSE (as every call that changes the inputs); epsilon outside [0, 1] or NaN DCP_EFUNCUSE; a
+ * profile, committed or not, that came by dcp_hip_add_profile, _add_protein or _load_dcp -- no distributions are
+ * kept for those -- DCP_EFUNCUSE, dcp_hip_strerror naming the first; device errors.  Without profiles it returns 0 and
+ * does nothing.  The translation table cannot be changed this way.  DECIPHON_HIP_TIMING prints profiles, nodes, bytes
+ * written and the kernel's seconds. */
+int dcp_hip_set_epsilon(struct dcp_hip *, float epsilon);
+/* the error rate profile `index` is at; NaN for a profile without kept distributions (and for a bad index or NULL) */
+float dcp_hip_profile_epsilon(struct dcp_hip const *, int index);
+/* Bytes of HBM the kept distributions occupy: 528 per node of every profile loaded from a HMMER3 file, and 2 x 528 per
+ * dcp_hip_load_hmm that added profiles (its null model and background).  dcp_hip_clear_profiles frees them. */
+int64_t dcp_hip_dist_bytes(struct dcp_hip const *);
 /* test hooks: floats profile i occupies in the pool (rows | trans | cost-order copy), and a copy of them */
 int64_t dcp_hip_profile_floats(struct dcp_hip const *, int i);
 int dcp_hip_profile_read(struct dcp_hip const *, int i, float *out, int64_t n);
@@ -115,7 +135,8 @@ void dcp_hip_xtrans(int seq_size, int multi_hits, int hmmer3_compat, float xt[DC
  * A window is the half-open range [start, stop) of sequence `seq` scored against
  * `profile`, i.e. one process_window call (c-core/thread.c:98-128).
  *
- * The inputs: every accepted call of dcp_hip_add_profile, _add_protein, _load_dcp, _load_hmm, _commit_profiles,
+ * The inputs: every accepted call of dcp_hip_add_profile, _add_protein, _load_dcp, _load_hmm, _set_epsilon (with
+ * profiles resident), _commit_profiles,
  * _clear_profiles, _set_sequences, _set_mode or _set_xtrans_table changes them, even one that sets what was
  * there already (a call refused for outstanding batches or for its arguments changes nothing).  Two things
  * outlive a call and are tied to the inputs they were made from: the staged window list (dcp_hip_stage) and the

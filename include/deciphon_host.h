@@ -81,6 +81,11 @@ int64_t dcp_window_count(int64_t seq_size, int core_size);
  * first column (behind the row's 32-float header), and the function returns the floats of one copy row (0 and
  * nothing written for Q < 1, W < 1 or Q*W > 64). */
 int dcp_cost_order_map(int Q, int W, int32_t *cols);
+/* The workgroups of dcp_hip_set_epsilon's kernel (csrc/press_reemit.h): one (profile, k0) pair per 64 positions of
+ * every profile, k0 = 0, 64, ... below its padded length Kp[i] (a multiple of 64), profiles in order and k0 ascending
+ * within each.  Returns the number of pairs, the sum of Kp[i] / 64, whatever `cap` is; the first min(count, cap) of them
+ * are written to profile[] and k0[] and nothing beyond (cap = 0: the arrays may be NULL). */
+int64_t dcp_reemit_tiles(int n, int32_t const *Kp, int32_t *profile, int32_t *k0, int64_t cap);
 /* Which columns of an emission row the lanes of a cost kernel read for a profile of K positions (csrc/dcp_types.h
  * dcp_row_read_offset: a lane with no position below K reads with the last lane that has one).  layout 0: one
  * wavefront of 64 lanes x Q positions on the canonical rows; 1: the same on the cost-order copy; 2: one group of S

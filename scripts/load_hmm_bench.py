@@ -6,6 +6,9 @@
   (c) the rows kernel alone, from (b)'s HIP-event seconds: pool bytes written per second, beside a device-to-device
       copy of as many bytes (hipMemcpyAsync, HIP events) -- the yardstick for a kernel that only moves data.
 
+  (d) --set-epsilon, instead of the routes: a full Engine.load_hmm, then Engine.set_epsilon on that engine -- wall clock
+      of both, the load's emission + rows kernel seconds beside the one re-emission kernel's, which does their work.
+
 The routes alternate, --runs times each.  Prints a line per run and one JSON line.  `--route direct --runs 1` is what
 to put behind `rocprofv3 --kernel-trace --stats --` for the kernels' shares of the load."""
 import argparse
@@ -29,6 +32,10 @@ ap.add_argument("--epsilon", type=float, default=0.01)
 ap.add_argument("--runs", type=int, default=3)
 ap.add_argument("--route", choices=["both", "file", "direct"], default="both")
 ap.add_argument("--dir", default=None, help="where the .hmm and .dcp go (default: a temporary directory)")
+ap.add_argument("--set-epsilon", action="store_true",
+                help="instead of the routes: --runs times a full Engine.load_hmm, then Engine.set_epsilon on that "
+                     "engine (to --to-epsilon), wall clock and kernel seconds of both")
+ap.add_argument("--to-epsilon", type=float, default=0.1)
 args = ap.parse_args()
 
 work = args.dir or tempfile.mkdtemp(prefix="load_hmm_bench_")
@@ -121,7 +128,47 @@ def device_copy_gb_per_s(nbytes):
     return best
 
 
+RETIMING = re.compile(r"dcp_hip_set_epsilon: (\d+) profiles, (\d+) nodes, (\d+) bytes written; re-emission kernel ([\d.]+) s")
+
+
+def set_epsilon_leg():
+    """A full load, then a change of the error rate on the same engine: the load's emission + rows kernels do the work
+    of the one re-emission kernel, through the scratch buffer."""
+    from deciphon_amd import Engine
+
+    os.environ["DECIPHON_HIP_TIMING"] = "1"
+    with Engine(0) as eng:
+        t0 = time.perf_counter()
+        _, text = stderr_of(lambda: eng.load_hmm(hmm, 1, args.epsilon))
+        t_load = time.perf_counter() - t0
+        m = TIMING.search(text)
+        assert m, text
+        v = [float(x) for x in m.groups()]
+        t0 = time.perf_counter()
+        _, text = stderr_of(lambda: eng.set_epsilon(args.to_epsilon))
+        t_set = time.perf_counter() - t0
+        m = RETIMING.search(text)
+        assert m, text
+        w = m.groups()
+        out = dict(load_s=t_load, emission_kernel_s=v[4], rows_kernel_s=v[5], load_kernels_s=v[4] + v[5],
+                   set_epsilon_s=t_set, reemit_kernel_s=float(w[3]), nodes=int(w[1]), bytes_written=int(w[2]),
+                   written_gb_per_s=int(w[2]) / 1e9 / float(w[3]) if float(w[3]) else None,
+                   pool_bytes=eng.pool_bytes, dist_bytes=eng.dist_bytes)
+    del os.environ["DECIPHON_HIP_TIMING"]
+    return out
+
+
 res = dict(profiles=nprof, hmm_mb=os.path.getsize(hmm) / 1e6, epsilon=args.epsilon, file=[], direct=[])
+if args.set_epsilon:
+    res["to_epsilon"], res["set_epsilon"] = args.to_epsilon, []
+    for run in range(args.runs):
+        r = set_epsilon_leg()
+        res["set_epsilon"].append(r)
+        print(f"run {run} load: {r['load_s']:.3f} s, emission kernel {r['emission_kernel_s']:.4f} + rows kernel "
+              f"{r['rows_kernel_s']:.4f} = {r['load_kernels_s']:.4f} s | set_epsilon: {r['set_epsilon_s']:.4f} s, "
+              f"re-emission kernel {r['reemit_kernel_s']:.4f} s, {r['written_gb_per_s']:.0f} GB/s written; "
+              f"distributions {r['dist_bytes'] / 1e6:.1f} MB beside a pool of {r['pool_bytes'] / 1e6:.1f} MB", flush=True)
+    args.runs = 0
 for run in range(args.runs):
     if args.route in ("both", "file"):
         r = file_route()
