@@ -14,7 +14,9 @@
 // probability space these products underflow long before log P(z) leaves its range: e^2 at e < 1e-19 (log P is
 // still about -100 at e = 1e-22), and p p M of an almost one-hot emission at any e.  So each term is taken as its
 // log, ln c + a ln e + b ln f + ln poly, in double, and the terms are combined by a max-shifted sum.  The
-// polynomials are sums of products of at most three probabilities, in double from the fp32 log inputs.  A zero power is left out of its term, never written as 0 * ln 0: with e = 0 or
+// polynomials are sums of products of at most three probabilities, in double from the fp32 log inputs; a 3-mer, whose
+// ln P lies beside fp32 midpoints by structure, keeps its exact parts apart to the end (press_emission.h).  A zero
+// power is left out of its term, never written as 0 * ln 0: with e = 0 or
 // e = 1 the terms that vanish are -inf (a positive multiple of -inf, or ln 0), nothing is NaN, and a code whose
 // terms all vanish is -inf exactly.  No term is ever +inf.  The result is rounded to fp32 once, at the end.
 // (The arithmetic itself is in press_emission.h, shared with press_reemit.hip.)
@@ -38,14 +40,14 @@ __global__ __launch_bounds__(THREADS) void emission_kernel(float const *__restri
   size_t const entry = blockIdx.x;
   if (tid < INPUTS) prob[tid] = input_prob(in[entry * DCP_PRESS_IN_STRIDE + (size_t)tid]);
   __syncthreads();
-  State const s{prob, prob + 4};
+  State const s{prob, prob + 4, in + entry * DCP_PRESS_IN_STRIDE};
   double const le = log((double)epsilon), lf = log1p(-(double)epsilon);
   float *row = out + entry * DCP_PRESS_TABLE;
   for (int code = tid; code < DCP_PRESS_TABLE; code += THREADS)
   {
     int z[5];
     int const n = decode(code, z);
-    row[code] = (float)emission_lprob(s, le, lf, n, z);
+    row[code] = emission_lprob(s, le, lf, n, z);
   }
 }
 

@@ -88,8 +88,8 @@ __global__ __launch_bounds__(THREADS) void reemit_kernel(float const *__restrict
         float v = inf;
         if (kk < nodes && code < DCP_TABLE_SIZE)
         {
-          State const s{prob[kk], prob[kk] + 4};
-          v = flip((float)emission_lprob(s, le, lf, n, z));
+          State const s{prob[kk], prob[kk] + 4, dist + (d.src + kh + kk) * DCP_PRESS_IN_STRIDE};
+          v = flip(emission_lprob(s, le, lf, n, z));
         }
         tile[kk][tx] = v;
       }

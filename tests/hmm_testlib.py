@@ -39,6 +39,30 @@ def star_profile(seeds, rng, K=60, accession="STAR0.1"):
     return star
 
 
+AMINO = "ACDEFGHIKLMNPQRSTVWY"  # the order of a HMMER3 match line
+# the nodes of edge_profile, in order; (amino acid, nats) = almost one-hot: every other amino acid that far down
+EDGE_NODES = ("real0", "real1", "real2", "star", ("M", 60), ("M", 200), ("L", 60), ("L", 200), "uniform")
+
+
+def edge_profile(seeds, rng, accession="EDGE0.1"):
+    """One node per kind of match emission the emission kernels can meet (EDGE_NODES): three as a real profile has
+    them, one of star_profile's (half the amino acids at probability 0), almost one-hot ones for an amino acid of one
+    codon (M) and of six (L) with every other amino acid at e^-60 and at e^-200 of it -- at 200 a product of three
+    inputs, e^-600, is still a normal double --, and a uniform one."""
+    from deciphon_amd import synth
+
+    prof = synth.resample_hmm(seeds, len(EDGE_NODES), rng, accession)
+    star = star_profile(seeds, rng, K=4)["nodes"][0]["match"]
+    for nd, kind in zip(prof["nodes"], EDGE_NODES):
+        if kind == "star":
+            nd["match"] = list(star)
+        elif kind == "uniform":
+            nd["match"] = ["2.99573"] * 20
+        elif isinstance(kind, tuple):
+            nd["match"] = ["0.00000" if a == kind[0] else f"{kind[1]:.5f}" for a in AMINO]
+    return prof
+
+
 def pool_words(eng, first=0, last=None):
     """(K, accession, words) of profiles [first, last) as they lie in the pool."""
     last = eng.num_profiles if last is None else last
