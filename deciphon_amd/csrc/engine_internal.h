@@ -171,6 +171,7 @@ struct HostProfile
   int64_t dist = -1;       // entry of its node 0 among the kept distributions; -1: none kept (add_profile, add_protein, load_dcp)
   int64_t dist_models = 0; // entry of its load's null model among the kept models; the background is the next
   float epsilon = 0;       // the error rate its rows are at
+  int gencode = 0;         // the translation table its rows are under (dcp_hip_set_gencode); 0: no distributions kept
   bool poisoned = false;   // DECIPHON_HIP_COST_ORDER=poison at its load: its canonical match columns are 0
 };
 
@@ -234,6 +235,9 @@ struct dcp_hip
   // more of its tables), and per load that added profiles the null model's and the background's.  Counted in entries.
   DevBuf<float> d_dist, d_dist_models;
   size_t dist_used = 0, dist_models_used = 0;
+  // What those entries were derived from, in host memory, for dcp_hip_set_gencode: the 20 amino log-odds of every kept
+  // node, which do not depend on the translation table (80 bytes beside the 528 in HBM); [dist_used * 20].
+  std::vector<float> lodds;
 
   // sequences
   std::vector<int64_t> seq_off, row_off;

@@ -342,6 +342,7 @@ struct HmmSlot : DcpPressBatch
 struct HmmLoad
 {
   dcp_hip *x;
+  int gencode;
   float epsilon;
   HmmSlot slot[2];
   PinBuf<float> h_models;            // the null model and the background: two entries in, behind the engine's kept ones ...
@@ -355,8 +356,8 @@ struct HmmLoad
   bool poison;
   double t_parse = 0, t_upload = 0, t_emission = 0, t_rows = 0, t_wait = 0, t_grow = 0;
   int grown = 0; // times the pool was reallocated during the load
-  HmmLoad(dcp_hip *x_, float eps)
-      : x(x_), epsilon(eps), used(x_->pool_used), dist_used(x_->dist_used), models_at(x_->dist_models_used)
+  HmmLoad(dcp_hip *x_, int gencode_id, float eps)
+      : x(x_), gencode(gencode_id), epsilon(eps), used(x_->pool_used), dist_used(x_->dist_used), models_at(x_->dist_models_used)
   {
     char const *e = getenv("DECIPHON_HIP_COST_ORDER");
     poison = e && strcmp(e, "poison") == 0;
@@ -417,7 +418,8 @@ struct HmmLoad
     }
     if (!floats) return 0;
     if (int rc = grow(used + floats)) return rc;
-    return grow_dist(dist_used + nodes); // the kept distributions are sized by the same lines
+    x->lodds.reserve((dist_used + nodes) * 20); // the kept distributions and log-odds are sized by the same lines
+    return grow_dist(dist_used + nodes);
   }
 
   // the slot's batch is through: its buffers are free again
@@ -482,6 +484,7 @@ struct HmmLoad
       hp.dist = (int64_t)dist_used + s.first[i];
       hp.dist_models = (int64_t)models_at;
       hp.epsilon = epsilon;
+      hp.gencode = gencode;
       hp.poisoned = d.poison != 0;
     }
     if (int rc = grow(used + off[n])) return rc;
@@ -503,6 +506,8 @@ struct HmmLoad
     s.launched = true;
     used += off[n];
     dist_used += entries;
+    // (behind the kept ones, in the order of the entries; dcp_hip_load_hmm_sink drops them again when the load fails)
+    for (DcpHmmProfile const &p : s.profiles) x->lodds.insert(x->lodds.end(), p.lodds.begin(), p.lodds.end());
     if (sink)
       for (DcpHmmProfile const &p : s.profiles) sink->profile(p);
     added.insert(added.end(), hps.begin(), hps.end());
@@ -533,7 +538,13 @@ int dcp_hip_load_hmm_sink(struct dcp_hip *x, char const *hmm, int gencode_id, fl
   bool const bad_first = first < 0 || (long)first > reader.count();
   long skip = bad_first ? LONG_MAX : first, limit = bad_first || count < 0 ? -1 : count;
 
-  HmmLoad load(x, epsilon);
+  HmmLoad load(x, gencode_id, epsilon);
+  // the amino log-odds go behind the kept ones batch by batch and count, as the entries in HBM do, once dist_used says so
+  struct KeptLodds
+  {
+    dcp_hip *x;
+    ~KeptLodds() { x->lodds.resize(x->dist_used * 20); }
+  } kept_lodds{x};
   if ((rc = load.models(reader))) return rc;
   if (!bad_first && (rc = load.presize(reader, first, count))) return rc;
   if (sink) sink->models(reader.null_dist(), reader.bg_dist());
@@ -576,6 +587,198 @@ int dcp_hip_load_hmm_sink(struct dcp_hip *x, char const *hmm, int gencode_id, fl
   return 0;
 }
 
+// what the re-emission kernel needs of one profile with kept distributions (press_reemit.h)
+static DcpReemitDesc reemit_desc(HostProfile const &hp)
+{
+  DcpReemitDesc d;
+  d.src = hp.dist;
+  d.rows_off = hp.pool_off;
+  d.copy_off = hp.pool_off + (int64_t)canonical_floats(hp.Kp);
+  d.K = hp.K;
+  d.Kp = hp.Kp;
+  d.stride = hp.Kp + DCP_ROW_HDR;
+  d.cQ = hp.cQ;
+  d.poison = hp.poisoned;
+  d.null_row = (int32_t)hp.dist_models;
+  d.bg_row = d.null_row + 1;
+  return d;
+}
+
+// the first profile without kept distributions refuses dcp_hip_set_epsilon and dcp_hip_set_gencode
+static int refuse_without_dist(dcp_hip *x)
+{
+  for (size_t i = 0; i < x->profiles.size(); ++i)
+    if (x->profiles[i].dist < 0)
+    {
+      char msg[128];
+      snprintf(msg, sizeof msg, "profile %zu has no distributions kept: only dcp_hip_load_hmm keeps them", i);
+      return fail(x, DCP_EFUNCUSE, msg);
+    }
+  return 0;
+}
+
+// Every kept entry again under another table: the nodes' from their amino log-odds (dcp_hip::lodds) by
+// dcp_regencode_entries, on the host threads, chunk by chunk into two pinned buffers whose uploads overlap the
+// recomputation of the next chunk; the null model and the background of every load are the table's.  Then what
+// dcp_hip_set_epsilon runs, once per error rate among the profiles: the emission kernel over the models and the
+// re-emission kernel over the pairs of the profiles at that rate.
+int dcp_hip_set_gencode_sink(struct dcp_hip *x, int gencode_id, DcpGencodeSink *sink)
+{
+  if (!x) return DCP_EFUNCUSE;
+  if (outstanding_batches(x)) return refuse_outstanding(x);
+  float null_lprobs[20];
+  DcpNucltDist null, bg;
+  if (!dcp_setup_models(gencode_id, null_lprobs, null, bg)) return fail(x, DCP_EGENCODEID, "unknown translation table");
+  if (int rc = refuse_without_dist(x)) return rc;
+  size_t const n = x->profiles.size();
+  if (!n) return 0;
+  if (x->lodds.size() != x->dist_used * 20) return fail(x, DCP_EFUNCUSE, "the kept amino log-odds do not match the kept distributions");
+  HIP_TRY(x, hipSetDevice(x->device), DCP_EFUNCUSE);
+  auto const t_begin = std::chrono::steady_clock::now();
+
+  // the profiles by error rate: dcp_press_reemit_launch takes one
+  std::vector<float> rates;
+  std::vector<std::vector<int32_t>> members;
+  std::vector<DcpReemitDesc> desc(n);
+  size_t nodes = 0;
+  for (size_t i = 0; i < n; ++i)
+  {
+    HostProfile const &hp = x->profiles[i];
+    desc[i] = reemit_desc(hp);
+    nodes += (size_t)hp.K;
+    size_t g = 0;
+    while (g < rates.size() && memcmp(&rates[g], &hp.epsilon, sizeof(float)) != 0) ++g;
+    if (g == rates.size())
+    {
+      rates.push_back(hp.epsilon);
+      members.emplace_back();
+    }
+    members[g].push_back((int32_t)i);
+  }
+  size_t const groups = rates.size();
+  std::vector<int64_t> pair_begin(groups + 1, 0);
+  std::vector<std::vector<int32_t>> group_Kp(groups);
+  for (size_t g = 0; g < groups; ++g)
+  {
+    for (int32_t i : members[g]) group_Kp[g].push_back(x->profiles[(size_t)i].Kp);
+    pair_begin[g + 1] = pair_begin[g] + dcp_reemit_tiles((int)members[g].size(), group_Kp[g].data(), nullptr, nullptr, 0);
+  }
+  int64_t const pairs = pair_begin[groups];
+  std::vector<int32_t> pair_profile((size_t)pairs), pair_k0((size_t)pairs);
+  for (size_t g = 0; g < groups; ++g)
+  {
+    int64_t const count = pair_begin[g + 1] - pair_begin[g];
+    int32_t *pp = pair_profile.data() + pair_begin[g];
+    (void)dcp_reemit_tiles((int)members[g].size(), group_Kp[g].data(), pp, pair_k0.data() + pair_begin[g], count);
+    for (int64_t j = 0; j < count; ++j) pp[j] = members[g][(size_t)pp[j]]; // of the group -> of the engine
+  }
+
+  // everything that can fail for want of memory, before the first byte of device memory changes
+  size_t const models = x->dist_models_used, kept = x->dist_used;
+  size_t chunk = ((size_t)64 << 20) / (DCP_PRESS_IN_STRIDE * sizeof(float));
+  if (char const *e = getenv("DECIPHON_HIP_STAGE_MB"))
+    chunk = std::max<size_t>(((size_t)std::max(atol(e), 1L) << 20) / (DCP_PRESS_IN_STRIDE * sizeof(float)), 1);
+  chunk = std::min(chunk, kept);
+  DevBuf<DcpReemitDesc> d_desc;
+  DevBuf<int32_t> d_pair_profile, d_pair_k0;
+  DevBuf<float> d_tables; // per error rate, the null and background tables of every kept model entry
+  PinBuf<float> h_models, stage[2];
+  struct Event
+  {
+    hipEvent_t e = nullptr;
+    ~Event()
+    {
+      if (e) (void)hipEventDestroy(e);
+    }
+  } up0[2], up1[2], ker[2];
+  HIP_TRY(x, d_desc.reserve(n), DCP_ENOMEM);
+  HIP_TRY(x, d_pair_profile.reserve((size_t)pairs), DCP_ENOMEM);
+  HIP_TRY(x, d_pair_k0.reserve((size_t)pairs), DCP_ENOMEM);
+  HIP_TRY(x, d_tables.reserve(groups * models * DCP_PRESS_TABLE), DCP_ENOMEM);
+  HIP_TRY(x, h_models.reserve(models * DCP_PRESS_IN_STRIDE), DCP_ENOMEM);
+  for (int b = 0; b < 2; ++b)
+  {
+    HIP_TRY(x, stage[b].reserve(chunk * DCP_PRESS_IN_STRIDE), DCP_ENOMEM);
+    HIP_TRY(x, hipEventCreate(&up0[b].e), DCP_ENOMEM);
+    HIP_TRY(x, hipEventCreate(&up1[b].e), DCP_ENOMEM);
+    HIP_TRY(x, hipEventCreate(&ker[b].e), DCP_ENOMEM);
+  }
+  // (until the stream is idle the pinned buffers stay: an early return below waits for what it queued)
+  struct Drain
+  {
+    hipStream_t q;
+    ~Drain() { (void)hipStreamSynchronize(q); }
+  } drain{x->stream};
+  HIP_TRY(x, hipMemcpy(d_desc.p, desc.data(), n * sizeof(DcpReemitDesc), hipMemcpyHostToDevice), DCP_EFUNCUSE);
+  HIP_TRY(x, hipMemcpy(d_pair_profile.p, pair_profile.data(), (size_t)pairs * sizeof(int32_t), hipMemcpyHostToDevice), DCP_EFUNCUSE);
+  HIP_TRY(x, hipMemcpy(d_pair_k0.p, pair_k0.data(), (size_t)pairs * sizeof(int32_t), hipMemcpyHostToDevice), DCP_EFUNCUSE);
+
+  // from here on the kept distributions change
+  hipStream_t const q = x->stream;
+  if (sink) sink->regencoded(gencode_id, null, bg);
+  for (size_t m = 0; m + 1 < models; m += 2)
+  {
+    dcp_press_put_entry(h_models.p + m * DCP_PRESS_IN_STRIDE, null);
+    dcp_press_put_entry(h_models.p + (m + 1) * DCP_PRESS_IN_STRIDE, bg);
+  }
+  HIP_TRY(x, hipMemcpyAsync(x->d_dist_models.p, h_models.p, models * DCP_PRESS_IN_STRIDE * sizeof(float), hipMemcpyHostToDevice, q),
+          DCP_EFUNCUSE);
+  double t_host = 0, t_upload = 0;
+  bool busy[2] = {false, false};
+  auto uploaded = [&](int b) -> int {
+    if (!busy[b]) return 0;
+    busy[b] = false;
+    float ms = 0;
+    HIP_TRY(x, hipEventSynchronize(up1[b].e), DCP_EFUNCUSE);
+    HIP_TRY(x, hipEventElapsedTime(&ms, up0[b].e, up1[b].e), DCP_EFUNCUSE);
+    t_upload += ms * 1e-3;
+    return 0;
+  };
+  int b = 0;
+  for (size_t c0 = 0; c0 < kept; c0 += chunk, b ^= 1)
+  {
+    size_t const c = std::min(chunk, kept - c0);
+    if (int rc = uploaded(b)) return rc;
+    auto const t0 = std::chrono::steady_clock::now();
+    (void)dcp_regencode_entries(gencode_id, (int64_t)c, x->lodds.data() + 20 * c0, 16, stage[b].p); // (the table is held)
+    t_host += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (sink) sink->entries(c0, c, stage[b].p);
+    HIP_TRY(x, hipEventRecord(up0[b].e, q), DCP_EFUNCUSE);
+    HIP_TRY(x, hipMemcpyAsync(x->d_dist.p + c0 * DCP_PRESS_IN_STRIDE, stage[b].p, c * DCP_PRESS_IN_STRIDE * sizeof(float),
+                              hipMemcpyHostToDevice, q),
+            DCP_EFUNCUSE);
+    HIP_TRY(x, hipEventRecord(up1[b].e, q), DCP_EFUNCUSE);
+    busy[b] = true;
+  }
+  HIP_TRY(x, hipEventRecord(ker[0].e, q), DCP_EFUNCUSE);
+  for (size_t g = 0; g < groups; ++g)
+  {
+    float *tables = d_tables.p + g * models * DCP_PRESS_TABLE;
+    if (dcp_press_emission_launch(x->d_dist_models.p, tables, (int)models, rates[g], q))
+      return fail(x, DCP_EFUNCUSE, "the emission kernel could not be launched");
+    if (dcp_press_reemit_launch(x->d_dist.p, tables, d_desc.p, d_pair_profile.p + pair_begin[g], d_pair_k0.p + pair_begin[g],
+                                pair_begin[g + 1] - pair_begin[g], rates[g], x->d_pool.p, q))
+      return fail(x, DCP_EFUNCUSE, "the re-emission kernel could not be launched");
+  }
+  HIP_TRY(x, hipEventRecord(ker[1].e, q), DCP_EFUNCUSE);
+  for (int s = 0; s < 2; ++s)
+    if (int rc = uploaded(s)) return rc;
+  HIP_TRY(x, hipStreamSynchronize(q), DCP_EFUNCUSE);
+  if (getenv("DECIPHON_HIP_TIMING"))
+  {
+    float ms = 0;
+    HIP_TRY(x, hipEventElapsedTime(&ms, ker[0].e, ker[1].e), DCP_EFUNCUSE);
+    fprintf(stderr,
+            "dcp_hip_set_gencode: %zu profiles, %zu nodes, table %d, %zu error rates; host recomputation %.6f s, upload %.6f s, "
+            "kernels %.6f s, wall %.6f s\n",
+            n, nodes, gencode_id, groups, t_host, t_upload, ms * 1e-3,
+            std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count());
+  }
+  for (HostProfile &hp : x->profiles) hp.gencode = gencode_id;
+  ++x->gen;
+  return 0;
+}
+
 extern "C" {
 
 int dcp_hip_load_hmm(struct dcp_hip *x, char const *hmm, int gencode_id, float epsilon, int first, int count)
@@ -593,13 +796,7 @@ int dcp_hip_set_epsilon(struct dcp_hip *x, float epsilon)
   if (outstanding_batches(x)) return refuse_outstanding(x);
   if (!(epsilon >= 0.0f && epsilon <= 1.0f)) return fail(x, DCP_EFUNCUSE, "epsilon must lie in [0, 1]");
   size_t const n = x->profiles.size();
-  for (size_t i = 0; i < n; ++i)
-    if (x->profiles[i].dist < 0)
-    {
-      char msg[128];
-      snprintf(msg, sizeof msg, "profile %zu has no distributions kept: only dcp_hip_load_hmm keeps them", i);
-      return fail(x, DCP_EFUNCUSE, msg);
-    }
+  if (int rc = refuse_without_dist(x)) return rc;
   if (!n) return 0;
   HIP_TRY(x, hipSetDevice(x->device), DCP_EFUNCUSE);
 
@@ -609,17 +806,8 @@ int dcp_hip_set_epsilon(struct dcp_hip *x, float epsilon)
   for (size_t i = 0; i < n; ++i)
   {
     HostProfile const &hp = x->profiles[i];
-    DcpReemitDesc &d = desc[i];
-    d.src = hp.dist;
-    d.rows_off = hp.pool_off;
-    d.copy_off = hp.pool_off + (int64_t)canonical_floats(hp.Kp);
-    d.K = hp.K;
-    d.Kp = Kp[i] = hp.Kp;
-    d.stride = hp.Kp + DCP_ROW_HDR;
-    d.cQ = hp.cQ;
-    d.poison = hp.poisoned;
-    d.null_row = (int32_t)hp.dist_models;
-    d.bg_row = d.null_row + 1;
+    DcpReemitDesc &d = desc[i] = reemit_desc(hp);
+    Kp[i] = hp.Kp;
     nodes += (size_t)hp.K;
     written += (size_t)DCP_TABLE_SIZE * ((size_t)d.stride + (hp.cQ ? (size_t)dcp_cost_order_stride(hp.cQ, hp.cW) : 0));
   }
@@ -670,6 +858,14 @@ float dcp_hip_profile_epsilon(struct dcp_hip const *x, int i)
 {
   if (!x || i < 0 || i >= (int)x->profiles.size() || x->profiles[(size_t)i].dist < 0) return NAN;
   return x->profiles[(size_t)i].epsilon;
+}
+
+int dcp_hip_set_gencode(struct dcp_hip *x, int gencode_id) { return dcp_hip_set_gencode_sink(x, gencode_id, nullptr); }
+
+int dcp_hip_profile_gencode(struct dcp_hip const *x, int i)
+{
+  if (!x || i < 0 || i >= (int)x->profiles.size() || x->profiles[(size_t)i].dist < 0) return 0;
+  return x->profiles[(size_t)i].gencode;
 }
 
 int64_t dcp_hip_dist_bytes(struct dcp_hip const *x)
@@ -756,6 +952,7 @@ void dcp_hip_clear_profiles(struct dcp_hip *x)
   x->profiles.clear();
   x->committed = 0;
   x->dist_used = x->dist_models_used = 0;
+  std::vector<float>().swap(x->lodds);
   (void)hipSetDevice(x->device);
   x->d_dist.release();
   x->d_dist_models.release();

@@ -4,6 +4,8 @@
 #include "dcp_errors.h"
 #include "dcp_types.h"
 #include "host_logic.h"
+#include "parallel_for.h"
+#include "press_batch.h"
 
 #include <ctype.h>
 #include <math.h>
@@ -159,17 +161,21 @@ void DcpHmmReader::close()
   end_ = false;
 }
 
-int DcpHmmReader::open(char const *path, int gencode_id)
+bool dcp_setup_models(int gencode_id, float null_lprobs[20], DcpNucltDist &null, DcpNucltDist &bg)
 {
-  close();
   // init_null_lprobs (c-core/hmm_reader.c:76-102): HMMER3's Swiss-Prot 50.8 amino frequencies
   static double const freq[20] = {0.0787945, 0.0151600, 0.0535222, 0.0668298, 0.0397062, 0.0695071, 0.0229198,
                                   0.0590092, 0.0594422, 0.0963728, 0.0237718, 0.0414386, 0.0482904, 0.0395639,
                                   0.0540978, 0.0683364, 0.0540687, 0.0673417, 0.0114135, 0.0304133};
-  for (int i = 0; i < 20; ++i) null_lprobs_[i] = logf((float)freq[i]);
+  for (int i = 0; i < 20; ++i) null_lprobs[i] = logf((float)freq[i]);
   float const zero[20] = {};
-  if (!dcp_setup_nuclt_dist(gencode_id, null_lprobs_, null_) || !dcp_setup_nuclt_dist(gencode_id, zero, bg_))
-    return DCP_EGENCODEID;
+  return dcp_setup_nuclt_dist(gencode_id, null_lprobs, null) && dcp_setup_nuclt_dist(gencode_id, zero, bg);
+}
+
+int DcpHmmReader::open(char const *path, int gencode_id)
+{
+  close();
+  if (!dcp_setup_models(gencode_id, null_lprobs_, null_, bg_)) return DCP_EGENCODEID;
   gencode_ = gencode_id;
   if (!path || !(fp_ = fopen(path, "rb"))) return DCP_EFOPEN;
   // press.c: count_proteins
@@ -256,6 +262,7 @@ int DcpHmmReader::profile(DcpHmmProfile &x)
   x.consensus.assign((size_t)n, ' ');
   std::vector<float> T((size_t)(n + 1) * 7); // T[0]: the transitions that follow COMPO (node 0)
   x.nodes.resize((size_t)n);
+  x.lodds.resize((size_t)n * 20);
   float v[20];
 
   // COMPO (optional; its emissions are not used), the insert emissions of node 0 and its transitions
@@ -280,7 +287,7 @@ int DcpHmmReader::profile(DcpHmmProfile &x)
     // "<k> <20 match values> <MAP> <CONS> ...", then 20 insert values, then 7 transitions
     if (t.str(0) != std::to_string(k + 1) || !values(t, 1, 20, v) || t.size() < 23) return DCP_EENDOFNODES;
     x.consensus[(size_t)k] = t.at[22][0];
-    float lodds[20];
+    float *lodds = x.lodds.data() + 20 * (size_t)k;
     for (int i = 0; i < 20; ++i) lodds[i] = v[i] - null_lprobs_[i]; // model_add_node, c-core/model.c:67-69
     dcp_setup_nuclt_dist(gencode_, lodds, x.nodes[(size_t)k]);
     if (!line() || !values(Tokens(line_), 0, 20, v)) return DCP_EENDOFNODES;
@@ -368,6 +375,43 @@ int dcp_hmm_read(struct dcp_hmm const *x, float *trans, float *BMk, float *nuclt
   }
   if (accession) memcpy(accession, p.accession.c_str(), p.accession.size() + 1);
   if (consensus) memcpy(consensus, p.consensus.c_str(), K + 1);
+  return 0;
+}
+
+int dcp_hmm_read_lodds(struct dcp_hmm const *x, float *lodds)
+{
+  if (!x || !x->have || !lodds) return DCP_EFUNCUSE;
+  memcpy(lodds, x->profile.lodds.data(), x->profile.lodds.size() * sizeof(float));
+  return 0;
+}
+
+int dcp_hmm_models(int gencode_id, float *nucltp8, float *codonm250)
+{
+  float null_lprobs[20];
+  DcpNucltDist d[2];
+  if (!dcp_setup_models(gencode_id, null_lprobs, d[0], d[1])) return DCP_EGENCODEID;
+  for (int e = 0; e < 2; ++e)
+  {
+    if (nucltp8) memcpy(nucltp8 + 4 * e, d[e].nucltp, sizeof d[e].nucltp);
+    if (codonm250) memcpy(codonm250 + 125 * e, d[e].codonm, sizeof d[e].codonm);
+  }
+  return 0;
+}
+
+int dcp_regencode_entries(int gencode_id, int64_t n, float const *lodds, int max_threads, float *entries)
+{
+  if (n < 0 || (n > 0 && (!lodds || !entries))) return DCP_EFUNCUSE;
+  {
+    DcpNucltDist probe;
+    float const zero[20] = {};
+    if (!dcp_setup_nuclt_dist(gencode_id, zero, probe)) return DCP_EGENCODEID;
+  }
+  unsigned const threads = (unsigned)std::min(std::max(max_threads, 1), 16);
+  dcp_parallel_for((size_t)n, threads, 64, 64, [=](size_t i) {
+    DcpNucltDist d;
+    dcp_setup_nuclt_dist(gencode_id, lodds + 20 * i, d);
+    dcp_press_put_entry(entries + i * DCP_PRESS_IN_STRIDE, d);
+  });
   return 0;
 }
 

@@ -34,11 +34,17 @@ struct DcpHmmProfile
   std::vector<float> trans;        // [(K+1) * 7] MM MI MD IM II DM DD: node i holds T[min(i + 1, K)]
   std::vector<float> BMk;          // [K] occupancy entry (entry_dist = 2)
   std::vector<DcpNucltDist> nodes; // [K] match distribution of node n; node K repeats node K - 1
+  std::vector<float> lodds;        // [K * 20] the amino log-odds `nodes` were set up from: they hold under every table
 };
 
 // Sets up the nucleotide distribution of amino log-odds `lodds[20]` (ACDEFGHIKLMNPQRSTVWY) under NCBI
 // translation table `gencode_id` (setup_nuclt_dist, c-core/model.c:397-411).  false: unknown table.
 bool dcp_setup_nuclt_dist(int gencode_id, float const lodds[20], DcpNucltDist &out);
+
+// The models every profile of a file shares (init_null_lprobs, c-core/hmm_reader.c:76-102): the log of HMMER3's
+// Swiss-Prot amino frequencies, the null model set up from them and the background set up from log-odds 0, under
+// table `gencode_id`.  false: unknown table.
+bool dcp_setup_models(int gencode_id, float null_lprobs[20], DcpNucltDist &null, DcpNucltDist &bg);
 
 // Reader of a HMMER3 text file, one profile per next().  All return 0 or a DCP_E* code.
 class DcpHmmReader

@@ -415,6 +415,21 @@ int dcp_scan_set_epsilon(struct dcp_scan *x, float epsilon)
   return 0;
 }
 
+int dcp_scan_set_gencode(struct dcp_scan *x, int gencode_id)
+{
+  // the arguments first: without a GPU the codes are still told apart
+  if (!x) return raise(DCP_EFUNCUSE, __func__);
+  if (!x->eng || !x->hmm) return raise(DCP_EFUNCUSE, __func__, "the scan was not set up by dcp_scan_setup_hmm");
+  {
+    DcpNucltDist probe;
+    float const zero[20] = {};
+    if (!dcp_setup_nuclt_dist(gencode_id, zero, probe)) return raise(DCP_EGENCODEID, __func__);
+  }
+  // the distributions the rows' codons are decoded from are the ones the engine recomputes (scan_rows.h)
+  if (int const rc = dcp_hip_set_gencode_sink(x->eng, gencode_id, x->hmm)) return raise(rc, __func__, dcp_hip_strerror(x->eng));
+  return 0;
+}
+
 int dcp_scan_partition_range(struct dcp_scan const *x, int *first, int *count)
 {
   if (!x || !first || !count) return DCP_EFUNCUSE;

@@ -2,6 +2,7 @@
 #include "scan_rows.h"
 #include "dcp_errors.h"
 #include "parallel_for.h"
+#include "press_kernel.h"
 #include <algorithm>
 #include <stdio.h>
 #include <string.h>
@@ -90,6 +91,19 @@ std::string format_row(dcp_batch::Seq const &seq, int window, int wstart, int ws
 }
 
 } // namespace
+
+// the engine's kept entries are the nodes of the scan's profiles, in order: one load, nothing else resident
+void DcpHmmDecoders::entries(size_t, size_t n, float const *in)
+{
+  for (size_t e = 0; e < n; ++e, in += DCP_PRESS_IN_STRIDE)
+  {
+    while (at_profile < nodes.size() && at_node == nodes[at_profile].size()) ++at_profile, at_node = 0;
+    if (at_profile == nodes.size()) return;
+    DcpNucltDist &d = nodes[at_profile][at_node++];
+    memcpy(d.nucltp, in, sizeof d.nucltp);
+    memcpy(d.codonm, in + 4, sizeof d.codonm);
+  }
+}
 
 int DcpHmmDecoders::read_decoder(int i, DcpDecoder &x) const
 {

@@ -47,7 +47,8 @@ struct DcpDbDecoders : DcpDecoderSource
 
 // A scan set up from a HMMER3 file (dcp_scan_setup_hmm) has no file to read them back from: it keeps the fp32 nucltp
 // and codonm of every node, 516 bytes each, as the load shows them (engine_hmm.h).
-struct DcpHmmDecoders : DcpDecoderSource, DcpHmmSink
+// dcp_scan_set_gencode: the engine shows the entries it recomputes (DcpGencodeSink) and they replace the kept ones.
+struct DcpHmmDecoders : DcpDecoderSource, DcpHmmSink, DcpGencodeSink
 {
   int gencode = 0;
   float epsilon = 0; // of the engine's tables: dcp_scan_set_epsilon moves both, between runs (a run's decoders copy it)
@@ -55,7 +56,16 @@ struct DcpHmmDecoders : DcpDecoderSource, DcpHmmSink
   std::vector<std::vector<DcpNucltDist>> nodes; // by profile: [K]
   void models(DcpNucltDist const &n, DcpNucltDist const &b) override { null = n, bg = b; }
   void profile(DcpHmmProfile const &p) override { nodes.emplace_back(p.nodes.begin(), p.nodes.begin() + p.core_size); }
+  void regencoded(int gencode_id, DcpNucltDist const &n, DcpNucltDist const &b) override
+  {
+    gencode = gencode_id, null = n, bg = b;
+    at_profile = at_node = 0;
+  }
+  void entries(size_t first, size_t n, float const *in) override;
   int read_decoder(int i, DcpDecoder &out) const override;
+
+private:
+  size_t at_profile = 0, at_node = 0; // where the next entry of a dcp_scan_set_gencode goes
 };
 
 // The rows of one dcp_scan_run.  Per path batch, in this order: warm_decoders, wait_steps_copied, dcp_hip_path, spans,

@@ -57,6 +57,8 @@ def load_library() -> C.CDLL:
     L.dcp_hip_set_epsilon.argtypes = [vp, C.c_float]
     L.dcp_hip_profile_epsilon.argtypes = [vp, i32]
     L.dcp_hip_profile_epsilon.restype = C.c_float
+    L.dcp_hip_set_gencode.argtypes = [vp, i32]
+    L.dcp_hip_profile_gencode.argtypes = [vp, i32]
     L.dcp_hip_dist_bytes.argtypes = [vp]
     L.dcp_hip_dist_bytes.restype = C.c_int64
     L.dcp_hip_profile_floats.argtypes = [vp, i32]
@@ -206,6 +208,16 @@ class Engine:
     def profile_epsilon(self, i: int) -> float:
         """The error rate profile i is at; NaN when it did not come by load_hmm."""
         return float(self.lib.dcp_hip_profile_epsilon(self.h, i))
+
+    def set_gencode(self, gencode: int) -> None:
+        """Every profile again under translation table `gencode`, each at its own error rate, without the files: the
+        pool load_hmm of the same files would leave under that table.  Only for engines all of whose profiles came by
+        load_hmm (DCP_EFUNCUSE otherwise); DCP_EGENCODEID for a table not held."""
+        self._check(self.lib.dcp_hip_set_gencode(self.h, int(gencode)))
+
+    def profile_gencode(self, i: int) -> int:
+        """The translation table profile i is under; 0 when it did not come by load_hmm."""
+        return int(self.lib.dcp_hip_profile_gencode(self.h, i))
 
     @property
     def dist_bytes(self) -> int:

@@ -96,6 +96,9 @@ def _lib():
     L.dcp_hmm_core_size.argtypes = [vp]
     L.dcp_hmm_has_ga.argtypes = [vp]
     L.dcp_hmm_read.argtypes = [vp, vp, vp, vp, vp, C.c_char_p, C.c_char_p]
+    L.dcp_hmm_read_lodds.argtypes = [vp, vp]
+    L.dcp_hmm_models.argtypes = [i32, vp, vp]
+    L.dcp_regencode_entries.argtypes = [i32, C.c_int64, vp, i32, vp]
     L._host_ready = True
     return L
 
@@ -151,12 +154,46 @@ class HmmFile:
         p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
         if rc := self.lib.dcp_hmm_read(self.h, p(trans), p(BMk), p(nucltp), p(codonm), acc, cons):
             raise HipError(rc)
+        lodds = np.zeros((K, 20), np.float32)
+        if rc := self.lib.dcp_hmm_read_lodds(self.h, p(lodds)):
+            raise HipError(rc)
         return dict(accession=acc.value.decode(), consensus=cons.value.decode(), core_size=K,
-                    has_ga=bool(self.lib.dcp_hmm_has_ga(self.h)), trans=trans, BMk=BMk, nucltp=nucltp, codonm=codonm)
+                    has_ga=bool(self.lib.dcp_hmm_has_ga(self.h)), trans=trans, BMk=BMk, nucltp=nucltp, codonm=codonm,
+                    lodds=lodds)
 
     def __iter__(self):
         while (p := self.next()) is not None:
             yield p
+
+    @staticmethod
+    def models(gencode: int = 1):
+        """(nucltp[2, 4], codonm[2, 125]): the null model, then the background, under translation table `gencode` --
+        entries 0 and 1 of every profile of a file opened under it (dcp_hmm_models); no file is needed."""
+        return hmm_models(gencode)
+
+
+ENTRY_FLOATS = 132  # one kept entry (csrc/press_kernel.h): nucltp[4], codonm[125], 3 floats of padding
+
+
+def hmm_models(gencode: int = 1):
+    """See HmmFile.models."""
+    nucltp = np.zeros((2, 4), np.float32)
+    codonm = np.zeros((2, 125), np.float32)
+    if rc := _lib().dcp_hmm_models(int(gencode), nucltp.ctypes.data_as(C.c_void_p), codonm.ctypes.data_as(C.c_void_p)):
+        raise HipError(rc)
+    return nucltp, codonm
+
+
+def regencode_entries(gencode: int, lodds, max_threads: int = 16) -> np.ndarray:
+    """entries float32[n, 132] -- nucltp[4], codonm[125], padding -- of n nodes under translation table `gencode`,
+    from their amino log-odds lodds[n, 20] (a profile's "lodds" of HmmFile, which hold under every table): what
+    Engine.set_gencode puts in place of the kept distributions (dcp_regencode_entries)."""
+    lo = np.ascontiguousarray(lodds, np.float32).reshape(-1, 20)
+    out = np.full((len(lo), ENTRY_FLOATS), np.nan, np.float32)
+    if rc := _lib().dcp_regencode_entries(int(gencode), len(lo), lo.ctypes.data_as(C.c_void_p), int(max_threads),
+                                          out.ctypes.data_as(C.c_void_p)):
+        raise HipError(rc)
+    return out
 
 
 class Database:

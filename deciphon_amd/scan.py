@@ -28,6 +28,7 @@ def _lib():
     L.dcp_scan_setup_partition_balanced.argtypes = L.dcp_scan_setup_partition.argtypes
     L.dcp_scan_setup_hmm.argtypes = [vp, C.c_char_p, i32, C.c_float, C.c_bool, C.c_bool, _CALLBACK, vp]
     L.dcp_scan_set_epsilon.argtypes = [vp, C.c_float]
+    L.dcp_scan_set_gencode.argtypes = [vp, i32]
     L.dcp_scan_partition_range.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
     L.dcp_scan_run.argtypes = [vp, vp, C.c_char_p]
     L.dcp_scan_interrupt.argtypes = [vp]
@@ -134,6 +135,12 @@ class Scan:
         """A scan made by from_hmm at another error rate (dcp_scan_set_epsilon): the next run writes the rows of a
         fresh from_hmm at `epsilon`.  Not while run() is running."""
         if rc := self._lib.dcp_scan_set_epsilon(self._cscan, float(epsilon)):
+            raise DeciphonError(rc)
+
+    def set_gencode(self, gencode: int):
+        """A scan made by from_hmm under another translation table (dcp_scan_set_gencode): the next run writes the
+        rows of a fresh from_hmm at `gencode` and the error rate the scan is at.  Not while run() is running."""
+        if rc := self._lib.dcp_scan_set_gencode(self._cscan, int(gencode)):
             raise DeciphonError(rc)
 
     def run(self, snap, batch: Batch):

@@ -175,6 +175,15 @@ int dcp_scan_setup_hmm(struct dcp_scan *, char const *hmm, int gencode_id, float
  * all checked before the GPU is touched.  Not to be called while dcp_scan_run runs on that scan (nothing locks).  The
  * rows of the last run (dcp_scan_product) stay valid. */
 int dcp_scan_set_epsilon(struct dcp_scan *, float epsilon);
+/* Not in the reference: a scan set up by dcp_scan_setup_hmm under another translation table, at the error rate it is
+ * at, without reading the file again (dcp_hip_set_gencode: the nodes' distributions are derived again on the host from
+ * their amino log-odds, the tables rewritten on the GPU, in place).  The scan's own distributions, which the codons of
+ * its rows are decoded from, come from the same recomputation.  The next dcp_scan_run writes the rows a fresh
+ * dcp_scan_setup_hmm at gencode_id would, codons and amino acids included.  DCP_EFUNCUSE for NULL, for a scan that is
+ * not set up or was set up from a pressed file (a .dcp holds no amino log-odds), then DCP_EGENCODEID for a table not
+ * held -- all checked before the GPU is touched, the scan left as it was.  Not to be called while dcp_scan_run runs on
+ * that scan.  The rows of the last run (dcp_scan_product) stay valid. */
+int dcp_scan_set_gencode(struct dcp_scan *, int gencode_id);
 /* Number of product rows the last dcp_scan_run wrote, and row i (without newline).  The pointer stands until the next
  * dcp_scan_run or dcp_scan_del of that scan.  Once the scan has spilled rows to run files (dcp_scan_product_stats:
  * runs > 0; DECIPHON_HIP_PRODUCT_MB) it stands only until the next dcp_scan_product on that scan, and

@@ -87,11 +87,32 @@ int dcp_hip_load_hmm(struct dcp_hip *, char const *hmm, int gencode_id, float ep
  * outstanding DCP_EFUNCUSE (as every call that changes the inputs); epsilon outside [0, 1] or NaN DCP_EFUNCUSE; a
  * profile, committed or not, that came by dcp_hip_add_profile, _add_protein or _load_dcp -- no distributions are
  * kept for those -- DCP_EFUNCUSE, dcp_hip_strerror naming the first; device errors.  Without profiles it returns 0 and
- * does nothing.  The translation table cannot be changed this way.  DECIPHON_HIP_TIMING prints profiles, nodes, bytes
- * written and the kernel's seconds. */
+ * does nothing.  The translation table stays what it is: dcp_hip_set_gencode changes it.  DECIPHON_HIP_TIMING prints
+ * profiles, nodes, bytes written and the kernel's seconds. */
 int dcp_hip_set_epsilon(struct dcp_hip *, float epsilon);
 /* the error rate profile `index` is at; NaN for a profile without kept distributions (and for a bad index or NULL) */
 float dcp_hip_profile_epsilon(struct dcp_hip const *, int index);
+/* The profiles that came by dcp_hip_load_hmm again under another translation table, without their files.  The kept
+ * distributions themselves depend on the table, but what they are derived from does not: a load also keeps every
+ * node's 20 amino log-odds, 80 bytes in host memory (not counted by dcp_hip_dist_bytes).  This call derives every
+ * node's nucltp and codonm from them again under gencode_id -- on the host, by the function the load uses
+ * (dcp_regencode_entries, include/deciphon_host.h), on up to 16 threads --, uploads them over the kept ones in chunks
+ * (64 MiB of pinned memory, twice; DECIPHON_HIP_STAGE_MB shrinks them) with the table's null model and background for
+ * every load, and writes the rows as dcp_hip_set_epsilon does, once per error rate among the profiles: every profile
+ * keeps its own.  Afterwards the pool is, word for word, what dcp_hip_load_hmm of the same files and ranges at
+ * (gencode_id, that profile's error rate) leaves, whatever tables the profiles were under; the table that is there
+ * already is written all the same.  Offsets and sizes stay, nothing needs committing again, and it is a change of the
+ * inputs (below) like dcp_hip_set_epsilon.
+ * Failures, in this order, each leaving the pool, the kept distributions and every query as they were: NULL
+ * DCP_EFUNCUSE; cost batches outstanding DCP_EFUNCUSE; a table not held DCP_EGENCODEID; a profile without kept
+ * distributions DCP_EFUNCUSE, dcp_hip_strerror naming the first; allocations, all made before the first byte of device
+ * memory changes, DCP_ENOMEM.  A device error after that is reported, and the tables and kept distributions are then
+ * undefined until dcp_hip_clear_profiles.  Without profiles it returns 0 (after the checks above) and does nothing.
+ * DECIPHON_HIP_TIMING prints one line "dcp_hip_set_gencode:" with profiles, nodes and the seconds of the host
+ * recomputation, of the uploads and of the kernels. */
+int dcp_hip_set_gencode(struct dcp_hip *, int gencode_id);
+/* the translation table profile `index` is under; 0 for a profile without kept distributions, a bad index or NULL */
+int dcp_hip_profile_gencode(struct dcp_hip const *, int index);
 /* Bytes of HBM the kept distributions occupy: 528 per node of every profile loaded from a HMMER3 file, and 2 x 528 per
  * dcp_hip_load_hmm that added profiles (its null model and background).  dcp_hip_clear_profiles frees them. */
 int64_t dcp_hip_dist_bytes(struct dcp_hip const *);
@@ -135,8 +156,8 @@ void dcp_hip_xtrans(int seq_size, int multi_hits, int hmmer3_compat, float xt[DC
  * A window is the half-open range [start, stop) of sequence `seq` scored against
  * `profile`, i.e. one process_window call (c-core/thread.c:98-128).
  *
- * The inputs: every accepted call of dcp_hip_add_profile, _add_protein, _load_dcp, _load_hmm, _set_epsilon (with
- * profiles resident), _commit_profiles,
+ * The inputs: every accepted call of dcp_hip_add_profile, _add_protein, _load_dcp, _load_hmm, _set_epsilon and
+ * _set_gencode (with profiles resident), _commit_profiles,
  * _clear_profiles, _set_sequences, _set_mode or _set_xtrans_table changes them, even one that sets what was
  * there already (a call refused for outstanding batches or for its arguments changes nothing).  Two things
  * outlive a call and are tied to the inputs they were made from: the staged window list (dcp_hip_stage) and the

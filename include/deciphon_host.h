@@ -60,6 +60,18 @@ int dcp_hmm_core_size(struct dcp_hmm const *);
 int dcp_hmm_has_ga(struct dcp_hmm const *);
 int dcp_hmm_read(struct dcp_hmm const *, float *trans, float *BMk, float *nucltp, float *codonm, char *accession,
                  char *consensus);
+/* What of a profile depends on the translation table, and what it is derived from.  dcp_hmm_read_lodds: lodds[K*20] of
+ * the profile just read, node n's 20 amino log-odds (match value minus the null model's, model_add_node,
+ * c-core/model.c:67-69) -- the same words under whichever table the file was opened.  dcp_regencode_entries: the nucltp
+ * and codonm of n nodes under table gencode_id from their lodds[n*20], by the reader's own function on at most
+ * max_threads host threads (clamped to 1..16; the result does not depend on it), as the entries a load keeps
+ * (csrc/press_kernel.h): entries[n*132], per node nucltp[4], codonm[125] and 3 floats of padding, 0.  DCP_EGENCODEID
+ * for a table not held, DCP_EFUNCUSE for n < 0 or NULL with n > 0.  dcp_hmm_models: the null model, then the
+ * background, under gencode_id, as entries 0 and 1 of dcp_hmm_read -- nucltp8[2*4], codonm250[2*125], either may be
+ * NULL; no file is needed.  DCP_EGENCODEID for a table not held. */
+int dcp_hmm_read_lodds(struct dcp_hmm const *, float *lodds);
+int dcp_regencode_entries(int gencode_id, int64_t n, float const *lodds, int max_threads, float *entries);
+int dcp_hmm_models(int gencode_id, float *nucltp8, float *codonm250);
 
 /* partition_size (c-core/partition_size.c:13-16): proteins of partition idx out of nparts */
 long dcp_partition_size(long nelems, long nparts, long idx);
