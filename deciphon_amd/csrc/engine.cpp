@@ -1,5 +1,5 @@
 // engine.cpp -- device-resident state and the C ABI of include/deciphon_hip.h: the engine itself, its sequences and
-// mode, staging and launching of window lists.  Profiles: engine_profiles.cpp; cost passes: engine_cost.cpp; path pass:
+// mode, staging and launching of window lists.  Profiles: engine_profiles.cpp, engine_hmm.cpp; cost passes: engine_cost.cpp; path pass:
 // engine_path.cpp; the state they share: engine_internal.h.
 //
 // HBM layout (one engine = one GPU):

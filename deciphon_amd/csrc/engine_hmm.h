@@ -1,5 +1,6 @@
-// engine_hmm.h -- the C++ entry behind dcp_hip_load_hmm (engine_profiles.cpp), for the scan: the same load, and every
-// profile that is loaded is shown to a sink while its model is at hand.  Inside the library only (exports.map).
+// engine_hmm.h -- the C++ entries behind dcp_hip_load_hmm and dcp_hip_set_gencode (engine_hmm.cpp), for the scan: the
+// same calls, and what is loaded or recomputed is shown to a sink while it is at hand.  Inside the library only
+// (exports.map).
 #pragma once
 #include "../../include/deciphon_hip.h"
 #include "hmm_model.h"

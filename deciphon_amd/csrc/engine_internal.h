@@ -1,5 +1,5 @@
 // engine_internal.h -- the engine's state and what its translation units share (engine.cpp, engine_profiles.cpp,
-// engine_cost.cpp, engine_path.cpp).  Everything here but struct dcp_hip has C++ linkage in namespace dcp_engine, which
+// engine_hmm.cpp, engine_cost.cpp, engine_path.cpp).  Everything here but struct dcp_hip has C++ linkage in namespace dcp_engine, which
 // exports.map keeps inside the library.
 #pragma once
 #include "../../include/deciphon_hip.h"
@@ -62,13 +62,13 @@ template <class T> struct PinBuf
   {
     if (p) (void)hipHostFree(p);
   }
-  hipError_t reserve(size_t n)
+  hipError_t reserve(size_t n) { return n <= cap ? hipSuccess : reserve_exact(n + n / 4 + 1024); }
+  // exactly `want` elements: for a buffer sized once (reserve() adds a quarter, for those that grow from call to call)
+  hipError_t reserve_exact(size_t want)
   {
-    if (n <= cap) return hipSuccess;
     if (p) (void)hipHostFree(p);
     p = nullptr;
     cap = 0;
-    size_t const want = n + n / 4 + 1024;
     hipError_t const e = hipHostMalloc((void **)&p, want * sizeof(T), hipHostMallocDefault);
     if (e != hipSuccess)
     {
@@ -79,6 +79,47 @@ template <class T> struct PinBuf
     return hipSuccess;
   }
 };
+
+// an event that is destroyed with its owner
+struct Event
+{
+  hipEvent_t e = nullptr;
+  Event() = default;
+  Event(Event const &) = delete;
+  Event &operator=(Event const &) = delete;
+  ~Event()
+  {
+    if (e) (void)hipEventDestroy(e);
+  }
+  hipError_t create(unsigned flags = hipEventDefault) { return hipEventCreateWithFlags(&e, flags); }
+};
+
+// Waits for the stream when it goes: declared behind the pinned buffers and events that queued work uses, so that an
+// early return after queuing drains the stream before they are freed.
+struct StreamDrain
+{
+  hipStream_t q;
+  ~StreamDrain() { (void)hipStreamSynchronize(q); }
+};
+
+// DECIPHON_HIP_STAGE_MB: bytes of a pinned staging chunk (at least 1 MiB), `unset` without it.  The callers convert to
+// their own unit and apply their own floor.
+inline size_t stage_bytes(size_t unset)
+{
+  char const *e = getenv("DECIPHON_HIP_STAGE_MB");
+  return e ? (size_t)std::max(atol(e), 1L) << 20 : unset;
+}
+
+// DECIPHON_HIP_COST_ORDER, read at ingest: 0 = no cost-order copies; "poison" = copies, and the canonical match columns
+// of those profiles staged as 0 (a test's proof that the narrow kernels read the copy: their scores stay the oracle's).
+enum CostOrder { COST_ORDER_OFF, COST_ORDER_ON, COST_ORDER_POISON };
+inline CostOrder cost_order_mode()
+{
+  char const *e = getenv("DECIPHON_HIP_COST_ORDER");
+  if (!e) return COST_ORDER_ON;
+  if (e[0] == '0') return COST_ORDER_OFF;
+  return strcmp(e, "poison") == 0 ? COST_ORDER_POISON : COST_ORDER_ON;
+}
 
 // DECIPHON_HIP_PATH_STRICT=1: the path pass's budget is a hard limit (what exceeds it is a DCP_ENOMEM)
 inline bool path_budget_strict()
@@ -173,6 +214,29 @@ struct HostProfile
   float epsilon = 0;       // the error rate its rows are at
   int gencode = 0;         // the translation table its rows are under (dcp_hip_set_gencode); 0: no distributions kept
   bool poisoned = false;   // DECIPHON_HIP_COST_ORDER=poison at its load: its canonical match columns are 0
+};
+
+// Where a profile's parts lie in the pool, in floats from HostProfile::pool_off (and in a host staging buffer, from its
+// first float): rows[1364][DCP_ROW_HDR + Kp] | trans[8][Kp] | +inf up to 128 bytes | the cost-order copy
+// [1364][dcp_cost_order_stride], for a profile that has one.  Every profile, and the copy behind its tables, starts on
+// a line; the padding is +inf wherever a profile is staged, so that a pool's words depend on its profiles alone.
+// (The cost kernels hold the same sum on the device side: viterbi_kernels.hip, viterbi_body.h.)
+struct ProfileLayout
+{
+  size_t stride;    // of a row: DCP_ROW_HDR + Kp
+  size_t rows = 0;
+  size_t trans;
+  size_t pad_begin; // behind trans ...
+  size_t pad_end;   // ... up to the next multiple of 32 floats
+  size_t copy;      // = pad_end
+  size_t total;     // = copy without a cost-order copy
+  ProfileLayout(int Kp, int cQ, int cW)
+      : stride((size_t)Kp + DCP_ROW_HDR), trans((size_t)DCP_TABLE_SIZE * stride),
+        pad_begin(trans + (size_t)DCP_NUM_TRANS * (size_t)Kp), pad_end((pad_begin + 31) & ~(size_t)31), copy(pad_end),
+        total(copy + (cQ ? (size_t)DCP_TABLE_SIZE * (size_t)dcp_cost_order_stride(cQ, cW) : 0))
+  {
+  }
+  explicit ProfileLayout(HostProfile const &hp) : ProfileLayout(hp.Kp, hp.cQ, hp.cW) {}
 };
 
 struct PathResult
@@ -445,5 +509,16 @@ inline int refuse_outstanding(dcp_hip *x)
 {
   return fail(x, DCP_EFUNCUSE, "cost batches are outstanding (dcp_hip_cost_hits_begin): end them first");
 }
+
+// engine_profiles.cpp, for the loads of engine_hmm.cpp as well:
+// class, shape, padded size and cost-order shape of a profile of K positions (pool_off is left 0)
+int describe(dcp_hip *x, int K, char const *accession, HostProfile &hp);
+// grows a device buffer to `floats`, keeping its first `keep`: once the stream is idle, a new allocation and a copy
+int grow_keeping(dcp_hip *x, DevBuf<float> &buf, size_t floats, size_t keep);
+// grows the device pool to `floats`, keeping what is resident (and, during a load that has written behind it, the
+// first `keep` floats)
+int ensure_pool(dcp_hip *x, size_t floats, size_t keep = 0);
+// whether the delete costs MD, DD of trans[8][Kp] are non-negative, as the kernels need them
+bool delete_costs_ok(float const *trans, int K, int Kp);
 
 } // namespace dcp_engine

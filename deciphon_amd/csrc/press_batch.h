@@ -1,4 +1,4 @@
-// press_batch.h -- what dcp_press_* (press.cpp) and dcp_hip_load_hmm (engine_profiles.cpp) share: profiles read from a
+// press_batch.h -- what dcp_press_* (press.cpp) and dcp_hip_load_hmm (engine_hmm.cpp) share: profiles read from a
 // HMMER3 file into batches of whole profiles, and a batch's nodes laid out as the emission kernel's input.
 #pragma once
 #include "hmm_model.h"

@@ -3,23 +3,19 @@
 // a load (press_kernel.hip, press_rows.hip) write between them, without the node-major tables in between and without
 // the transitions, which do not depend on the error rate.
 #pragma once
+#include "press_out.h"
+
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
 #define DCP_REEMIT_TILE 64 // positions and codes per workgroup: DCP_ROWS_TILE, and what dcp_reemit_tiles counts by
 
-// One profile.  Offsets are floats into the pool; its nodes' inputs are entries [src, src + K) of the distributions
-// (press_kernel.h: DCP_PRESS_IN_STRIDE floats each), and the null and background tables under the new error rate are
-// rows `null_row` and `bg_row` of the model tables, 1364 log-probabilities each.
+// One profile.  Its nodes' inputs are entries [out.src, out.src + K) of the distributions (press_kernel.h:
+// DCP_PRESS_IN_STRIDE floats each), and the null and background tables under the new error rate are rows `null_row` and
+// `bg_row` of the model tables, 1364 log-probabilities each.
 struct DcpReemitDesc
 {
-  int64_t src;      // entry of node 0
-  int64_t rows_off; // rows[1364][stride]
-  int64_t copy_off; // cost-order copy [1364][DCP_COST_ORDER_HDR + 64 cQ]; unused when cQ == 0
-  int32_t K, Kp;
-  int32_t stride; // DCP_ROW_HDR + Kp
-  int32_t cQ;     // as DcpRowsDesc::cQ
-  int32_t poison; // as DcpRowsDesc::poison
+  DcpRowsOut out;
   int32_t null_row, bg_row;
 };
 

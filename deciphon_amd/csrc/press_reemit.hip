@@ -30,6 +30,7 @@
 #include "dcp_types.h"
 #include "press_emission.h"
 #include "press_kernel.h"
+#include "press_out_dev.h"
 
 #include <hip/hip_runtime.h>
 
@@ -47,7 +48,7 @@ constexpr int CODE_TILES = (DCP_TABLE_SIZE + TILE - 1) / TILE; // 22: 21 whole o
 constexpr int CT = 11;                                         // code tiles per workgroup
 constexpr int64_t MAX_PAIRS = (int64_t)1 << 22;                // per launch: gridDim.x * THREADS stays below 2^32
 
-__device__ float flip(float v) { return __uint_as_float(__float_as_uint(v) ^ 0x80000000u); }
+using dcp_out::flip;
 
 __global__ __launch_bounds__(THREADS) void reemit_kernel(float const *__restrict__ dist, float const *__restrict__ models,
                                                          DcpReemitDesc const *__restrict__ desc,
@@ -59,24 +60,24 @@ __global__ __launch_bounds__(THREADS) void reemit_kernel(float const *__restrict
   __shared__ float tile[HALF][PITCH]; // [position][code]
   int64_t const pair = first + (int64_t)blockIdx.x;
   DcpReemitDesc const d = desc[pair_profile[pair]];
+  DcpRowsOut const &o = d.out;
   int const k0 = pair_k0[pair]; // (a multiple of the tile below Kp)
   int const tid = (int)threadIdx.x, tx = tid & (TILE - 1), ty = tid / TILE;
   float const inf = __uint_as_float(0x7f800000u);
   double const le = log((double)epsilon), lf = log1p(-(double)epsilon);
-  int const copy_cols = TILE * d.cQ, copy_stride = DCP_COST_ORDER_HDR + copy_cols;
 
   for (int h = 0; h < TILE / HALF; ++h)
   {
     int const kh = k0 + h * HALF;
-    int const nodes = d.K - kh < HALF ? d.K - kh : HALF; // of this half below K; may be <= 0
+    int const nodes = o.K - kh < HALF ? o.K - kh : HALF; // of this half below K; may be <= 0
     for (int i = tid; i < nodes * INPUTS; i += THREADS)
     {
       int const node = i / INPUTS, j = i % INPUTS;
-      prob[node][j] = input_prob(dist[(d.src + kh + node) * DCP_PRESS_IN_STRIDE + j]);
+      prob[node][j] = input_prob(dist[(o.src + kh + node) * DCP_PRESS_IN_STRIDE + j]);
     }
     __syncthreads();
     int const k = kh + (tx & (HALF - 1)); // the position this lane writes
-    int const col = k < copy_cols ? dcp_cost_order_col(d.cQ, 1, k) : 0;
+    int const col = dcp_out::copy_col(o, k);
     for (int ct = 0; ct < CT; ++ct)
     {
       int const c0 = ((int)blockIdx.y * CT + ct) * TILE;
@@ -88,7 +89,7 @@ __global__ __launch_bounds__(THREADS) void reemit_kernel(float const *__restrict
         float v = inf;
         if (kk < nodes && code < DCP_TABLE_SIZE)
         {
-          State const s{prob[kk], prob[kk] + 4, dist + (d.src + kh + kk) * DCP_PRESS_IN_STRIDE};
+          State const s{prob[kk], prob[kk] + 4, dist + (o.src + kh + kk) * DCP_PRESS_IN_STRIDE};
           v = flip(emission_lprob(s, le, lf, n, z));
         }
         tile[kk][tx] = v;
@@ -98,9 +99,7 @@ __global__ __launch_bounds__(THREADS) void reemit_kernel(float const *__restrict
       {
         int const c = c0 + cc;
         if (c >= DCP_TABLE_SIZE) continue;
-        float const v = tile[tx & (HALF - 1)][cc];
-        pool[d.rows_off + (int64_t)c * d.stride + DCP_ROW_HDR + k] = d.poison && k < d.K ? 0.0f : v;
-        if (k < copy_cols) pool[d.copy_off + (int64_t)c * copy_stride + DCP_COST_ORDER_HDR + col] = v;
+        dcp_out::store(pool, o, c, k, col, tile[tx & (HALF - 1)][cc]);
       }
       __syncthreads(); // the tile has been read, and after the last code tile the half's inputs
     }
@@ -109,26 +108,10 @@ __global__ __launch_bounds__(THREADS) void reemit_kernel(float const *__restrict
   if (k0 != 0) return;
   // the headers of this workgroup's codes
   float const *null = models + (int64_t)d.null_row * DCP_PRESS_TABLE, *bg = models + (int64_t)d.bg_row * DCP_PRESS_TABLE;
-  for (int ct = 0; ct < CT; ++ct)
-  {
-    int const c0 = ((int)blockIdx.y * CT + ct) * TILE;
-    {
-      int const c = c0 + tid / DCP_ROW_HDR, j = tid % DCP_ROW_HDR; // THREADS = TILE * DCP_ROW_HDR
-      if (c < DCP_TABLE_SIZE)
-        pool[d.rows_off + (int64_t)c * d.stride + j] = j == 0 ? flip(null[c]) : j == 1 ? flip(bg[c]) : 0.0f;
-    }
-    if (d.cQ)
-      for (int i = tid; i < TILE * DCP_COST_ORDER_HDR; i += THREADS)
-      {
-        int const c = c0 + i / DCP_COST_ORDER_HDR, j = i % DCP_COST_ORDER_HDR;
-        if (c < DCP_TABLE_SIZE)
-          pool[d.copy_off + (int64_t)c * copy_stride + j] =
-              j == 0 ? flip(null[c]) : j == 1 ? flip(bg[c]) : j < DCP_ROW_HDR ? 0.0f : inf;
-      }
-  }
+  for (int ct = 0; ct < CT; ++ct) dcp_out::headers(pool, o, ((int)blockIdx.y * CT + ct) * TILE, tid, null, bg);
 }
 
-static_assert(THREADS == TILE * DCP_ROW_HDR, "one thread per header float of a tile");
+static_assert(TILE == dcp_out::TILE && THREADS == dcp_out::THREADS, "the tiles press_out_dev.h writes");
 static_assert(CODE_TILES % CT == 0, "whole workgroups of code tiles");
 static_assert(DCP_PRESS_TABLE == DCP_TABLE_SIZE, "the model tables are rows of the emission kernel");
 

@@ -10,9 +10,11 @@
 // of a 32-lane half then fall on 32 different banks), so both sides are 256-byte runs per wavefront.  The grid is
 // (position tiles up to the largest Kp of the batch, code tiles and one more for the transitions, profile); a profile's
 // descriptor (press_rows.h) is uniform over the workgroup.  Tiles beyond K write the +inf padding without reading.
-// The sign flip is exact (the sign bit: -inf becomes +inf, 0 becomes -0 as on the host).
+// The sign flip is exact (the sign bit: -inf becomes +inf, 0 becomes -0 as on the host).  How a value and the headers go
+// out to the two layouts is shared with the re-emission kernel (press_out_dev.h).
 #include "press_rows.h"
 #include "dcp_types.h"
+#include "press_out_dev.h"
 
 #include <hip/hip_runtime.h>
 
@@ -24,7 +26,7 @@ constexpr int PITCH = TILE + 1;
 constexpr int THREADS = 256;
 constexpr int CODE_TILES = (DCP_TABLE_SIZE + TILE - 1) / TILE; // 22: 21 whole ones and one of 20 codes
 
-__device__ float flip(float v) { return __uint_as_float(__float_as_uint(v) ^ 0x80000000u); }
+using dcp_out::flip;
 
 __global__ __launch_bounds__(THREADS) void rows_kernel(float const *__restrict__ em, float const *__restrict__ null,
                                                        float const *__restrict__ bg, float const *__restrict__ trans,
@@ -33,8 +35,9 @@ __global__ __launch_bounds__(THREADS) void rows_kernel(float const *__restrict__
 {
   __shared__ float tile[TILE][PITCH]; // [position][code]
   DcpRowsDesc const d = desc[first + (int)blockIdx.z];
+  DcpRowsOut const &o = d.out;
   int const k0 = (int)blockIdx.x * TILE;
-  if (k0 >= d.Kp) return; // (Kp is a multiple of the tile)
+  if (k0 >= o.Kp) return; // (Kp is a multiple of the tile)
   int const tid = (int)threadIdx.x, tx = tid & (TILE - 1), ty = tid / TILE;
   float const inf = __uint_as_float(0x7f800000u);
 
@@ -43,11 +46,11 @@ __global__ __launch_bounds__(THREADS) void rows_kernel(float const *__restrict__
     // the transitions, built on the host: columns k0 .. of the eight rows, and behind the last row the padding
     for (int i = tid; i < DCP_NUM_TRANS * TILE; i += THREADS)
     {
-      int64_t const at = (int64_t)(i / TILE) * d.Kp + k0 + (i & (TILE - 1));
+      int64_t const at = (int64_t)(i / TILE) * o.Kp + k0 + (i & (TILE - 1));
       pool[d.trans_off + at] = trans[d.trans_src + at];
     }
     if (k0 == 0)
-      for (int i = DCP_NUM_TRANS * d.Kp + tid; i < d.trans_floats; i += THREADS)
+      for (int i = DCP_NUM_TRANS * o.Kp + tid; i < d.trans_floats; i += THREADS)
         pool[d.trans_off + i] = trans[d.trans_src + i];
     return;
   }
@@ -57,41 +60,24 @@ __global__ __launch_bounds__(THREADS) void rows_kernel(float const *__restrict__
   {
     int const k = k0 + kk, c = c0 + tx;
     float v = inf;
-    if (k < d.K && c < DCP_TABLE_SIZE) v = flip(em[(d.src + k) * DCP_TABLE_SIZE + c]);
+    if (k < o.K && c < DCP_TABLE_SIZE) v = flip(em[(o.src + k) * DCP_TABLE_SIZE + c]);
     tile[kk][tx] = v;
   }
   __syncthreads();
 
   int const k = k0 + tx;
-  int const copy_cols = TILE * d.cQ, copy_stride = DCP_COST_ORDER_HDR + copy_cols;
-  int const col = k < copy_cols ? dcp_cost_order_col(d.cQ, 1, k) : 0;
+  int const col = dcp_out::copy_col(o, k);
   for (int cc = ty; cc < TILE; cc += THREADS / TILE)
   {
     int const c = c0 + cc;
     if (c >= DCP_TABLE_SIZE) break;
-    float const v = tile[tx][cc];
-    pool[d.rows_off + (int64_t)c * d.stride + DCP_ROW_HDR + k] = d.poison && k < d.K ? 0.0f : v;
-    if (k < copy_cols) pool[d.copy_off + (int64_t)c * copy_stride + DCP_COST_ORDER_HDR + col] = v;
+    dcp_out::store(pool, o, c, k, col, tile[tx][cc]);
   }
 
-  if (k0 != 0) return;
-  // the headers of this tile's codes
-  {
-    int const c = c0 + tid / DCP_ROW_HDR, j = tid % DCP_ROW_HDR; // THREADS = TILE * DCP_ROW_HDR
-    if (c < DCP_TABLE_SIZE)
-      pool[d.rows_off + (int64_t)c * d.stride + j] = j == 0 ? flip(null[c]) : j == 1 ? flip(bg[c]) : 0.0f;
-  }
-  if (d.cQ)
-    for (int i = tid; i < TILE * DCP_COST_ORDER_HDR; i += THREADS)
-    {
-      int const c = c0 + i / DCP_COST_ORDER_HDR, j = i % DCP_COST_ORDER_HDR;
-      if (c < DCP_TABLE_SIZE)
-        pool[d.copy_off + (int64_t)c * copy_stride + j] =
-            j == 0 ? flip(null[c]) : j == 1 ? flip(bg[c]) : j < DCP_ROW_HDR ? 0.0f : inf;
-    }
+  if (k0 == 0) dcp_out::headers(pool, o, c0, tid, null, bg); // of this tile's codes
 }
 
-static_assert(THREADS == TILE * DCP_ROW_HDR, "one thread per header float of a tile");
+static_assert(TILE == dcp_out::TILE && THREADS == dcp_out::THREADS, "the tiles press_out_dev.h writes");
 
 } // namespace
 
