@@ -149,7 +149,7 @@ int stage(dcp_hip *x, int n, dcp_hip_window const *w, ArenaKind arena_kind, Stag
     st.cells += (double)hp.K * (double)L;
     if (arena_kind != ARENA_NONE)
     {
-      size_t const bytes = arena_kind == ARENA_TRELLIS ? trellis_bytes(L, hp.K) : table_bytes(L, hp.Kp);
+      size_t const bytes = arena_kind == ARENA_TRELLIS ? trellis_bytes(L, hp.K) : dcp_table_bytes(L, hp.Kp);
       // trellises: offsets into d_trellis; DP tables: addresses the caller placed in x->tables
       p.trellis = arena_kind == ARENA_TRELLIS ? (int64_t)arena : x->table_addr[(size_t)i];
       arena += (bytes + 15) & ~(size_t)15;

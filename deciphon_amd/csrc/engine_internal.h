@@ -7,6 +7,7 @@
 #include "dcp_errors.h"
 #include "dcp_types.h"
 #include "host_logic.h"
+#include "path_plan.h"
 #include "viterbi_kernels.h"
 
 #include <algorithm>
@@ -158,6 +159,19 @@ struct TableArena
     cur = 0;
     placed = 0;
     alloc_ms = 0;
+  }
+  // chunk after chunk (of CHUNK at the most) until the arena holds `bytes`; false: the device is full
+  bool hold(size_t bytes)
+  {
+    reset();
+    while (held < bytes)
+    {
+      size_t const step = std::min(CHUNK, bytes - held), before = held;
+      cur = chunks.size(); // past every chunk: place() makes a new one
+      if (!place(step, held + step) || held == before) return false;
+    }
+    reset();
+    return true;
   }
   // nullptr when `bytes` more would take the arena past `budget` (or the device is full)
   unsigned char *place(size_t bytes, size_t budget)
@@ -360,9 +374,8 @@ struct dcp_hip
   DevBuf<unsigned char> d_trellis; // trellises of the literal path pass
   std::vector<dcp_hip_window> path_wins; // the windows of the last dcp_hip_path
   int path_redone = 0;                   // how many of them needed the literal pass
-  int path_group = 1;                    // blocks of a window computed side by side in the fast path pass
-  std::vector<char> path_in_blocks;      // per window of path_sorted: a strip-class window whose table is held in blocks
-  int path_blocked = 0;                  // how many of those the last dcp_hip_path had (dcp_hip_path_blocked)
+  DcpPathPlan path_plan;                 // fast path pass: what every window of path_sorted places (path_plan.h)
+  int path_blocked = 0;                  // strip-class windows the last dcp_hip_path took in blocks (dcp_hip_path_blocked)
   int64_t path_table_bytes = 0;          // the most of tables.placed at one time since the last dcp_hip_path began
   PinBuf<int32_t> h_nsteps;        // path pass results on the host (pinned: see PinBuf)
   // the steps of a dcp_hip_path call stay where the copies from the device put them (PathResult::steps points there):
@@ -486,9 +499,6 @@ struct Staged : StagedPlan
 };
 
 enum ArenaKind { ARENA_NONE, ARENA_TRELLIS, ARENA_TABLE };
-
-// DP table of one window: float specials[(L+1)][8], float cells[(L+1)][3][Kp] (traceback.h)
-inline size_t table_bytes(int L, int Kp) { return ((size_t)L + 1) * (DCP_SP_STRIDE + 3 * (size_t)Kp) * 4; }
 
 // trellis of one window: uint32 xnodes[L+1], uint16 nodes[(L+1)][K] (c-core/trellis.h:12-21); in the arena of a staged
 // list (ARENA_TRELLIS) the windows follow each other in the order given, each from a multiple of 16 bytes

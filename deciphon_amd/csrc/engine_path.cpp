@@ -4,14 +4,6 @@
 namespace
 {
 
-// for functions that enqueue copies from vectors of their own: whichever way they leave, the stream has passed the
-// copies before the vectors go (a no-op when the function has synchronised already)
-struct StreamDrain
-{
-  hipStream_t s;
-  ~StreamDrain() { (void)hipStreamSynchronize(s); }
-};
-
 // The fast path pass in blocks (dcp_types.h): rows between checkpoints.  DECIPHON_HIP_CKPT_ROWS overrides (tests
 // use small blocks; 0 = whole windows, the tables of round 1); always a multiple of 5.
 int ckpt_rows()
@@ -21,55 +13,6 @@ int ckpt_rows()
   if (B < 0) B = 0;
   return B - B % 5;
 }
-// one block's table, then the window's checkpoints (16-byte aligned)
-size_t block_table_bytes(int L, int Kp, int B) { return (size_t)dcp_block_slots(L, B) * (DCP_SP_STRIDE + 3 * (size_t)Kp) * 4; }
-// (strip: a window of the strip class, whose checkpoints carry B of five rows as well)
-size_t ckpt_bytes(int L, int Kp, int W, int B, bool strip = false)
-{
-  return (size_t)(dcp_num_blocks(L, B) - 1) * (size_t)(strip ? dcp_strip_ckpt_floats(Kp, W) : dcp_ckpt_floats(Kp, W)) * 4;
-}
-// the G tables of a window whose G blocks are computed at once (dcp_cost_store_kernel); its checkpoints come behind them
-size_t group_tables_bytes(int L, int Kp, int B, int G)
-{
-  return ((size_t)std::min(G, dcp_num_blocks(L, B)) * block_table_bytes(L, Kp, B) + 15) & ~(size_t)15;
-}
-size_t fast_bytes(int L, int Kp, int W, int B, int G = 1, bool strip = false)
-{
-  return group_tables_bytes(L, Kp, B, G) + ckpt_bytes(L, Kp, W, B, strip);
-}
-
-// Does this window of the strip class go in blocks?  `whole` = what it takes otherwise: its whole table (fast pass),
-// or that and the replay scratch of all its rows (literal pass).  Where that fits the budget the window keeps it: its
-// rows are walked once instead of twice.  Where it does not the window is taken a block at a time like every other
-// class -- unless the budget is strict: DECIPHON_HIP_PATH_STRICT=1 refuses a strip window whose WHOLE table exceeds the
-// budget, as it always has (its block table might fit; the rule is kept because callers and tests rely on it).
-bool strip_in_blocks(size_t whole, int B, size_t budget) { return B > 0 && whole > budget && !path_budget_strict(); }
-
-// The G block tables, the checkpoints and (literal pass) the replay scratch of a window are ONE placement, and a
-// placement lies in one chunk of the arena.  Once the arena holds chunks -- dcp_hip_path_reserve sets the whole budget
-// aside in chunks of TableArena::CHUNK -- a placement beyond the largest of them would be allocated on top of what is
-// held, outside the budget: G is held to what a chunk takes.  per_block, fixed: bytes of one more block, of the rest.
-int group_chunk_cap(dcp_hip const *x, size_t per_block, size_t fixed)
-{
-  size_t const chunk = x->tables.largest_chunk();
-  if (chunk == 0 || per_block == 0) return INT32_MAX; // nothing held yet: the first chunk is made to measure
-  size_t const slack = 1024; // the alignments of group_tables_bytes and TableArena::place
-  return chunk > fixed + slack + per_block ? (int)std::min<size_t>((chunk - fixed - slack) / per_block, (size_t)INT32_MAX) : 1;
-}
-
-// How many blocks of a window go side by side: what 90 % of the budget holds of them at `one` bytes each beside
-// `fixed`, no more than the window with the most blocks has (`most`) or a chunk takes (`cap`, group_chunk_cap).
-// DECIPHON_HIP_PATH_GROUP overrides.
-int group_size(size_t budget, double fixed, double one, int most, int cap)
-{
-  double const room = 0.9 * (double)budget - fixed;
-  int G = one > 0 && room > one ? (int)std::min<double>(room / one, (double)most) : 1;
-  G = std::min(G, cap);
-  if (char const *e = getenv("DECIPHON_HIP_PATH_GROUP")) G = std::max(atoi(e), 1);
-  return std::max(1, std::min(G, most));
-}
-
-void note_placed(dcp_hip *x) { x->path_table_bytes = std::max(x->path_table_bytes, (int64_t)x->tables.placed); }
 
 // the path pass works on its own bank and streams (see dcp_hip::bank): swapped in for the duration of a call
 struct PathContext
@@ -192,86 +135,80 @@ size_t path_budget(dcp_hip *x)
   return std::max(std::min(want, avail > 2 * margin ? avail - margin : avail / 2), (size_t)256 << 20);
 }
 
+// The memory plan (path_plan.h) of these windows under the engine's settings: rows between checkpoints, budget and its
+// strictness, the chunks the arena holds, DECIPHON_HIP_PATH_GROUP (blocks side by side, at least 1).
+DcpPathPlan plan_path(dcp_hip *x, DcpPathKind kind, std::vector<dcp_hip_window> const &w, size_t budget)
+{
+  std::vector<DcpPathWindow> pw;
+  for (dcp_hip_window const &v : w)
+  {
+    HostProfile const &hp = x->profiles[(size_t)v.profile];
+    pw.push_back(DcpPathWindow{v.stop - v.start, hp.K, hp.Kp, hp.W, hp.cls == DCP_STRIP_CLASS});
+  }
+  char const *group = getenv("DECIPHON_HIP_PATH_GROUP");
+  return dcp_plan_path(kind, (int)pw.size(), pw.data(), ckpt_rows(), budget, path_budget_strict(), x->tables.largest_chunk(),
+                       group ? std::max(atoi(group), 1) : 0);
+}
+
+// A slice: the placements of windows [b, e) of a plan, until the arena refuses one (e == b: not even the first).  Their
+// addresses go to x->table_addr, where stage() looks for them.
+size_t place_slice(dcp_hip *x, DcpPathPlan const &plan, size_t b, size_t budget)
+{
+  x->tables.reset();
+  x->table_addr.clear();
+  size_t e = b;
+  for (; e < plan.place.size(); ++e)
+  {
+    unsigned char *at = x->tables.place(plan.place[e].bytes, budget);
+    if (!at) break;
+    x->table_addr.push_back((int64_t)(uintptr_t)at);
+  }
+  x->path_table_bytes = std::max(x->path_table_bytes, (int64_t)x->tables.placed);
+  return e;
+}
+
 // The literal pass of the profiles beyond 4096 positions (strip class): the register-resident path kernel does not
 // reach them; their trellis is replayed row by row from the DP table (row_replay.h), into d_trellis at trel_off[j] for
 // window w[sl[..]] = j, its score into slot j of d_out.  The tables are placed slice by slice within the budget like
 // the fast pass's.  A window keeps its whole table, with (L + 1) * 3 * K floats of scratch, where the two fit the
-// budget; where they do not -- and the budget is not strict, see strip_in_blocks -- the table comes a block at a time
-// from checkpoints, G blocks side by side, and a block serves the rows of the traceback's partition (dcp_types.h).
+// budget; where they do not -- and the budget is not strict -- the table comes a block at a time from checkpoints, G
+// blocks side by side, and a block serves the rows of the traceback's partition (dcp_types.h): DCP_PATH_LITERAL.
 // count_blocked: the windows taken in blocks go into x->path_blocked (a dcp_hip_path whose fast pass was skipped).
 int literal_strips(dcp_hip *x, std::vector<dcp_hip_window> const &w, std::vector<int> const &sl,
                    std::vector<size_t> const &trel_off, bool count_blocked)
 {
   int const n = (int)w.size();
   size_t const budget = path_budget(x);
-  int const B = ckpt_rows();
-  auto const scratch_bytes = [](int rows, int K) { return (size_t)rows * 3 * (size_t)K * sizeof(float); };
-  auto const aligned = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
-  std::vector<char> blocked(sl.size(), 0);
-  int G = 1;
+  std::vector<dcp_hip_window> strips;
+  for (int j : sl)
   {
-    // as many blocks side by side as the budget holds for the window that needs the most
-    double fixed = 0, one = 0;
-    int most = 1, cap = INT32_MAX;
-    for (size_t i = 0; i < sl.size(); ++i)
-    {
-      dcp_hip_window const &v = w[(size_t)sl[i]];
-      HostProfile const &hp = x->profiles[(size_t)v.profile];
-      int const L = v.stop - v.start;
-      if (L < 1) return fail(x, DCP_EZEROSEQ, "empty window");
-      blocked[i] = strip_in_blocks(aligned(table_bytes(L, hp.Kp)) + scratch_bytes(L + 1, hp.K), B, budget);
-      if (!blocked[i]) continue;
-      size_t const per_block = block_table_bytes(L, hp.Kp, B) + scratch_bytes(dcp_replay_block_rows(B), hp.K);
-      fixed = std::max(fixed, (double)ckpt_bytes(L, hp.Kp, hp.W, B, true));
-      one = std::max(one, (double)per_block);
-      most = std::max(most, dcp_num_blocks(L, B));
-      cap = std::min(cap, group_chunk_cap(x, per_block, ckpt_bytes(L, hp.Kp, hp.W, B, true)));
-      if (count_blocked) ++x->path_blocked;
-    }
-    G = group_size(budget, fixed, one, most, cap);
+    if (w[(size_t)j].stop - w[(size_t)j].start < 1) return fail(x, DCP_EZEROSEQ, "empty window");
+    strips.push_back(w[(size_t)j]);
   }
+  DcpPathPlan const plan = plan_path(x, DCP_PATH_LITERAL, strips, budget);
+  int const B = plan.B, G = plan.G;
+  if (count_blocked) x->path_blocked += plan.blocked;
   HIP_TRY(x, x->d_aux.reserve(4 * sl.size()), DCP_ENOMEM);
   for (size_t sb = 0; sb < sl.size();)
   {
-    size_t se = sb;
-    x->tables.reset();
-    x->table_addr.clear();
-    std::vector<dcp_hip_window> ws;
-    std::vector<int64_t> aux; // [4][windows of the slice]: trellis, scratch, checkpoints, score slot
-    std::vector<int64_t> scr, ckp;
-    int max_rows = 0, max_blocks = 0;
-    for (; se < sl.size(); ++se)
-    {
-      dcp_hip_window const &v = w[(size_t)sl[se]];
-      HostProfile const &hp = x->profiles[(size_t)v.profile];
-      int const L = v.stop - v.start;
-      // one placement per window: its table(s), then the checkpoints, then the scratch
-      size_t const tables = aligned(blocked[se] ? fast_bytes(L, hp.Kp, hp.W, B, G, true) : table_bytes(L, hp.Kp));
-      int const nb = blocked[se] ? dcp_num_blocks(L, B) : 1;
-      int const rows = blocked[se] ? std::min(G, nb) * dcp_replay_block_rows(B) : L + 1;
-      unsigned char *t = x->tables.place(tables + scratch_bytes(rows, hp.K), budget);
-      if (!t) break;
-      x->table_addr.push_back((int64_t)(uintptr_t)t);
-      ws.push_back(v);
-      scr.push_back((int64_t)(uintptr_t)(t + tables));
-      ckp.push_back(blocked[se] ? (int64_t)(uintptr_t)t + (int64_t)group_tables_bytes(L, hp.Kp, B, G) : 0);
-      max_rows = std::max(max_rows, rows);
-      if (blocked[se]) max_blocks = std::max(max_blocks, nb);
-    }
+    size_t const se = place_slice(x, plan, sb, budget);
     if (se == sb) return fail(x, DCP_ENOMEM, "no device memory for the DP table of a long profile's path pass");
-    note_placed(x);
-    int const ns = (int)ws.size();
+    int const ns = (int)(se - sb);
     Staged ss;
-    int rc = stage(x, ns, ws.data(), ARENA_TABLE, ss);
+    int rc = stage(x, ns, strips.data() + sb, ARENA_TABLE, ss);
     if (rc) return rc;
-    aux.resize(4 * (size_t)ns);
+    std::vector<int64_t> aux(4 * (size_t)ns); // [4][windows of the slice]: trellis, scratch, checkpoints, score slot
+    int max_rows = 0, max_blocks = 0;
     for (int i = 0; i < ns; ++i)
     {
       int const j = sl[sb + (size_t)i];
+      DcpPathPlace const &p = plan.place[sb + (size_t)i];
       aux[(size_t)i] = (int64_t)(uintptr_t)(x->d_trellis.p + trel_off[(size_t)j]);
-      aux[(size_t)ns + i] = scr[(size_t)i];
-      aux[2 * (size_t)ns + i] = ckp[(size_t)i];
+      aux[(size_t)ns + i] = x->table_addr[(size_t)i] + (int64_t)p.scratch_off;
+      aux[2 * (size_t)ns + i] = p.in_blocks ? x->table_addr[(size_t)i] + (int64_t)p.ckpt_off : 0;
       aux[3 * (size_t)ns + i] = j;
+      max_rows = std::max(max_rows, p.replay_rows);
+      if (p.in_blocks) max_blocks = std::max(max_blocks, p.blocks);
     }
     HIP_TRY(x, hipMemcpyAsync(x->d_aux.p, aux.data(), aux.size() * sizeof(int64_t), hipMemcpyHostToDevice, x->stream),
             DCP_EFUNCUSE);
@@ -388,21 +325,18 @@ int path_fast(dcp_hip *x, int b, int e, std::vector<int> &redo)
   if (rc) return rc;
   tm.lap("stage");
   HIP_TRY(x, BK(x).d_out.reserve(2 * (size_t)n), DCP_ENOMEM);
-  int const B = ckpt_rows();
-  // checkpoints sit behind each window's block table (dcp_hip_path placed fast_bytes per window)
+  int const B = x->path_plan.B, G = x->path_plan.G;
+  // checkpoints sit behind each window's block tables (DcpPathPlace::ckpt_off)
   std::vector<int64_t> ckpt_addr((size_t)n, 0), step_off;
   StreamDrain drain{x->stream}; // destroyed before the two: an early return does not pull them from under a copy
   int max_blocks = 1, strip_blocks = 0; // strip_blocks > 0: windows of the strip class that go in blocks
   for (DcpProblem const &p : st.problems)
   {
-    HostProfile const &hp = x->profiles[(size_t)p.profile];
-    // (a window of the strip class that keeps its whole table has no checkpoints: address 0, dcp_hip_path placed
-    // table_bytes for it)
-    if (hp.cls == DCP_STRIP_CLASS && !x->path_in_blocks[(size_t)(b + p.out)]) continue;
-    int const nb = dcp_num_blocks(p.L, B);
-    ckpt_addr[(size_t)p.out] = p.trellis + (int64_t)group_tables_bytes(p.L, hp.Kp, B, x->path_group);
-    int &most = hp.cls == DCP_STRIP_CLASS ? strip_blocks : max_blocks;
-    most = std::max(most, nb);
+    DcpPathPlace const &pl = x->path_plan.place[(size_t)(b + p.out)];
+    if (!pl.in_blocks) continue; // a window of the strip class that keeps its whole table has no checkpoints: address 0
+    ckpt_addr[(size_t)p.out] = p.trellis + (int64_t)pl.ckpt_off;
+    int &most = x->profiles[(size_t)p.profile].cls == DCP_STRIP_CLASS ? strip_blocks : max_blocks;
+    most = std::max(most, pl.blocks);
   }
   HIP_TRY(x, x->d_ckpt_addr.reserve((size_t)n), DCP_ENOMEM);
   HIP_TRY(x, hipMemcpyAsync(x->d_ckpt_addr.p, ckpt_addr.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, x->stream),
@@ -433,7 +367,6 @@ int path_fast(dcp_hip *x, int b, int e, std::vector<int> &redo)
       {
         // the checkpoints of those that go in blocks, then G blocks at a time; a window that keeps its whole table (no
         // checkpoint address) is one block of the first round
-        int const G = std::max(x->path_group, 1);
         if (strip_blocks > 0) HIP_TRY(x, dcp_launch_strip_ckpt(a, x->d_ckpt_addr.p, B), DCP_EFUNCUSE);
         for (int it = 0; it == 0 || it * G < strip_blocks; ++it)
         {
@@ -443,7 +376,7 @@ int path_fast(dcp_hip *x, int b, int e, std::vector<int> &redo)
                   DCP_EFUNCUSE);
         }
       }
-      else if (x->path_group <= 1 && fused) // one launch: every window walks its own blocks (dcp_path_blocks_kernel)
+      else if (G <= 1 && fused) // one launch: every window walks its own blocks (dcp_path_blocks_kernel)
         HIP_TRY(x, dcp_launch_path_blocks(c, a, x->d_ckpt_addr.p, B, x->d_steps.p, x->d_step_off.p, x->d_nsteps.p, x->d_trace.p),
                 DCP_EFUNCUSE);
       else
@@ -451,7 +384,6 @@ int path_fast(dcp_hip *x, int b, int e, std::vector<int> &redo)
         // The checkpoints; then, G blocks at a time from the last to the first, the rows of those blocks of every
         // window -- a workgroup per (window, block): G times the wavefronts, each walking 1 / blocks of the rows --
         // and the traceback through them.  (G = 1 with DECIPHON_HIP_PATH_FUSED=0: a launch per block and phase.)
-        int const G = std::max(x->path_group, 1);
         if (max_blocks > 1) HIP_TRY(x, dcp_launch_cost_ckpt(c, a, x->d_ckpt_addr.p, B), DCP_EFUNCUSE);
         for (int it = 0; it * G < max_blocks; ++it)
         {
@@ -508,7 +440,6 @@ int path_run(dcp_hip *x, int n, dcp_hip_window const *w)
   std::vector<int> redo;
   char const *mode = getenv("DECIPHON_HIP_PATH"); // "literal": skip the fast pass (tests, debugging)
   bool const literal_only = mode && strcmp(mode, "literal") == 0;
-  x->path_in_blocks.clear();
   if (literal_only)
     for (int i = 0; i < n; ++i) redo.push_back(i);
   else
@@ -529,56 +460,12 @@ int path_run(dcp_hip *x, int n, dcp_hip_window const *w)
     for (int i = 0; i < n; ++i) x->path_sorted[(size_t)i] = w[x->path_order[(size_t)i]];
     // slices bounded by the HBM their DP tables take
     size_t const budget = path_budget(x);
-    int const B = ckpt_rows();
-    dcp_hip_window const *ws = x->path_sorted.data();
-    // How many blocks of a window are computed side by side: as many as the budget holds tables for, for ALL the
-    // windows of the request at once -- with few hits every block of every window (the rows of a window are then
-    // walked once by one wavefront, for the checkpoints, and once by many); with many hits one (a slice of windows
-    // fills the GPU by itself).  DECIPHON_HIP_PATH_GROUP overrides.
-    {
-      double one = 0, fixed = 0;
-      int most = 1, cap = INT32_MAX;
-      x->path_in_blocks.assign((size_t)n, 0);
-      for (int i = 0; i < n; ++i)
-      {
-        HostProfile const &hp = x->profiles[(size_t)ws[i].profile];
-        int const L = ws[i].stop - ws[i].start;
-        bool const strip = hp.cls == DCP_STRIP_CLASS;
-        if (strip && !strip_in_blocks(table_bytes(L, hp.Kp), B, budget))
-          fixed += (double)table_bytes(L, hp.Kp);
-        else
-        {
-          x->path_in_blocks[(size_t)i] = strip;
-          x->path_blocked += strip;
-          one += (double)block_table_bytes(L, hp.Kp, B);
-          fixed += (double)ckpt_bytes(L, hp.Kp, hp.W, B, strip);
-          most = std::max(most, dcp_num_blocks(L, B));
-          cap = std::min(cap, group_chunk_cap(x, block_table_bytes(L, hp.Kp, B), ckpt_bytes(L, hp.Kp, hp.W, B, strip)));
-        }
-      }
-      x->path_group = group_size(budget, fixed, one, most, cap);
-    }
+    x->path_plan = plan_path(x, DCP_PATH_FAST, x->path_sorted, budget);
+    x->path_blocked += x->path_plan.blocked;
     for (int b = 0; b < n;)
     {
-      int e = b;
-      x->tables.reset();
-      x->table_addr.clear();
-      while (e < n)
-      {
-        // the block tables and the checkpoints (dcp_types.h); beyond 4096 positions the whole table where it fits
-        HostProfile const &hp = x->profiles[(size_t)ws[e].profile];
-        int const L = ws[e].stop - ws[e].start;
-        bool const strip = hp.cls == DCP_STRIP_CLASS;
-        unsigned char *at = x->tables.place(strip && !x->path_in_blocks[(size_t)e]
-                                                ? table_bytes(L, hp.Kp)
-                                                : fast_bytes(L, hp.Kp, hp.W, B, x->path_group, strip),
-                                            budget);
-        if (!at) break;
-        x->table_addr.push_back((int64_t)(uintptr_t)at);
-        ++e;
-      }
+      int const e = (int)place_slice(x, x->path_plan, (size_t)b, budget);
       if (e == b) return fail(x, DCP_ENOMEM, "a window's DP table does not fit the device memory left");
-      note_placed(x);
       int rc = path_fast(x, b, e, redo);
       if (rc) return rc;
       b = e;
@@ -626,17 +513,7 @@ int dcp_hip_path_reserve(struct dcp_hip *x, int64_t bytes)
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && (size_t)bytes > x->tables.held + free_b / 4)
       bytes = (int64_t)(x->tables.held + free_b / 4);
   }
-  x->tables.reset();
-  // place() allocates chunk after chunk until the arena holds `bytes`
-  while (x->tables.held < (size_t)bytes)
-  {
-    size_t const step = std::min(TableArena::CHUNK, (size_t)bytes - x->tables.held);
-    size_t const before = x->tables.held;
-    x->tables.cur = x->tables.chunks.size(); // past every chunk: force a new one
-    if (!x->tables.place(step, x->tables.held + step) || x->tables.held == before)
-      return fail(x, DCP_ENOMEM, "dcp_hip_path_reserve: hipMalloc failed");
-  }
-  x->tables.reset();
+  if (!x->tables.hold((size_t)bytes)) return fail(x, DCP_ENOMEM, "dcp_hip_path_reserve: hipMalloc failed");
   return 0;
 }
 

@@ -4,6 +4,7 @@
 #include "dcp_errors.h"
 #include "dcp_types.h"
 #include "host_logic.h"
+#include "path_plan.h"
 #include "scan_walk.h"
 
 #include <string.h>
@@ -146,6 +147,34 @@ int dcp_xcd_eighths_entry_of(int b, int n) { return b < 0 || b >= n ? -1 : dcp_x
 int dcp_xcd_placement_of(int workgroups, int windows_per_profile, int64_t table_bytes, int resident_per_xcd)
 {
   return dcp_xcd_placement(workgroups, windows_per_profile, (long long)table_bytes, resident_per_xcd);
+}
+
+int dcp_path_plan_of(int kind, int n, int32_t const *L, int32_t const *K, int32_t const *Kp, int32_t const *W,
+                     uint8_t const *strip, int B, int64_t budget, int strict, int64_t largest_chunk, int group_override,
+                     int32_t *in_blocks, int32_t *blocks, int32_t *replay_rows, int64_t *ckpt_off, int64_t *scratch_off,
+                     int64_t *bytes, int *G, int *blocked)
+{
+  if ((kind != DCP_PATH_FAST && kind != DCP_PATH_LITERAL) || n < 0 || B < 0 || budget < 0 || largest_chunk < 0 || !G || !blocked)
+    return DCP_EFUNCUSE;
+  if (n > 0 && (!L || !K || !Kp || !W || !strip || !in_blocks || !blocks || !replay_rows || !ckpt_off || !scratch_off || !bytes))
+    return DCP_EFUNCUSE;
+  std::vector<DcpPathWindow> w;
+  for (int i = 0; i < n; ++i) w.push_back(DcpPathWindow{L[i], K[i], Kp[i], W[i], strip[i] != 0});
+  DcpPathPlan const plan = dcp_plan_path((DcpPathKind)kind, n, w.data(), B, (size_t)budget, strict != 0, (size_t)largest_chunk,
+                                         group_override);
+  for (int i = 0; i < n; ++i)
+  {
+    DcpPathPlace const &p = plan.place[(size_t)i];
+    in_blocks[i] = p.in_blocks;
+    blocks[i] = p.blocks;
+    replay_rows[i] = p.replay_rows;
+    ckpt_off[i] = (int64_t)p.ckpt_off;
+    scratch_off[i] = (int64_t)p.scratch_off;
+    bytes[i] = (int64_t)p.bytes;
+  }
+  *G = plan.G;
+  *blocked = plan.blocked;
+  return 0;
 }
 
 int dcp_partition_bounds_of(int n, int32_t const *core_sizes, int nparts, int balanced, int32_t *first)

@@ -50,6 +50,8 @@ def _lib():
     L.dcp_reemit_tiles.restype = C.c_int64
     L.dcp_scan_plan_chunks.argtypes = [i32, vp, i32, vp, C.c_double, C.c_double, C.c_int64, C.c_int64, i32, vp, vp,
                                        C.POINTER(i32)]
+    L.dcp_path_plan_of.argtypes = [i32, i32, vp, vp, vp, vp, vp, i32, C.c_int64, i32, C.c_int64, i32, vp, vp, vp, vp, vp, vp,
+                                   C.POINTER(i32), C.POINTER(i32)]
     L.dcp_scan_walk_new.argtypes = [i32, vp, i32, vp]
     L.dcp_scan_walk_new.restype = vp
     L.dcp_scan_walk_del.argtypes = [vp]
@@ -394,6 +396,25 @@ def plan_chunks(core_sizes, read_lengths, first_cells: float, later_cells: float
         if rc:
             raise HipError(rc)
         return chunks[: n.value].copy(), windows[: n.value].copy()
+
+
+PATH_FAST, PATH_LITERAL = 0, 1
+
+
+def path_plan(kind: int, windows, B: int, budget: int, strict: bool = False, largest_chunk: int = 0, group_override: int = 0):
+    """The memory plan of the path pass (csrc/path_plan.h dcp_plan_path) for windows = [(L, K, Kp, W, strip), ...]:
+    a dict of G, blocked and, per window, in_blocks, blocks, replay_rows, ckpt_off, scratch_off and bytes."""
+    cols = [np.ascontiguousarray([w[c] for w in windows], t) for c, t in enumerate((np.int32,) * 4 + (np.uint8,))]
+    n = len(windows)
+    out = {k: np.zeros(n, t) for k, t in (("in_blocks", np.int32), ("blocks", np.int32), ("replay_rows", np.int32),
+                                          ("ckpt_off", np.int64), ("scratch_off", np.int64), ("bytes", np.int64))}
+    G, blocked = C.c_int(0), C.c_int(0)
+    rc = _lib().dcp_path_plan_of(int(kind), n, *(a.ctypes.data_as(C.c_void_p) for a in cols), int(B), int(budget),
+                                 int(bool(strict)), int(largest_chunk), int(group_override),
+                                 *(a.ctypes.data_as(C.c_void_p) for a in out.values()), C.byref(G), C.byref(blocked))
+    if rc:
+        raise HipError(rc)
+    return dict(out, G=G.value, blocked=blocked.value)
 
 
 WALK_HIT = np.dtype([("batch_index", "i4"), ("profile", "i4"), ("seq", "i4"), ("window", "i4"), ("start", "i4"),

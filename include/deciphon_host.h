@@ -114,6 +114,19 @@ int dcp_row_lane_offsets(int layout, int Q, int S, int K, uint32_t *offsets);
  * kernel of which one XCD holds resident_per_xcd workgroups. */
 int dcp_xcd_eighths_entry_of(int b, int n);
 int dcp_xcd_placement_of(int workgroups, int windows_per_profile, int64_t table_bytes, int resident_per_xcd);
+/* The memory plan of the path pass (csrc/path_plan.h dcp_plan_path: the rules), for n windows of L[i] rows of profiles
+ * of K[i] positions, padded to Kp[i], on W[i] wavefronts, strip[i] != 0 for the strip class (K > 4096).  kind 0: the
+ * fast pass over every window of a request; 1: the literal pass over its strip windows (strip[] is not read).  B: rows
+ * between checkpoints (a multiple of 5; 0 = none); budget: bytes the table arena may hold; strict != 0: the budget is
+ * a hard limit; largest_chunk: the largest chunk the arena holds already (0: none); group_override > 0: blocks side by
+ * side whatever the budget says.  Per window: in_blocks (0 = the whole table), its blocks, the rows of replay scratch
+ * (kind 1), the bytes from the start of its placement to its checkpoints (0: none) and to its scratch (kind 1), and the
+ * bytes of the placement.  *G: blocks of a window side by side; *blocked: strip windows in blocks.  Returns 0, or
+ * DCP_EFUNCUSE with nothing written. */
+int dcp_path_plan_of(int kind, int n, int32_t const *L, int32_t const *K, int32_t const *Kp, int32_t const *W,
+                     uint8_t const *strip, int B, int64_t budget, int strict, int64_t largest_chunk, int group_override,
+                     int32_t *in_blocks, int32_t *blocks, int32_t *replay_rows, int64_t *ckpt_off, int64_t *scratch_off,
+                     int64_t *bytes, int *G, int *blocked);
 /* How dcp_scan_run cuts profiles x reads into cost batches (csrc/host_logic.h dcp_plan_chunks: the rules).
  * dcp_scan_run plans with first_cells = DCP_SCAN_FIRST_CHUNK_CELLS, later_cells = unlimited (both
  * DECIPHON_HIP_CHUNK_CELLS when that is set), max_pairs = DCP_SCAN_CHUNK_PAIRS and max_windows =

@@ -1,5 +1,5 @@
-// host_sanitize.cpp -- TEST INFRASTRUCTURE: the host-side .dcp reader, windows, partitions and one short window walk
-// under ASan + UBSan, on the golden database, on truncated copies and on 200 randomly corrupted copies (must fail
+// host_sanitize.cpp -- TEST INFRASTRUCTURE: the host-side .dcp reader, windows, partitions, one short window walk and a
+// few memory plans of the path pass under ASan + UBSan, on the golden database, on truncated copies and on 200 randomly corrupted copies (must fail
 // cleanly, never fault).
 #include "deciphon_hip.h"
 #include "deciphon_host.h"
@@ -65,6 +65,32 @@ int main(int argc, char **argv)
     printf("walk done: %lld of %lld windows, %ld hits, %lld scored again\n", (long long)dcp_scan_walk_windows(walk),
            (long long)nw, nhits, (long long)dcp_scan_walk_take_queued(walk));
     dcp_scan_walk_del(walk);
+  }
+  {
+    /* memory plans of the path pass (csrc/path_plan.h), cases of tests/test_path_plan.py: strip windows of K = 4200 and
+     * 8192 and two short profiles, both kinds, every B, budgets around a whole table, a chunk cap, overrides; every
+     * placement holds its checkpoints and its scratch */
+    int32_t const L[5] = {120, 120, 3000, 600, 2000}, K[5] = {4200, 300, 4200, 8192, 1000}, Kp[5] = {6144, 384, 6144, 8192, 1024};
+    int32_t const W[5] = {8, 1, 8, 8, 4}, Bs[4] = {0, 5, 50, 500};
+    uint8_t const strip[5] = {1, 0, 1, 1, 0};
+    int64_t const budgets[5] = {1, 8924960, 8924959, (int64_t)64 << 20, (int64_t)200 << 20}, chunks[3] = {0, 40000000, (int64_t)2 << 30};
+    long plans = 0;
+    for (int kind = 0; kind < 2; ++kind) for (int b = 0; b < 4; ++b) for (int m = 0; m < 5; ++m) for (int c = 0; c < 3; ++c)
+      for (int strict = 0; strict < 2; ++strict) for (int over = 0; over < 8; over += 3)
+      {
+        int32_t inb[5], nb[5], rows[5];
+        int64_t ck[5], scr[5], bytes[5];
+        int G = 0, blocked = 0;
+        rc = dcp_path_plan_of(kind, 5, L, K, Kp, W, strip, Bs[b], budgets[m], strict, chunks[c], over, inb, nb, rows, ck, scr,
+                              bytes, &G, &blocked);
+        if (rc || G < 1) { printf("plan rc %d G %d\n", rc, G); return 1; }
+        for (int i = 0; i < 5; ++i)
+          if (ck[i] > bytes[i] || scr[i] + (int64_t)rows[i] * 3 * K[i] * 4 > bytes[i] || (kind == 0 && (scr[i] || rows[i])))
+          { printf("plan: window %d leaves its placement\n", i); return 1; }
+        ++plans;
+      }
+    if (dcp_path_plan_of(2, 0, NULL, NULL, NULL, NULL, NULL, 0, 0, 0, 0, 0, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL) == 0) return 1;
+    printf("plan done: %ld plans\n", plans);
   }
   /* truncated and corrupt files must fail cleanly */
   FILE *f = fopen(argv[1], "rb"); fseek(f, 0, SEEK_END); long sz = ftell(f); fseek(f, 0, SEEK_SET);

@@ -2,7 +2,7 @@
 table exceeds DECIPHON_HIP_PATH_BUDGET_MB is taken from checkpoints every DECIPHON_HIP_CKPT_ROWS rows, G blocks side by
 side, fast pass and literal pass alike; one whose table fits keeps it.  Against the CPU oracle and the reference's own
 bits (tests/golden/large_classes.npz, window_cap.npz).  The budgets are computed from the layout of
-deciphon_amd/csrc/dcp_types.h so that the blocks fit and the whole table does not; every budget is set on a fresh
+deciphon_amd/csrc/dcp_types.h (tests/path_layout.py) so that the blocks fit and the whole table does not; every budget is set on a fresh
 Engine (its table arena holds nothing yet and never shrinks)."""
 import os
 import zlib
@@ -12,52 +12,9 @@ import pytest
 
 from dcp_testlib import GOLDEN, bits, synth_profile
 from large_cases import build_case, large_cases, tiled_protein, window_cap_cases
+from path_layout import MB, budget_mb, fast_bytes, fast_bytes_of, literal_bytes, table_bytes
 
 pytestmark = pytest.mark.gpu
-
-MB = 1 << 20
-STRIP, WAVES = 2048, 8  # DCP_STRIP_POSITIONS; wavefronts of the strip kernels
-
-
-# ---- the layout (dcp_types.h, engine_internal.h) ----
-def padded(K):
-    return STRIP * ((K + STRIP - 1) // STRIP)
-
-
-def num_blocks(L, B):
-    return 1 if B <= 0 or L <= B + 5 else (L - 5 + B - 1) // B
-
-
-def block_slots(L, B):
-    return (L if B <= 0 or L <= B + 5 else B + 5) + 1
-
-
-def table_bytes(L, K):
-    return (L + 1) * (8 + 3 * padded(K)) * 4
-
-
-def block_table_bytes(L, K, B):
-    return block_slots(L, B) * (8 + 3 * padded(K)) * 4
-
-
-def ckpt_bytes(L, K, B):  # dcp_strip_ckpt_floats: ring[10][Kp], six lane rows, B of five rows padded to 8 floats
-    return (num_blocks(L, B) - 1) * (10 * padded(K) + 6 * 64 * WAVES + 8) * 4
-
-
-def fast_bytes(L, K, B, G):
-    """G block tables and the checkpoints of one window, as the engine places them (a multiple of 256 bytes)"""
-    tables = (min(G, num_blocks(L, B)) * block_table_bytes(L, K, B) + 15) & ~15
-    return (tables + ckpt_bytes(L, K, B) + 255) & ~255
-
-
-def literal_bytes(L, K, B, G):
-    """the same with the replay scratch of G blocks: 3 K floats for each of the B + 6 rows a block can serve"""
-    return fast_bytes(L, K, B, G) + ((min(G, num_blocks(L, B)) * (B + 6) * 3 * K * 4 + 255) & ~255)
-
-
-def budget_mb(nbytes):
-    return nbytes // MB + 1
-
 
 _oracle_paths = {}
 
@@ -289,3 +246,65 @@ def test_the_literal_pass_alone_counts_its_blocks(orc, monkeypatch):
         assert same_path(p, want)
         assert eng.path_redone == 1 and eng.path_blocked == 1
         assert 0 < eng.path_table_bytes <= budget * MB
+
+
+@pytest.mark.parametrize("G", [1, 2, 3])
+@pytest.mark.parametrize("mode", ["fast", "literal"])
+def test_the_bytes_placed_are_the_layouts(orc, monkeypatch, mode, G):
+    """K = 4200 x 120 rows in blocks of 50: three blocks, the smallest window that has them.  The budget holds one block
+    table and the checkpoints and not the whole table (8.9 MB), so the window goes in blocks; G of them side by side are
+    what DECIPHON_HIP_PATH_GROUP says, and beyond G = 1 they pass the budget as the lone placement of a slice does.  The
+    bytes placed are exactly the layout's: G tables and the checkpoints in the fast pass, and with the replay scratch
+    of G blocks when DECIPHON_HIP_PATH=literal skips it."""
+    import deciphon_amd
+
+    K, L, B = STRICT_CASE["K"], 120, 50
+    prof, seq, _ = build_case(STRICT_CASE, orc)
+    seq = np.ascontiguousarray(seq[:L])
+    want = oracle_path(orc, "strict-120", prof, seq)
+    budget = budget_mb(fast_bytes(L, K, B, 1))
+    assert fast_bytes(L, K, B, 1) <= budget * MB < table_bytes(L, K)
+    monkeypatch.delenv("DECIPHON_HIP_PATH_STRICT", raising=False)
+    monkeypatch.delenv("DECIPHON_HIP_PATH", raising=False)
+    if mode == "literal":
+        monkeypatch.setenv("DECIPHON_HIP_PATH", "literal")
+    monkeypatch.setenv("DECIPHON_HIP_CKPT_ROWS", str(B))
+    monkeypatch.setenv("DECIPHON_HIP_PATH_GROUP", str(G))
+    monkeypatch.setenv("DECIPHON_HIP_PATH_BUDGET_MB", str(budget))
+    with deciphon_amd.Engine(0) as eng:
+        eng.add_profile(prof.K, prof.trans, prof.match, prof.null, prof.bg)
+        eng.commit()
+        eng.set_sequences([seq])
+        eng.set_mode(True, False)
+        p = eng.path([(0, 0, 0, L)], trellis=False)[0]
+        print(f"{mode} G={G}: placed {eng.path_table_bytes}, fast {fast_bytes(L, K, B, G)}, literal {literal_bytes(L, K, B, G)}, "
+              f"blocked {eng.path_blocked}, redone {eng.path_redone}")
+        assert same_path(p, want)
+        assert eng.path_blocked == 1
+        assert eng.path_redone == (1 if mode == "literal" else 0)
+        assert eng.path_table_bytes == (literal_bytes if mode == "literal" else fast_bytes)(L, K, B, G)
+
+
+def test_the_bytes_placed_for_a_short_profile_are_the_layouts(orc, monkeypatch):
+    """K = 300 (384 padded positions on one wavefront) x 120 rows in blocks of 50, two side by side: two block tables
+    and the two checkpoints of the class's own size, rounded up to 256 bytes."""
+    import deciphon_amd
+
+    L, B, G = 120, 50, 2
+    small = synth_profile(np.random.default_rng(5), 300)
+    seq = np.ascontiguousarray(build_case(STRICT_CASE, orc)[1][100 : 100 + L])
+    want = oracle_path(orc, "small-120", small, seq)
+    for name in ("DECIPHON_HIP_PATH_STRICT", "DECIPHON_HIP_PATH", "DECIPHON_HIP_PATH_BUDGET_MB"):
+        monkeypatch.delenv(name, raising=False)
+    monkeypatch.setenv("DECIPHON_HIP_CKPT_ROWS", str(B))
+    monkeypatch.setenv("DECIPHON_HIP_PATH_GROUP", str(G))
+    with deciphon_amd.Engine(0) as eng:
+        eng.add_profile(small.K, small.trans, small.match, small.null, small.bg)
+        eng.commit()
+        eng.set_sequences([seq])
+        eng.set_mode(True, False)
+        p = eng.path([(0, 0, 0, L)], trellis=False)[0]
+        print(f"K=300: placed {eng.path_table_bytes}, layout {fast_bytes_of(L, 384, 1, B, G, False)}, redone {eng.path_redone}")
+        assert same_path(p, want)
+        assert eng.path_blocked == 0 and eng.path_redone == 0
+        assert eng.path_table_bytes == fast_bytes_of(L, 384, 1, B, G, False)
