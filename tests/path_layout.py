@@ -3,6 +3,7 @@ rules of csrc/path_plan.h in plain arithmetic -- the check of the planner (test_
 budgets of the GPU tests (test_gpu_strip_blocks.py), so nothing here calls the library.  K alone describes a profile of
 the strip class (K > 4096: padded to strips of 2048 positions, eight wavefronts); the *_of functions take the padded
 size Kp and the wavefronts W of any class."""
+from collections import namedtuple
 
 MB = 1 << 20
 STRIP, WAVES = 2048, 8  # DCP_STRIP_POSITIONS; wavefronts of the strip kernels
@@ -18,6 +19,20 @@ def num_blocks(L, B):
 
 def block_slots(L, B):
     return (L if B <= 0 or L <= B + 5 else B + 5) + 1
+
+
+Block = namedtuple("Block", "row_base last lo first ckpt slots")
+
+
+def block(L, B, j):
+    """dcp_block: block j of a window of L rows -- the row it starts from, the last row it computes, the stage at or
+    below which the traceback hands over to block j - 1 (-1: block 0), the first row the replay serves, the slot of its
+    checkpoint (-1: from row 0), the rows of its table"""
+    slots = block_slots(L, B)
+    row_base = j * B
+    last = L if L - row_base < slots else row_base + slots - 1
+    lo = row_base + 5 if j > 0 else -1
+    return Block(row_base, last, lo, lo + 1, j - 1, slots)
 
 
 def aligned(nbytes, to=256):
