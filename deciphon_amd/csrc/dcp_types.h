@@ -8,6 +8,9 @@
 #define DCP_XT_STRIDE 16     // floats per row of the special-transition table
 #define DCP_REF_LANES 8      // SIMD width of the reference build whose E tie rule is reproduced (-mavx2)
 #define DCP_MODEL_MAX 16384  // c-core/model.h:12
+#define DCP_NUM_CLASSES 12      // kernel classes by padded size (viterbi_kernels.h dcp_class_of)
+#define DCP_STRIP_CLASS 11      // K > 4096: strips of DCP_STRIP_POSITIONS, state ring in HBM (StripWave)
+#define DCP_NUM_PACK_SHAPES 11  // shapes of the packed cost kernels (viterbi_kernels.h dcp_pack_shape_of)
 
 enum { DCP_BM, DCP_MM, DCP_MI, DCP_MD, DCP_IM, DCP_II, DCP_DM, DCP_DD };
 enum { DCP_RR, DCP_SN, DCP_NN, DCP_SB, DCP_NB, DCP_EB, DCP_JB, DCP_EJ, DCP_JJ, DCP_EC, DCP_CC, DCP_ET, DCP_CT };

@@ -1,6 +1,7 @@
 // engine.cpp -- device-resident state and the C ABI of include/deciphon_hip.h: the engine itself, its sequences and
-// mode, staging and launching of window lists.  Profiles: engine_profiles.cpp, engine_hmm.cpp; cost passes: engine_cost.cpp; path pass:
-// engine_path.cpp; the state they share: engine_internal.h.
+// mode, the upload of staged window lists and their launches.  What is staged and what a cost pass launches is decided in
+// stage_plan.cpp, host only (plan_stage, cost_schedule).  Profiles: engine_profiles.cpp, engine_hmm.cpp; cost passes:
+// engine_cost.cpp; path pass: engine_path.cpp; the state they share: engine_internal.h.
 //
 // HBM layout (one engine = one GPU):
 //   pool      float[]          all profiles back to back; per profile
@@ -40,71 +41,6 @@ int ensure_xt(dcp_hip *x, int rows_needed)
   return 0;
 }
 
-// v reordered by key(v[i]) in [0, nkeys), equal keys keeping their order: count, prefix, scatter
-template <class Key> void bucket_stable(std::vector<DcpProblem> &v, int nkeys, Key key)
-{
-  std::vector<size_t> at((size_t)nkeys + 1, 0);
-  std::vector<unsigned char> k(v.size());
-  for (size_t i = 0; i < v.size(); ++i) ++at[(size_t)(k[i] = (unsigned char)key(v[i])) + 1];
-  bool one = false;
-  for (int j = 0; j < nkeys; ++j)
-  {
-    one = one || at[(size_t)j + 1] == v.size();
-    at[(size_t)j + 1] += at[(size_t)j];
-  }
-  if (one) return; // a single key: already in order
-  std::vector<DcpProblem> out(v.size());
-  for (size_t i = 0; i < v.size(); ++i) out[at[k[i]]++] = v[i];
-  v.swap(out);
-}
-
-// the n problems at p ordered by window length, longest first, equal lengths keeping their order
-void longest_first(DcpProblem *p, size_t n)
-{
-  if (n < 2) return;
-  int lens[32];
-  int nl = 0;
-  bool sorted = true;
-  for (size_t i = 0; i < n && nl <= 32; ++i)
-  {
-    sorted = sorted && (i == 0 || p[i].L <= p[i - 1].L);
-    int j = 0;
-    while (j < nl && lens[j] != p[i].L) ++j;
-    if (j == nl)
-    {
-      if (nl == 32)
-      {
-        nl = 33;
-        break;
-      }
-      lens[nl++] = p[i].L;
-    }
-  }
-  if (sorted && nl <= 32) return;
-  if (nl > 32)
-  {
-    std::stable_sort(p, p + n, [](DcpProblem const &a, DcpProblem const &b) { return a.L > b.L; });
-    return;
-  }
-  std::sort(lens, lens + nl, [](int a, int b) { return a > b; });
-  size_t at[33] = {0};
-  for (size_t i = 0; i < n; ++i)
-  {
-    int j = 0;
-    while (lens[j] != p[i].L) ++j;
-    ++at[j + 1];
-  }
-  for (int j = 0; j < nl; ++j) at[j + 1] += at[j];
-  std::vector<DcpProblem> out(n);
-  for (size_t i = 0; i < n; ++i)
-  {
-    int j = 0;
-    while (lens[j] != p[i].L) ++j;
-    out[at[j]++] = p[i];
-  }
-  std::copy(out.begin(), out.end(), p);
-}
-
 // a staged list goes up from pinned memory (see dcp_hip::Bank); dev has been reserved
 template <class T> int upload(dcp_hip *x, DevBuf<T> &dev, PinBuf<T> &pinned, std::vector<T> const &v, hipStream_t stream)
 {
@@ -117,160 +53,38 @@ template <class T> int upload(dcp_hip *x, DevBuf<T> &dev, PinBuf<T> &pinned, std
 
 } // namespace
 
+// Ask for a plan, reserve, upload.
 int stage(dcp_hip *x, int n, dcp_hip_window const *w, ArenaKind arena_kind, Staged &st, hipStream_t origin)
 {
   if (!origin) origin = x->stream;
   if (n < 0 || (n > 0 && !w)) return fail(x, DCP_EFUNCUSE, "bad window array");
   if (BK(x).n >= 0) return fail(x, DCP_EFUNCUSE, "a dcp_hip_cost_hits_begin is outstanding on these buffers: call dcp_hip_cost_hits_end first");
   if (x->committed != x->profiles.size()) return fail(x, DCP_EFUNCUSE, "profiles not committed");
-  int const nseq = (int)x->seq_off.size() - 1;
-  int max_s = 1;
-  st.problems.resize((size_t)n);
-  size_t arena = 0;
-  bool by_profile = true; // the windows come in ascending profile order (dcp_scan_run's do): no sort needed below
-  for (int i = 0; i < n; ++i)
-  {
-    by_profile = by_profile && (i == 0 || w[i].profile >= w[i - 1].profile);
-    if (w[i].profile < 0 || w[i].profile >= (int)x->profiles.size()) return fail(x, DCP_EFUNCUSE, "bad profile index");
-    if (w[i].seq < 0 || w[i].seq >= nseq) return fail(x, DCP_EFUNCUSE, "bad sequence index");
-    int64_t const len = x->seq_off[(size_t)w[i].seq + 1] - x->seq_off[(size_t)w[i].seq];
-    if (w[i].start < 0 || w[i].stop < w[i].start || w[i].stop > len) return fail(x, DCP_EFUNCUSE, "bad window range");
-    int const L = w[i].stop - w[i].start;
-    if (L < 1) return fail(x, DCP_EZEROSEQ, "empty window");
-    HostProfile const &hp = x->profiles[(size_t)w[i].profile];
-    DcpProblem &p = st.problems[(size_t)i];
-    p.profile = w[i].profile;
-    p.L = L;
-    p.code_row = x->row_off[(size_t)w[i].seq] + w[i].start;
-    p.xt_row = std::max(L / 3, 1); // c-core/thread.c:112
-    p.out = i;
-    p.trellis = 0;
-    max_s = std::max(max_s, p.xt_row);
-    st.cells += (double)hp.K * (double)L;
-    if (arena_kind != ARENA_NONE)
-    {
-      size_t const bytes = arena_kind == ARENA_TRELLIS ? trellis_bytes(L, hp.K) : dcp_table_bytes(L, hp.Kp);
-      // trellises: offsets into d_trellis; DP tables: addresses the caller placed in x->tables
-      p.trellis = arena_kind == ARENA_TRELLIS ? (int64_t)arena : x->table_addr[(size_t)i];
-      arena += (bytes + 15) & ~(size_t)15;
-    }
-  }
-  st.arena_bytes = arena;
-  // Cost pass: the windows of short profiles go several to a wavefront (viterbi_pack.h).  They leave the
-  // problem list and come back as packs: up to G windows of ONE profile each, longest first, so that the
-  // windows of a pack are of similar length (a pack runs as many rows as its longest window).
-  // DECIPHON_HIP_PACK=0 keeps every window on the one-window-per-wavefront kernels (tests compare the two).
-  st.packs.clear();
-  for (int s = 0; s <= DCP_NUM_PACK_SHAPES; ++s) st.pk_begin[s] = 0;
-  char const *pack_env = getenv("DECIPHON_HIP_PACK");
-  bool const packing = arena_kind == ARENA_NONE && !(pack_env && pack_env[0] == '0') &&
-                       (uint64_t)x->row_off.back() < ((uint64_t)1 << 32); // code rows are addressed by u32 index
-  if (packing)
-  {
-    std::vector<DcpProblem> packed, rest;
-    for (DcpProblem const &p : st.problems)
-      (x->profiles[(size_t)p.profile].pack >= 0 ? packed : rest).push_back(p);
-    if (by_profile)
-    {
-      // order (shape, profile, longest first) without a comparison sort over everything: a stable scatter by shape
-      // keeps the profiles ascending, then each profile's run is ordered by length -- a counting pass when the run
-      // holds few distinct lengths (the windows of a chain: whole windows and one tail)
-      bucket_stable(packed, DCP_NUM_PACK_SHAPES, [&](DcpProblem const &a) { return x->profiles[(size_t)a.profile].pack; });
-      for (size_t b = 0; b < packed.size();)
-      {
-        size_t e = b + 1;
-        while (e < packed.size() && packed[e].profile == packed[b].profile) ++e;
-        longest_first(packed.data() + b, e - b);
-        b = e;
-      }
-    }
-    else
-      std::stable_sort(packed.begin(), packed.end(), [&](DcpProblem const &a, DcpProblem const &b) {
-        int sa = x->profiles[(size_t)a.profile].pack, sb = x->profiles[(size_t)b.profile].pack;
-        if (sa != sb) return sa < sb;
-        if (a.profile != b.profile) return a.profile < b.profile;
-        return a.L > b.L;
-      });
-    int shape = 0;
-    for (size_t i = 0; i < packed.size();)
-    {
-      int const sh = x->profiles[(size_t)packed[i].profile].pack;
-      while (shape < sh) st.pk_begin[++shape] = (int)st.packs.size();
-      int pq = 0, ps = 0;
-      dcp_pack_shape(sh, &pq, &ps);
-      int const G = 64 / ps;
-      DcpPack pk;
-      memset(&pk, 0, sizeof pk);
-      pk.profile = packed[i].profile;
-      pk.Lmax = packed[i].L;
-      int g = 0;
-      for (; g < G && i < packed.size() && packed[i].profile == pk.profile; ++g, ++i)
-      {
-        pk.L[g] = packed[i].L;
-        pk.xt_row[g] = packed[i].xt_row;
-        pk.out[g] = packed[i].out;
-        pk.code_row[g] = (uint32_t)packed[i].code_row;
-      }
-      st.packs.push_back(pk);
-    }
-    while (shape < DCP_NUM_PACK_SHAPES) st.pk_begin[++shape] = (int)st.packs.size();
-    st.problems.swap(rest);
-    // four-lane groups: the packs of one profile go WG to a workgroup, which shares the profile's table in LDS
-    st.pack_groups.clear();
-    char const *lds_env = getenv("DECIPHON_HIP_PACK_LDS");
-    bool const lds_tables = !(lds_env && lds_env[0] == '0');
-    for (int s = 0; s < DCP_NUM_PACK_SHAPES; ++s)
-    {
-      st.pg_begin[s] = (int)st.pack_groups.size();
-      int const wg = lds_tables ? dcp_pack_lds_waves(s) : 0;
-      if (!wg) continue;
-      for (int i = st.pk_begin[s]; i < st.pk_begin[s + 1];)
-      {
-        int j = i;
-        while (j < st.pk_begin[s + 1] && j - i < wg && st.packs[(size_t)j].profile == st.packs[(size_t)i].profile) ++j;
-        st.pack_groups.push_back(make_int2(i - st.pk_begin[s], j - i));
-        i = j;
-      }
-    }
-    st.pg_begin[DCP_NUM_PACK_SHAPES] = (int)st.pack_groups.size();
-  }
-  int const nu = (int)st.problems.size(); // windows that keep a wavefront (or a workgroup) to themselves
-  // by (class, the narrow profiles of a class first -- one position per lane less: their own launch of the cost pass --,
-  // profile)
-  if (by_profile)
-    bucket_stable(st.problems, 2 * DCP_NUM_CLASSES, [&](DcpProblem const &a) {
-      HostProfile const &hp = x->profiles[(size_t)a.profile];
-      return 2 * hp.cls + (hp.narrow ? 0 : 1);
-    });
-  else
-    std::stable_sort(st.problems.begin(), st.problems.end(), [&](DcpProblem const &a, DcpProblem const &b) {
-      HostProfile const &pa = x->profiles[(size_t)a.profile], &pb = x->profiles[(size_t)b.profile];
-      if (pa.cls != pb.cls) return pa.cls < pb.cls;
-      if (pa.narrow != pb.narrow) return pa.narrow;
-      return a.profile < b.profile;
-    });
-  int i = 0;
-  for (int c = 0; c < DCP_NUM_CLASSES; ++c)
-  {
-    st.c_begin[c] = i;
-    st.c_profiles[c][0] = st.c_profiles[c][1] = 0;
-    // (the list is in profile order inside either part: a profile is one run of it)
-    auto const starts_run = [&](int j) { return j == st.c_begin[c] || st.problems[(size_t)j].profile != st.problems[(size_t)j - 1].profile; };
-    while (i < nu && x->profiles[(size_t)st.problems[(size_t)i].profile].cls == c &&
-           x->profiles[(size_t)st.problems[(size_t)i].profile].narrow)
-      st.c_profiles[c][0] += starts_run(i), ++i;
-    st.c_wide[c] = i;
-    while (i < nu && x->profiles[(size_t)st.problems[(size_t)i].profile].cls == c) st.c_profiles[c][1] += starts_run(i), ++i;
-  }
-  st.c_begin[DCP_NUM_CLASSES] = i;
-  if (i != nu) return fail(x, DCP_ELARGECORESIZE, "profile outside every kernel class");
+  // DECIPHON_HIP_PACK=0 keeps every window on the one-window-per-wavefront kernels, DECIPHON_HIP_PACK_LDS=0 every pack
+  // on the kernels that read their rows from global memory (tests compare, and flip them between calls)
+  char const *pack_env = getenv("DECIPHON_HIP_PACK"), *lds_env = getenv("DECIPHON_HIP_PACK_LDS");
+  StageInput in;
+  in.n = n;
+  in.w = w;
+  in.profiles = x->plan_profiles.data();
+  in.nprofiles = (int)x->plan_profiles.size();
+  in.nseq = (int)x->seq_off.size() - 1;
+  in.seq_off = x->seq_off.data();
+  in.row_off = x->row_off.data();
+  in.arena = arena_kind;
+  in.table_addr = x->table_addr.data(); // ARENA_TABLE: the addresses the caller placed (place_slice)
+  in.pack = !(pack_env && pack_env[0] == '0');
+  in.pack_lds = !(lds_env && lds_env[0] == '0');
+  in.shapes = pack_shapes();
+  Refusal const refused = plan_stage(in, st);
+  if (refused.code) return fail(x, refused.code, refused.what);
   if (st.c_begin[DCP_STRIP_CLASS + 1] > st.c_begin[DCP_STRIP_CLASS])
     HIP_TRY(x, BK(x).d_ring.reserve((size_t)DCP_RING_SLOTS * DCP_RING_FLOATS), DCP_ENOMEM);
-  int rc = ensure_xt(x, max_s + 1);
+  int rc = ensure_xt(x, st.max_xt_row + 1);
   if (rc) return rc;
   if (x->cur != 2) x->staged_n = -1; // a cost bank's problem list and results are about to be replaced
   // every allocation first: after the first copy is enqueued nothing below can fail but a copy itself
-  HIP_TRY(x, BK(x).d_problems.reserve((size_t)std::max(nu, 1)), DCP_ENOMEM);
+  HIP_TRY(x, BK(x).d_problems.reserve(std::max(st.problems.size(), (size_t)1)), DCP_ENOMEM);
   if (!st.packs.empty()) HIP_TRY(x, BK(x).d_packs.reserve(st.packs.size()), DCP_ENOMEM);
   if (!st.pack_groups.empty()) HIP_TRY(x, BK(x).d_pack_groups.reserve(st.pack_groups.size()), DCP_ENOMEM);
   dcp_hip::Bank &B = BK(x);
@@ -321,26 +135,20 @@ int launch_all(dcp_hip *x, StagedPlan const &st, bool path)
   return fk.join();
 }
 
-// Cost pass.  The packed kernels (short profiles, several windows per wavefront) have one stream per shape.
-// Of the rest, a small launch that mixes single-wave classes goes out as ONE fused kernel (classes 0..3
-// are contiguous in the sorted problem list); large launches keep one kernel per class, which fills the GPU
-// by itself and has its own register budget.  Everything is forked from `origin` (the stream the window lists were
-// uploaded on; x->stream by default) and joined into x->stream.
+// the device sees a pack group as an int2 (dcp_launch_cost_pack_lds), the plan as two plain int32
+static_assert(sizeof(PackGroup) == sizeof(int2) && alignof(PackGroup) <= alignof(int2), "PackGroup goes up as int2");
+
+// Cost pass: ask for the schedule (cost_schedule, stage_plan.h: which kernels, in which order, on which branches), run
+// it.  Everything is forked from `origin` (the stream the window lists were uploaded on; x->stream by default) and
+// joined into x->stream.
 // reps > 1 (measurement): every kernel `reps` times in its own stream before the join -- the passes of a kernel class
 // follow each other without waiting for the other classes, exactly as the batches of a scan do when a second batch is
 // begun while the first is in flight (dcp_hip_cost_hits_begin): no kernel's tail leaves the GPU idle but the last's.
 int launch_cost_all(dcp_hip *x, StagedPlan const &st, hipStream_t origin, int reps)
 {
   if (!origin) origin = x->stream;
-  int const single_wave = st.c_begin[4] - st.c_begin[0];
-  int mixed = 0;
-  for (int c = 0; c < 4; ++c) mixed += st.c_begin[c + 1] > st.c_begin[c];
-  bool const fused = mixed >= 2 && single_wave <= 16384;
-  int kernels = fused ? 1 : 0;
-  for (int c = fused ? 4 : 0; c < DCP_NUM_CLASSES; ++c) kernels += st.c_begin[c + 1] > st.c_begin[c];
-  for (int s = 0; s < DCP_NUM_PACK_SHAPES; ++s) kernels += st.pk_begin[s + 1] > st.pk_begin[s];
+  // DECIPHON_HIP_NARROW=0: the class's kernel for all its windows (tests compare)
   char const *narrow_env = getenv("DECIPHON_HIP_NARROW");
-  bool const narrow = !(narrow_env && narrow_env[0] == '0');
   // DECIPHON_HIP_XCD_PLACEMENT=plain | eighths: every class's cost kernel that way (measurements, tests); auto, or
   // not set: dcp_xcd_placement decides per launch
   int placement = DCP_PLACE_AUTO;
@@ -350,72 +158,42 @@ int launch_cost_all(dcp_hip *x, StagedPlan const &st, hipStream_t origin, int re
     else if (!strcmp(e, "eighths")) placement = DCP_PLACE_EIGHTHS;
     else if (strcmp(e, "auto")) return fail(x, DCP_EFUNCUSE, "DECIPHON_HIP_XCD_PLACEMENT is not plain, eighths or auto");
   }
-  for (int c = 4; narrow && c < DCP_NUM_CLASSES; ++c) kernels += st.c_wide[c] > st.c_begin[c];
+  std::vector<CostLaunch> const schedule = cost_schedule(st, !(narrow_env && narrow_env[0] == '0'));
   // x->stream joins the kernels only after the last launch (Fork::join): a wait is a barrier in x->stream's hardware
   // queue, and a stream that shares that queue would start its kernel behind every barrier issued before
   // (profiles/r02_step_timeline.txt)
-  Fork fk(x, kernels > 1 || origin != x->stream);
+  Fork fk(x, schedule.size() > 1 || origin != x->stream);
   int rc = fk.begin(origin);
   if (rc) return rc;
-  // Launch order = start order (the hardware runs a few queues side by side and takes kernels as they come):
-  // the classes with the fewest, longest-running workgroups go first -- multi-wave groups, then 8, 6, 4, 3
-  // positions per lane -- and the packed kernels with their many short wavefronts last, where they fill what
-  // the tails of the others leave idle.  (The other way round the K > 384 classes ran alone at the end of a
-  // Pfam-shaped step: 33 + 50 ms of 456, profiles/r02_b.)
-  for (int c = DCP_NUM_CLASSES - 1; c >= (fused ? 4 : 0); --c)
+  dcp_hip::Bank &B = BK(x);
+  uint32_t const ncode_rows = (uint32_t)x->row_off.back();
+  for (CostLaunch const &e : schedule)
   {
-    DcpLaunch b = launch_args(x, st, c);
-    if (b.nprob <= 0) continue;
-    if ((rc = fk.enter(x->cls_branch[c], b))) return rc;
-    b.placement = placement;
-    // the windows that fit with one position per lane less (dcp_class_narrow_limit) lead the class's list and have
-    // their own kernel, on its own stream.  DECIPHON_HIP_NARROW=0: the class's kernel for all (tests compare).
-    int const nn = narrow ? st.c_wide[c] - st.c_begin[c] : 0;
-    if (nn > 0)
-    {
-      DcpLaunch n = b;
-      n.nprob = nn;
-      n.windows_per_profile = nn / st.c_profiles[c][0];
-      if ((rc = fk.enter(x->narrow_branch[c], n))) return rc;
-      for (int r = 0; r < reps; ++r) HIP_TRY(x, dcp_launch_cost_narrow(c, n), DCP_EFUNCUSE);
-      if ((rc = fk.leave(x->narrow_branch[c]))) return rc;
-      b.problems += nn;
-      b.nprob -= nn;
-    }
-    if (b.nprob > 0)
-    {
-      // all of the class's windows in one launch (no narrow kernel, or none wanted): both parts' profiles
-      int const np = st.c_profiles[c][1] + (nn > 0 ? 0 : st.c_profiles[c][0]);
-      b.windows_per_profile = b.nprob / np;
-      for (int r = 0; r < reps; ++r) HIP_TRY(x, dcp_launch_cost(c, b), DCP_EFUNCUSE);
-    }
-    if ((rc = fk.leave(x->cls_branch[c]))) return rc;
-  }
-  if (fused)
-  {
+    Branch const &branch = (e.branch == BRANCH_NARROW ? x->narrow_branch : e.branch == BRANCH_PACK ? x->pack_branch : x->cls_branch)[e.index];
     DcpLaunch a = launch_args(x, st, 0);
-    a.nprob = single_wave;
-    if ((rc = fk.enter(x->cls_branch[0], a))) return rc;
-    for (int r = 0; r < reps; ++r) HIP_TRY(x, dcp_launch_cost_fused(a), DCP_EFUNCUSE);
-    if ((rc = fk.leave(x->cls_branch[0]))) return rc;
-  }
-  for (int s = DCP_NUM_PACK_SHAPES - 1; s >= 0; --s)
-  {
-    int const np = st.pk_begin[s + 1] - st.pk_begin[s];
-    if (np <= 0) continue;
-    DcpLaunch a = launch_args(x, st, 0);
-    if ((rc = fk.enter(x->pack_branch[s], a))) return rc;
-    int const ng = st.pg_begin[s + 1] - st.pg_begin[s];
+    if ((rc = fk.enter(branch, a))) return rc;
+    a.problems = B.d_problems.p + e.first; // (the pack kernels do not read them)
+    a.nprob = e.count;
+    a.windows_per_profile = e.windows_per_profile;
+    a.placement = placement;
     for (int r = 0; r < reps; ++r)
     {
-      if (ng > 0)
-        HIP_TRY(x, dcp_launch_cost_pack_lds(s, a, BK(x).d_packs.p + st.pk_begin[s], BK(x).d_pack_groups.p + st.pg_begin[s], ng,
-                                            (uint32_t)x->row_off.back()),
-                DCP_EFUNCUSE);
-      else
-        HIP_TRY(x, dcp_launch_cost_pack(s, a, BK(x).d_packs.p + st.pk_begin[s], np, (uint32_t)x->row_off.back()), DCP_EFUNCUSE);
+      hipError_t err = hipSuccess;
+      switch (e.kernel)
+      {
+      case COST_CLASS: err = dcp_launch_cost(e.index, a); break;
+      case COST_NARROW: err = dcp_launch_cost_narrow(e.index, a); break;
+      case COST_FUSED: err = dcp_launch_cost_fused(a); break;
+      case COST_PACK: err = dcp_launch_cost_pack(e.index, a, B.d_packs.p + e.first, e.count, ncode_rows); break;
+      case COST_PACK_LDS:
+        err = dcp_launch_cost_pack_lds(e.index, a, B.d_packs.p + st.pk_begin[e.index],
+                                       reinterpret_cast<int2 const *>(B.d_pack_groups.p + e.first), e.count, ncode_rows);
+        break;
+      default: break; // COST_NONE
+      }
+      if (err != hipSuccess) return fail(x, DCP_EFUNCUSE, "cost kernel launch", err);
     }
-    if ((rc = fk.leave(x->pack_branch[s]))) return rc;
+    if ((rc = fk.leave(branch))) return rc;
   }
   return fk.join();
 }

@@ -1,6 +1,7 @@
 // engine_internal.h -- the engine's state and what its translation units share (engine.cpp, engine_profiles.cpp,
 // engine_hmm.cpp, engine_cost.cpp, engine_path.cpp).  Everything here but struct dcp_hip has C++ linkage in namespace dcp_engine, which
-// exports.map keeps inside the library.
+// exports.map keeps inside the library.  What a staged window list holds (Staged, StagedPlan) and how it is planned:
+// stage_plan.h, host only.
 #pragma once
 #include "../../include/deciphon_hip.h"
 #include "dcp_db.h"
@@ -8,6 +9,7 @@
 #include "dcp_types.h"
 #include "host_logic.h"
 #include "path_plan.h"
+#include "stage_plan.h"
 #include "viterbi_kernels.h"
 
 #include <algorithm>
@@ -214,11 +216,9 @@ struct TableArena
   }
 };
 
-struct HostProfile
+struct HostProfile : StageProfile // K, Kp, cls, pack, narrow: what the plan of a window list reads (dcp_hip::plan_profiles)
 {
-  int K, Kp, Q, W, cls;
-  int pack = -1; // shape of the packed cost kernel (several windows per wavefront), -1: none
-  bool narrow = false; // fits its class with one position per lane less (dcp_class_narrow_limit)
+  int Q, W;
   int cQ = 0, cW = 0;  // shape of the cost kernel its cost-order copy of the rows is for (host_logic.h); 0: no copy
   int64_t pool_off; // floats
   std::string accession;
@@ -274,17 +274,6 @@ struct Branch
   hipEvent_t joined = nullptr;
 };
 
-// what the launch functions need of a staged window list: whose share of the lists on the device is whose
-struct StagedPlan
-{
-  int c_begin[DCP_NUM_CLASSES + 1] = {0}; // problems of class c are [c_begin[c], c_begin[c+1])
-  int c_wide[DCP_NUM_CLASSES] = {0};      // ... the narrow profiles' first: [c_begin[c], c_wide[c])
-  int c_profiles[DCP_NUM_CLASSES][2] = {{0}}; // profiles with a window among the narrow ones, and among the rest
-  int pk_begin[DCP_NUM_PACK_SHAPES + 1] = {0};
-  int pg_begin[DCP_NUM_PACK_SHAPES + 1] = {0};
-  double cells = 0;
-};
-
 } // namespace dcp_engine
 
 using namespace dcp_engine; // for the engine's own files only: nothing else includes this
@@ -304,6 +293,9 @@ struct dcp_hip
   // profiles
   std::vector<HostProfile> profiles;
   size_t committed = 0; // profiles whose descriptors are published
+  // ... and what the plan of a window list reads of them (stage_plan.h), 20 bytes each: a window list looks its profiles
+  // up several times per window
+  std::vector<StageProfile> plan_profiles;
   DevBuf<float> d_pool;
   size_t pool_used = 0; // floats of d_pool holding profiles
   int load_chunks = 0;  // staging chunks the last dcp_hip_load_dcp went through
@@ -338,7 +330,7 @@ struct dcp_hip
   {
     DevBuf<DcpProblem> d_problems;
     DevBuf<DcpPack> d_packs;         // cost pass: windows of short profiles, several per wavefront
-    DevBuf<int2> d_pack_groups;      // ... and, for four-lane groups, the packs of one profile that share a workgroup
+    DevBuf<PackGroup> d_pack_groups;     // ... and, for four-lane groups, the packs of one profile that share a workgroup
     DevBuf<float> d_out;             // (null, alt) per window
     DevBuf<uint32_t> d_hits;         // dcp_hip_cost_hits: count, then (window, lrt bits) pairs
     DevBuf<float> d_ring;            // strip class (K > 4096): the rings of folded rows, one per workgroup in flight
@@ -349,7 +341,7 @@ struct dcp_hip
     // (the upload of a batch begun while another was in flight took as long as the rest of that batch's cost pass)
     PinBuf<DcpProblem> h_problems;
     PinBuf<DcpPack> h_packs;
-    PinBuf<int2> h_groups;
+    PinBuf<PackGroup> h_groups;
     hipEvent_t up_ev = nullptr; // recorded behind the uploads: the pinned lists are not rewritten before
     bool up_pending = false;
   };
@@ -487,25 +479,8 @@ struct Stopwatch
   }
 };
 
-struct Staged : StagedPlan
-{
-  std::vector<DcpProblem> problems; // sorted by (class, profile); cost pass: without the packed ones
-  std::vector<DcpPack> packs;       // cost pass: sorted by (shape, profile), pk_begin[s] = the first of shape s
-  std::vector<int2> pack_groups;    // shapes with an LDS variant: {first pack, count} per workgroup, from pg_begin[s]
-  size_t arena_bytes = 0;
-  Staged() = default;
-  Staged(Staged const &) = delete;
-  Staged &operator=(Staged const &) = delete;
-};
-
-enum ArenaKind { ARENA_NONE, ARENA_TRELLIS, ARENA_TABLE };
-
-// trellis of one window: uint32 xnodes[L+1], uint16 nodes[(L+1)][K] (c-core/trellis.h:12-21); in the arena of a staged
-// list (ARENA_TRELLIS) the windows follow each other in the order given, each from a multiple of 16 bytes
-inline size_t trellis_bytes(int L, int K) { return ((size_t)L + 1) * 4 + ((size_t)L + 1) * (size_t)K * 2; }
-inline size_t trellis_stride(int L, int K) { return (trellis_bytes(L, K) + 15) & ~(size_t)15; }
-
-// validates windows and builds the device problem list in the current bank
+// Plans the window list (plan_stage, stage_plan.h: the checks, the lists, their order and shares) and brings the lists
+// to the device, into the current bank
 // (origin: the stream the lists are uploaded on -- x->stream unless a batch is begun asynchronously)
 int stage(dcp_hip *x, int n, dcp_hip_window const *w, ArenaKind arena_kind, Staged &st, hipStream_t origin = nullptr);
 DcpLaunch launch_args(dcp_hip *x, StagedPlan const &st, int c);
@@ -523,6 +498,10 @@ inline int refuse_outstanding(dcp_hip *x)
 // engine_profiles.cpp, for the loads of engine_hmm.cpp as well:
 // class, shape, padded size and cost-order shape of a profile of K positions (pool_off is left 0)
 int describe(dcp_hip *x, int K, char const *accession, HostProfile &hp);
+// the part of it that needs no engine (dcp_engine_core_size, include/deciphon_host.h): false when no class holds K
+bool describe_core_size(int K, StageProfile &p, int &Q, int &W);
+// the pack shapes as the plan of a window list reads them, [DCP_NUM_PACK_SHAPES]: the kernels' own tables, asked once
+StageShape const *pack_shapes();
 // grows a device buffer to `floats`, keeping its first `keep`: once the stream is idle, a new allocation and a copy
 int grow_keeping(dcp_hip *x, DevBuf<float> &buf, size_t floats, size_t keep);
 // grows the device pool to `floats`, keeping what is resident (and, during a load that has written behind it, the

@@ -108,7 +108,7 @@ int fetch_trellis(dcp_hip *x, int i)
   PathResult &r = x->paths[(size_t)i];
   if (r.trellis_on_host) return 0;
   std::vector<unsigned char> &buf = x->host_trellis[(size_t)i];
-  size_t const bytes = ((size_t)r.L + 1) * 4 + ((size_t)r.L + 1) * (size_t)r.K * 2;
+  size_t const bytes = trellis_bytes(r.L, r.K);
   buf.resize(bytes);
   HIP_TRY(x, hipMemcpyAsync(buf.data(), x->d_trellis.p + r.trellis_off, bytes, hipMemcpyDeviceToHost, x->stream),
           DCP_EFUNCUSE);
@@ -240,16 +240,11 @@ int path_literal(dcp_hip *x, std::vector<int> const &idx, bool count_blocked = f
   if (n == 0) return 0;
   std::vector<dcp_hip_window> w((size_t)n);
   for (int j = 0; j < n; ++j) w[(size_t)j] = x->path_wins[(size_t)idx[(size_t)j]];
-  // where stage() will put every window's trellis (ARENA_TRELLIS)
-  std::vector<size_t> trel_off((size_t)n + 1, 0);
+  // where the plan of the list below puts every window's trellis (ARENA_TRELLIS)
+  std::vector<size_t> const trel_off = trellis_offsets(n, w.data(), x->plan_profiles.data());
   std::vector<int> sl; // the windows of the strip class
   for (int j = 0; j < n; ++j)
-  {
-    HostProfile const &hp = x->profiles[(size_t)w[(size_t)j].profile];
-    int const L = w[(size_t)j].stop - w[(size_t)j].start;
-    trel_off[(size_t)j + 1] = trel_off[(size_t)j] + trellis_stride(std::max(L, 0), hp.K);
-    if (hp.cls == DCP_STRIP_CLASS) sl.push_back(j);
-  }
+    if (x->profiles[(size_t)w[(size_t)j].profile].cls == DCP_STRIP_CLASS) sl.push_back(j);
   HIP_TRY(x, BK(x).d_out.reserve(3 * (size_t)n), DCP_ENOMEM);
   HIP_TRY(x, x->d_trellis.reserve(trel_off[(size_t)n]), DCP_ENOMEM);
   int rc = 0;
@@ -257,7 +252,6 @@ int path_literal(dcp_hip *x, std::vector<int> const &idx, bool count_blocked = f
   if (!sl.empty() && (rc = literal_strips(x, w, sl, trel_off, count_blocked))) return rc;
   Staged st;
   if ((rc = stage(x, n, w.data(), ARENA_TRELLIS, st))) return rc;
-  if (st.arena_bytes != trel_off[(size_t)n]) return fail(x, DCP_EFUNCUSE, "trellis arena laid out otherwise than expected");
   if ((rc = launch_all(x, st, true))) return rc; // (not the strip class)
 
   std::vector<int64_t> step_off;
@@ -424,14 +418,13 @@ int path_run(dcp_hip *x, int n, dcp_hip_window const *w)
 {
   HIP_TRY(x, hipSetDevice(x->device), DCP_EFUNCUSE);
   PathContext ctx(x); // its own window lists, result buffers and streams: cost batches may be in flight
+  // (as stage() would: the literal pass lays its trellises out by the committed profiles before it stages)
+  if (x->committed != x->profiles.size()) return fail(x, DCP_EFUNCUSE, "profiles not committed");
   // every window is checked here, whichever pass takes it (path_literal indexes x->profiles before stage() looks)
-  int const nseq = (int)x->seq_off.size() - 1;
   for (int i = 0; i < n; ++i)
   {
-    if (w[i].profile < 0 || w[i].profile >= (int)x->profiles.size()) return fail(x, DCP_EFUNCUSE, "bad profile index");
-    if (w[i].seq < 0 || w[i].seq >= nseq) return fail(x, DCP_EFUNCUSE, "bad sequence index");
-    int64_t const len = x->seq_off[(size_t)w[i].seq + 1] - x->seq_off[(size_t)w[i].seq];
-    if (w[i].start < 0 || w[i].stop < w[i].start || w[i].stop > len) return fail(x, DCP_EFUNCUSE, "bad window range");
+    Refusal const bad = check_window(w[i], (int)x->profiles.size(), (int)x->seq_off.size() - 1, x->seq_off.data());
+    if (bad.code) return fail(x, bad.code, bad.what);
   }
   x->path_wins.assign(w, w + n);
   x->paths.resize((size_t)n);

@@ -40,27 +40,49 @@ static void stage_cost_order(HostProfile const &hp, float *staged)
 namespace dcp_engine
 {
 
+bool describe_core_size(int K, StageProfile &p, int &Q, int &W)
+{
+  int const cls = dcp_class_of(K);
+  if (cls < 0) return false;
+  p.K = K;
+  p.cls = cls;
+  dcp_class_shape(cls, &Q, &W);
+  p.Kp = 64 * Q * W;
+  if (cls == DCP_STRIP_CLASS) p.Kp *= (K + p.Kp - 1) / p.Kp; // whole strips
+  p.narrow = K <= dcp_class_narrow_limit(cls);
+  p.pack = dcp_pack_shape_of(K);
+  if (p.pack >= 0)
+  {
+    int pq = 0, ps = 0;
+    dcp_pack_shape(p.pack, &pq, &ps);
+    if (W != 1 || ps * pq > p.Kp) p.pack = -1; // the shape reads S * Q columns of a row
+  }
+  return true;
+}
+
+StageShape const *pack_shapes()
+{
+  static StageShape const *const shapes = [] {
+    static StageShape t[DCP_NUM_PACK_SHAPES];
+    for (int s = 0; s < DCP_NUM_PACK_SHAPES; ++s)
+    {
+      int pq = 0, ps = 0;
+      dcp_pack_shape(s, &pq, &ps);
+      t[s] = StageShape{64 / ps, dcp_pack_lds_waves(s)};
+    }
+    return t;
+  }();
+  return shapes;
+}
+
 int describe(dcp_hip *x, int K, char const *accession, HostProfile &hp)
 {
   if (K < 1 || K > DCP_MODEL_MAX) return fail(x, DCP_ELARGECORESIZE, "core size out of range");
-  int const cls = dcp_class_of(K);
-  if (cls < 0) return fail(x, DCP_ELARGECORESIZE, "core size beyond DCP_MAX_CORE_SIZE (16383: state ids keep 14 bits for k + 1)");
-  hp.K = K;
-  hp.cls = cls;
-  dcp_class_shape(cls, &hp.Q, &hp.W);
-  hp.Kp = 64 * hp.Q * hp.W;
-  if (cls == DCP_STRIP_CLASS) hp.Kp *= (K + hp.Kp - 1) / hp.Kp; // whole strips
+  if (!describe_core_size(K, hp, hp.Q, hp.W))
+    return fail(x, DCP_ELARGECORESIZE, "core size beyond DCP_MAX_CORE_SIZE (16383: state ids keep 14 bits for k + 1)");
   hp.pool_off = 0;
   hp.accession = accession ? accession : "";
-  hp.narrow = K <= dcp_class_narrow_limit(cls);
   cost_order_shape(hp);
-  hp.pack = dcp_pack_shape_of(K);
-  if (hp.pack >= 0)
-  {
-    int pq = 0, ps = 0;
-    dcp_pack_shape(hp.pack, &pq, &ps);
-    if (hp.W != 1 || ps * pq > hp.Kp) hp.pack = -1; // the shape reads S * Q columns of a row
-  }
   return 0;
 }
 
@@ -341,6 +363,7 @@ int dcp_hip_commit_profiles(struct dcp_hip *x)
           DCP_EFUNCUSE);
   HIP_TRY(x, hipStreamSynchronize(x->stream), DCP_EFUNCUSE);
   x->committed = x->profiles.size();
+  x->plan_profiles.assign(x->profiles.begin(), x->profiles.end());
   return 0;
 }
 
@@ -355,12 +378,31 @@ void dcp_hip_clear_profiles(struct dcp_hip *x)
   ++x->gen;
   x->pool_used = 0;
   x->profiles.clear();
+  x->plan_profiles.clear();
   x->committed = 0;
   x->dist_used = x->dist_models_used = 0;
   std::vector<float>().swap(x->lodds);
   (void)hipSetDevice(x->device);
   x->d_dist.release();
   x->d_dist_models.release();
+}
+
+// ---- include/deciphon_host.h: what the engine decides for a core size and a pack shape, without a device ----
+int dcp_engine_core_size(int K, int32_t out[4])
+{
+  StageProfile p;
+  int Q = 0, W = 0;
+  if (!out) return DCP_EFUNCUSE;
+  if (K < 1 || K > DCP_MODEL_MAX || !describe_core_size(K, p, Q, W)) return DCP_ELARGECORESIZE;
+  out[0] = p.cls, out[1] = p.narrow, out[2] = p.pack, out[3] = p.Kp;
+  return 0;
+}
+
+int dcp_engine_pack_shape(int shape, int32_t out[2])
+{
+  if (shape < 0 || shape >= DCP_NUM_PACK_SHAPES || !out) return DCP_EFUNCUSE;
+  out[0] = pack_shapes()[shape].windows, out[1] = pack_shapes()[shape].lds_waves;
+  return 0;
 }
 
 } // extern "C"

@@ -1,4 +1,4 @@
-// host_capi.cpp -- C ABI of include/deciphon_host.h over dcp_db / host_logic / scan_walk.
+// host_capi.cpp -- C ABI of include/deciphon_host.h over dcp_db / host_logic / scan_walk / path_plan / stage_plan.
 #include "../../include/deciphon_host.h"
 #include "dcp_db.h"
 #include "dcp_errors.h"
@@ -6,6 +6,7 @@
 #include "host_logic.h"
 #include "path_plan.h"
 #include "scan_walk.h"
+#include "stage_plan.h"
 
 #include <string.h>
 #include <string>
@@ -175,6 +176,91 @@ int dcp_path_plan_of(int kind, int n, int32_t const *L, int32_t const *K, int32_
   *G = plan.G;
   *blocked = plan.blocked;
   return 0;
+}
+
+int dcp_stage_plan_of(int n, struct dcp_hip_window const *windows, int nprof, int32_t const *profiles, int nseq,
+                      int64_t const *seq_off, int64_t const *row_off, int arena_kind, int64_t const *table_addr, int pack,
+                      int pack_lds, int32_t const *shapes, int64_t sizes[3], void *problems, void *packs, int32_t *groups,
+                      int32_t *c_begin, int32_t *c_wide, int32_t *c_profiles, int32_t *pk_begin, int32_t *pg_begin,
+                      double *cells, int64_t *arena_bytes, int32_t *max_xt_row, char const **what)
+{
+  using namespace dcp_engine;
+  if (what) *what = "";
+  if (n < 0 || nprof < 0 || nseq < 0 || (n && !windows) || (nprof && !profiles) || !seq_off || !row_off || !shapes || !sizes)
+    return DCP_EFUNCUSE;
+  if (arena_kind < ARENA_NONE || arena_kind > ARENA_TABLE || (arena_kind == ARENA_TABLE && n && !table_addr)) return DCP_EFUNCUSE;
+  std::vector<StageProfile> prof((size_t)nprof);
+  for (int i = 0; i < nprof; ++i)
+  {
+    int32_t const *p = profiles + 5 * (size_t)i;
+    if (p[4] < -1 || p[4] >= DCP_NUM_PACK_SHAPES) return DCP_EFUNCUSE;
+    prof[(size_t)i].K = p[0], prof[(size_t)i].Kp = p[1], prof[(size_t)i].cls = p[2], prof[(size_t)i].narrow = p[3] != 0, prof[(size_t)i].pack = p[4];
+  }
+  StageShape sh[DCP_NUM_PACK_SHAPES];
+  for (int s = 0; s < DCP_NUM_PACK_SHAPES; ++s)
+  {
+    sh[s] = StageShape{shapes[2 * s], shapes[2 * s + 1]};
+    if (sh[s].windows < 1 || sh[s].windows > 16 || sh[s].lds_waves < 0) return DCP_EFUNCUSE; // DcpPack holds 16 windows
+  }
+  StageInput const in{n,  windows, prof.data(), nprof, nseq, seq_off, row_off, (ArenaKind)arena_kind,
+                      table_addr, pack != 0, pack_lds != 0, sh};
+  Staged st;
+  Refusal const refused = plan_stage(in, st);
+  if (refused.code)
+  {
+    if (what) *what = refused.what;
+    return refused.code;
+  }
+  int64_t const counts[3] = {(int64_t)st.problems.size(), (int64_t)st.packs.size(), (int64_t)st.pack_groups.size()};
+  bool const fits = (!problems || sizes[0] >= counts[0]) && (!packs || sizes[1] >= counts[1]) && (!groups || sizes[2] >= counts[2]);
+  memcpy(sizes, counts, sizeof counts);
+  if (!fits) return DCP_ENOMEM;
+  if (problems && counts[0]) memcpy(problems, st.problems.data(), st.problems.size() * sizeof(DcpProblem));
+  if (packs && counts[1]) memcpy(packs, st.packs.data(), st.packs.size() * sizeof(DcpPack));
+  if (groups && counts[2]) memcpy(groups, st.pack_groups.data(), st.pack_groups.size() * sizeof(PackGroup));
+  if (c_begin) memcpy(c_begin, st.c_begin, sizeof st.c_begin);
+  if (c_wide) memcpy(c_wide, st.c_wide, sizeof st.c_wide);
+  if (c_profiles) memcpy(c_profiles, st.c_profiles, sizeof st.c_profiles);
+  if (pk_begin) memcpy(pk_begin, st.pk_begin, sizeof st.pk_begin);
+  if (pg_begin) memcpy(pg_begin, st.pg_begin, sizeof st.pg_begin);
+  if (cells) *cells = st.cells;
+  if (arena_bytes) *arena_bytes = (int64_t)st.arena_bytes;
+  if (max_xt_row) *max_xt_row = st.max_xt_row;
+  return 0;
+}
+
+int dcp_cost_schedule_of(int32_t const *c_begin, int32_t const *c_wide, int32_t const *c_profiles, int32_t const *pk_begin,
+                         int32_t const *pg_begin, int narrow, int cap, int32_t *rows)
+{
+  using namespace dcp_engine;
+  if (!c_begin || !c_wide || !c_profiles || !pk_begin || !pg_begin || cap < 0 || (cap && !rows)) return -1;
+  StagedPlan st;
+  memcpy(st.c_begin, c_begin, sizeof st.c_begin);
+  memcpy(st.c_wide, c_wide, sizeof st.c_wide);
+  memcpy(st.c_profiles, c_profiles, sizeof st.c_profiles);
+  memcpy(st.pk_begin, pk_begin, sizeof st.pk_begin);
+  memcpy(st.pg_begin, pg_begin, sizeof st.pg_begin);
+  std::vector<CostLaunch> const s = cost_schedule(st, narrow != 0);
+  static_assert(sizeof(CostLaunch) == 6 * sizeof(int32_t), "a launch goes out as a row of six int32");
+  if (!s.empty() && (int)s.size() <= cap) memcpy(rows, s.data(), s.size() * sizeof(CostLaunch));
+  return (int)s.size();
+}
+
+int64_t dcp_trellis_arena_of(int n, int32_t const *L, int32_t const *K, int64_t *offsets)
+{
+  using namespace dcp_engine;
+  if (n < 0 || (n && (!L || !K))) return -1;
+  std::vector<dcp_hip_window> w((size_t)n);
+  std::vector<StageProfile> prof((size_t)n);
+  for (int i = 0; i < n; ++i)
+  {
+    if (L[i] < 0 || K[i] < 1) return -1;
+    w[(size_t)i].profile = i, w[(size_t)i].seq = 0, w[(size_t)i].start = 0, w[(size_t)i].stop = L[i];
+    prof[(size_t)i].K = K[i];
+  }
+  std::vector<size_t> const off = trellis_offsets(n, w.data(), prof.data());
+  for (int i = 0; offsets && i < n; ++i) offsets[i] = (int64_t)off[(size_t)i];
+  return (int64_t)off[(size_t)n];
 }
 
 int dcp_partition_bounds_of(int n, int32_t const *core_sizes, int nparts, int balanced, int32_t *first)

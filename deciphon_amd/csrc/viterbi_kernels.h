@@ -7,8 +7,7 @@
 //   0..3: Kp = 64..256, one wavefront, 1..4 positions per lane
 //   4..10: Kp = 384, 512, 768, 1024, 1536, 2048, 4096, several wavefronts or more positions per lane
 //   11:    4096 < K <= 16383, strip by strip
-#define DCP_NUM_CLASSES 12
-#define DCP_STRIP_CLASS 11      // K > 4096: strips of DCP_STRIP_POSITIONS, state ring in HBM (StripWave)
+// (DCP_NUM_CLASSES, DCP_STRIP_CLASS and DCP_NUM_PACK_SHAPES: dcp_types.h, for the host-only units as well)
 #define DCP_STRIP_POSITIONS 2048 // 64 lanes x 4 positions x 8 wavefronts
 #define DCP_MAX_CORE_SIZE 16383 // state ids keep 14 bits for k + 1 (c-core/state.h:27-39)
 // per-problem ring scratch of the strip class: rest[5][Kp] + Ipre[5][Kp] floats at the largest Kp
@@ -20,7 +19,6 @@ void dcp_class_shape(int cls, int *Q, int *W);
 // Several windows per wavefront (viterbi_pack.h), cost pass of short profiles: shape i runs groups of S lanes
 // with Q positions per lane, (S - 1) * Q positions at most (DCP_PACK_TABLE, viterbi_kernels.hip: K <= 3 .. 124).
 // The tables keep the layout of the class the profile belongs to.
-#define DCP_NUM_PACK_SHAPES 11
 int dcp_pack_shape_of(int K); // -1: no shape holds K
 void dcp_pack_shape(int shape, int *Q, int *S);
 

@@ -52,6 +52,13 @@ def _lib():
                                        C.POINTER(i32)]
     L.dcp_path_plan_of.argtypes = [i32, i32, vp, vp, vp, vp, vp, i32, C.c_int64, i32, C.c_int64, i32, vp, vp, vp, vp, vp, vp,
                                    C.POINTER(i32), C.POINTER(i32)]
+    L.dcp_stage_plan_of.argtypes = [i32, vp, i32, vp, i32, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                    C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_char_p)]
+    L.dcp_cost_schedule_of.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp]
+    L.dcp_trellis_arena_of.argtypes = [i32, vp, vp, vp]
+    L.dcp_trellis_arena_of.restype = C.c_int64
+    L.dcp_engine_core_size.argtypes = [i32, vp]
+    L.dcp_engine_pack_shape.argtypes = [i32, vp]
     L.dcp_scan_walk_new.argtypes = [i32, vp, i32, vp]
     L.dcp_scan_walk_new.restype = vp
     L.dcp_scan_walk_del.argtypes = [vp]
@@ -415,6 +422,106 @@ def path_plan(kind: int, windows, B: int, budget: int, strict: bool = False, lar
     if rc:
         raise HipError(rc)
     return dict(out, G=G.value, blocked=blocked.value)
+
+
+ARENA_NONE, ARENA_TRELLIS, ARENA_TABLE = 0, 1, 2
+NUM_CLASSES, NUM_PACK_SHAPES = 12, 11
+PROBLEM = np.dtype([("profile", "i4"), ("L", "i4"), ("code_row", "i8"), ("xt_row", "i4"), ("out", "i4"),
+                    ("trellis", "i8")])  # struct DcpProblem
+PACK = np.dtype([("profile", "i4"), ("Lmax", "i4"), ("L", "i4", 16), ("xt_row", "i4", 16), ("out", "i4", 16),
+                 ("code_row", "u4", 16)])  # struct DcpPack
+_RANGES = (("c_begin", NUM_CLASSES + 1), ("c_wide", NUM_CLASSES), ("c_profiles", (NUM_CLASSES, 2)),
+           ("pk_begin", NUM_PACK_SHAPES + 1), ("pg_begin", NUM_PACK_SHAPES + 1))
+COST_KERNELS = ("none", "class", "narrow", "fused", "pack", "pack_lds")
+COST_BRANCHES = ("class", "narrow", "pack")
+
+
+def engine_core_size(K: int):
+    """What the engine decides for a profile of K positions, without a device: (K, Kp, class, narrow, pack shape or -1),
+    a row of stage_plan's `profiles`."""
+    out = np.zeros(4, np.int32)
+    rc = _lib().dcp_engine_core_size(int(K), out.ctypes.data_as(C.c_void_p))
+    if rc:
+        raise HipError(rc)
+    return int(K), int(out[3]), int(out[0]), int(out[1]), int(out[2])
+
+
+def engine_pack_shapes():
+    """int32[11][2]: per pack shape the windows of a pack and the wavefronts of an LDS workgroup (0: none), the engine's"""
+    out = np.zeros((NUM_PACK_SHAPES, 2), np.int32)
+    for s in range(NUM_PACK_SHAPES):
+        rc = _lib().dcp_engine_pack_shape(s, out[s].ctypes.data_as(C.c_void_p))
+        if rc:
+            raise HipError(rc)
+    return out
+
+
+def stage_plan(windows, profiles, seq_off, row_off=None, arena=ARENA_NONE, table_addr=None, pack=True, pack_lds=True,
+               shapes=None):
+    """The plan of a window list (csrc/stage_plan.h plan_stage) without an engine: windows int32[n][4] = (profile, read,
+    start, stop), profiles rows of (K, Kp, class, narrow, pack shape), seq_off / row_off[nseq + 1] (row_off: as the
+    engine lays the code rows out, by default), shapes as engine_pack_shapes() (the default).  A dict of problems
+    (PROBLEM), packs (PACK), groups int32[..][2], the five range arrays, cells, arena_bytes and max_xt_row.  A refusal
+    raises HipError with the engine's message."""
+    L = _lib()
+    vp = C.c_void_p
+    w = np.ascontiguousarray(windows, np.int32).reshape(-1, 4)
+    prof = np.ascontiguousarray(profiles, np.int32).reshape(-1, 5)
+    so = np.ascontiguousarray(seq_off, np.int64)
+    ro = np.ascontiguousarray(so + np.arange(len(so)) if row_off is None else row_off, np.int64)
+    ta = None if table_addr is None else np.ascontiguousarray(table_addr, np.int64)
+    sh = np.ascontiguousarray(engine_pack_shapes() if shapes is None else shapes, np.int32)
+    assert len(ro) == len(so) >= 1 and sh.shape == (NUM_PACK_SHAPES, 2) and (ta is None or len(ta) == len(w))
+    ranges = {k: np.zeros(shape, np.int32) for k, shape in _RANGES}
+    cells, arena_bytes, max_xt, what = C.c_double(0), C.c_int64(0), C.c_int32(0), C.c_char_p()
+
+    def call(sizes, problems, packs, groups):
+        return L.dcp_stage_plan_of(
+            len(w), w.ctypes.data_as(vp), len(prof), prof.ctypes.data_as(vp), len(so) - 1, so.ctypes.data_as(vp),
+            ro.ctypes.data_as(vp), int(arena), None if ta is None else ta.ctypes.data_as(vp), int(bool(pack)),
+            int(bool(pack_lds)), sh.ctypes.data_as(vp), sizes.ctypes.data_as(vp),
+            *(None if a is None else a.ctypes.data_as(vp) for a in (problems, packs, groups)),
+            *(a.ctypes.data_as(vp) for a in ranges.values()), C.byref(cells), C.byref(arena_bytes), C.byref(max_xt),
+            C.byref(what))
+
+    sizes = np.zeros(3, np.int64)
+    rc = call(sizes, None, None, None)
+    if rc:
+        raise HipError(rc, (what.value or b"").decode())
+    problems, packs, groups = np.zeros(sizes[0], PROBLEM), np.zeros(sizes[1], PACK), np.zeros((sizes[2], 2), np.int32)
+    rc = call(sizes, problems, packs, groups)
+    if rc:
+        raise HipError(rc, (what.value or b"").decode())
+    return dict(ranges, problems=problems, packs=packs, groups=groups, cells=cells.value, arena_bytes=arena_bytes.value,
+                max_xt_row=max_xt.value)
+
+
+def cost_schedule(plan, narrow: bool = True):
+    """The launches of a cost pass over a staged list (csrc/stage_plan.h cost_schedule): plan holds the five range
+    arrays (as stage_plan returns them); a list of dicts kernel, index, first, count, windows_per_profile, branch."""
+    L = _lib()
+    r = [np.ascontiguousarray(plan[k], np.int32) for k, _ in _RANGES]
+    for a, (k, shape) in zip(r, _RANGES):
+        assert a.shape == (shape if isinstance(shape, tuple) else (shape,)), k
+    rows = np.zeros((2 * NUM_CLASSES + NUM_PACK_SHAPES + 1, 6), np.int32)
+    n = L.dcp_cost_schedule_of(*(a.ctypes.data_as(C.c_void_p) for a in r), int(bool(narrow)), len(rows),
+                               rows.ctypes.data_as(C.c_void_p))
+    if n < 0 or n > len(rows):
+        raise HipError(8)
+    return [dict(kernel=COST_KERNELS[k], index=int(i), first=int(f), count=int(c), windows_per_profile=int(wpp),
+                 branch=COST_BRANCHES[b]) for k, i, f, c, wpp, b in rows[:n]]
+
+
+def trellis_arena(L, K):
+    """(offsets int64[n], bytes): where the literal path pass puts the trellises of windows of L[i] rows and K[i]
+    positions (csrc/stage_plan.h trellis_offsets)"""
+    Ls, Ks = np.ascontiguousarray(L, np.int32), np.ascontiguousarray(K, np.int32)
+    off = np.zeros(len(Ls), np.int64)
+    total = _lib().dcp_trellis_arena_of(len(Ls), Ls.ctypes.data_as(C.c_void_p), Ks.ctypes.data_as(C.c_void_p),
+                                        off.ctypes.data_as(C.c_void_p))
+    if total < 0:
+        raise HipError(8)
+    return off, int(total)
 
 
 WALK_HIT = np.dtype([("batch_index", "i4"), ("profile", "i4"), ("seq", "i4"), ("window", "i4"), ("start", "i4"),

@@ -127,6 +127,38 @@ int dcp_path_plan_of(int kind, int n, int32_t const *L, int32_t const *K, int32_
                      uint8_t const *strip, int B, int64_t budget, int strict, int64_t largest_chunk, int group_override,
                      int32_t *in_blocks, int32_t *blocks, int32_t *replay_rows, int64_t *ckpt_off, int64_t *scratch_off,
                      int64_t *bytes, int *G, int *blocked);
+/* The plan of a window list (csrc/stage_plan.h plan_stage: the rules) -- what the engine stages for a cost or a path
+ * pass, without an engine.  windows[n]; profiles[nprof][5] = {K, Kp, class, narrow, pack shape or -1} per profile;
+ * seq_off, row_off[nseq + 1]: the nucleotides and the code rows in front of each read, and in all; arena_kind 0 = none,
+ * 1 = trellises, 2 = DP tables at table_addr[n]; pack, pack_lds: what DECIPHON_HIP_PACK and _PACK_LDS say;
+ * shapes[DCP_NUM_PACK_SHAPES = 11][2] = {windows of a pack, wavefronts of an LDS workgroup or 0}.
+ * sizes[3]: on entry the elements that problems, packs and groups hold (not read for a NULL one), on return the
+ * elements of the plan.  problems: struct DcpProblem (csrc/dcp_types.h, 32 bytes), packs: struct DcpPack (264 bytes),
+ * groups: {first pack, count} pairs; c_begin[13], c_wide[12], c_profiles[12][2], pk_begin[12], pg_begin[12]: whose
+ * share of those lists is whose (csrc/stage_plan.h StagedPlan); *cells = sum of K L, *arena_bytes, *max_xt_row.  Any
+ * output may be NULL.  Returns 0; the engine's refusal (DCP_EFUNCUSE, DCP_EZEROSEQ, DCP_ELARGECORESIZE) with its
+ * message in *what and nothing else written; DCP_EFUNCUSE with *what = "" for arguments no engine would pass (a pack
+ * shape outside -1..10, a shape of more than 16 windows, ...); DCP_ENOMEM, with sizes set, when an array is too small. */
+struct dcp_hip_window;
+int dcp_stage_plan_of(int n, struct dcp_hip_window const *windows, int nprof, int32_t const *profiles, int nseq,
+                      int64_t const *seq_off, int64_t const *row_off, int arena_kind, int64_t const *table_addr, int pack,
+                      int pack_lds, int32_t const *shapes, int64_t sizes[3], void *problems, void *packs, int32_t *groups,
+                      int32_t *c_begin, int32_t *c_wide, int32_t *c_profiles, int32_t *pk_begin, int32_t *pg_begin,
+                      double *cells, int64_t *arena_bytes, int32_t *max_xt_row, char const **what);
+/* The launches of a cost pass over a list with those shares (csrc/stage_plan.h cost_schedule), narrow: what
+ * DECIPHON_HIP_NARROW says.  Returns their number; when it is at most cap, rows[..][6] = {kernel (0 none, 1 class,
+ * 2 narrow, 3 fused, 4 packs, 5 packs with LDS tables), class or shape, first element, count, windows per profile,
+ * branch (0 class, 1 narrow, 2 pack)} in launch order.  The pass forks when there is more than one.  -1: a NULL array. */
+int dcp_cost_schedule_of(int32_t const *c_begin, int32_t const *c_wide, int32_t const *c_profiles, int32_t const *pk_begin,
+                         int32_t const *pg_begin, int narrow, int cap, int32_t *rows);
+/* Where the literal path pass puts the trellises of n windows of L[i] rows and K[i] positions (csrc/stage_plan.h
+ * trellis_offsets): offsets[n] (may be NULL); returns the bytes of the arena, -1 for L < 0 or K < 1. */
+int64_t dcp_trellis_arena_of(int n, int32_t const *L, int32_t const *K, int64_t *offsets);
+/* What the engine decides for a profile of K positions, without a device: out[4] = {class, narrow, pack shape or -1,
+ * Kp}; DCP_ELARGECORESIZE for a core size no class holds.  And for pack shape 0..10: out[2] = {windows of a pack,
+ * wavefronts of an LDS workgroup or 0}; DCP_EFUNCUSE otherwise.  (The kernels' own tables, csrc/viterbi_kernels.h.) */
+int dcp_engine_core_size(int K, int32_t out[4]);
+int dcp_engine_pack_shape(int shape, int32_t out[2]);
 /* How dcp_scan_run cuts profiles x reads into cost batches (csrc/host_logic.h dcp_plan_chunks: the rules).
  * dcp_scan_run plans with first_cells = DCP_SCAN_FIRST_CHUNK_CELLS, later_cells = unlimited (both
  * DECIPHON_HIP_CHUNK_CELLS when that is set), max_pairs = DCP_SCAN_CHUNK_PAIRS and max_windows =

@@ -1,5 +1,5 @@
-// host_sanitize.cpp -- TEST INFRASTRUCTURE: the host-side .dcp reader, windows, partitions, one short window walk and a
-// few memory plans of the path pass under ASan + UBSan, on the golden database, on truncated copies and on 200 randomly corrupted copies (must fail
+// host_sanitize.cpp -- TEST INFRASTRUCTURE: the host-side .dcp reader, windows, partitions, one short window walk, a
+// few memory plans of the path pass and a few hundred plans of window lists under ASan + UBSan, on the golden database, on truncated copies and on 200 randomly corrupted copies (must fail
 // cleanly, never fault).
 #include "deciphon_hip.h"
 #include "deciphon_host.h"
@@ -91,6 +91,70 @@ int main(int argc, char **argv)
       }
     if (dcp_path_plan_of(2, 0, NULL, NULL, NULL, NULL, NULL, 0, 0, 0, 0, 0, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL) == 0) return 1;
     printf("plan done: %ld plans\n", plans);
+  }
+  {
+    /* plans of small random window lists (csrc/stage_plan.h) and the launches of their cost passes, on tables of this
+     * program's own: 7 profiles (the last outside every class), 5 reads, lists ascending by profile and not, every
+     * arena kind and switch, windows that are refused; the lists of a plan stay inside what it says they hold */
+    int32_t const prof[7][5] = {{3, 64, 0, 0, 0}, {14, 64, 0, 0, 3}, {100, 128, 1, 0, 10}, {300, 384, 4, 1, -1},
+                                {350, 384, 4, 0, -1}, {5000, 6144, 11, 0, -1}, {20000, 20480, -1, 0, -1}};
+    int32_t shapes[11][2];
+    for (int s = 0; s < 11; ++s) { shapes[s][0] = s < 3 ? 16 : s < 5 ? 8 : s < 8 ? 4 : 2; shapes[s][1] = s < 8 ? 1 + s % 4 : 0; }
+    int64_t const seq_off[6] = {0, 40, 41, 141, 142, 400}, row_off[6] = {0, 41, 43, 144, 146, 405};
+    long plans = 0, refusals = 0;
+    srand(7);
+    for (int it = 0; it < 400; ++it)
+    {
+      int const nw = rand() % 60, arena = it % 3 == 0 ? rand() % 3 : 0;
+      std::vector<dcp_hip_window> wins((size_t)nw);
+      std::vector<int64_t> addr((size_t)nw);
+      for (int i = 0; i < nw; ++i)
+      {
+        int const bad = rand() % 300; /* now and then a window that is refused, or the profile that is */
+        dcp_hip_window &v = wins[(size_t)i];
+        v.profile = it % 2 ? rand() % 6 : i * 6 / nw;
+        v.seq = rand() % 5;
+        int const len = (int)(seq_off[v.seq + 1] - seq_off[v.seq]);
+        v.start = len ? rand() % len : 0;
+        v.stop = v.start + (len - v.start ? 1 + rand() % (len - v.start) : 0);
+        if (bad == 0) v.profile = rand() % 2 ? -1 : 7;
+        if (bad == 1) v.seq = rand() % 2 ? -1 : 5;
+        if (bad == 2) v.stop = len + 1;
+        if (bad == 3) v.stop = v.start;
+        if (bad == 4) v.profile = 6;
+        addr[(size_t)i] = 4096 + 512 * (int64_t)i;
+      }
+      int64_t sizes[3] = {0, 0, 0};
+      int32_t cb[13], cw[12], cp[24], pk[12], pg[12], xt = 0;
+      double cells = 0;
+      int64_t arena_bytes = 0;
+      char const *what = NULL;
+      rc = dcp_stage_plan_of(nw, wins.data(), 7, &prof[0][0], 5, seq_off, row_off, arena, addr.data(), it % 5 != 0, it % 7 != 0,
+                             &shapes[0][0], sizes, NULL, NULL, NULL, cb, cw, cp, pk, pg, &cells, &arena_bytes, &xt, &what);
+      if (rc) { if (!what || !what[0]) { printf("stage: refusal %d without a message\n", rc); return 1; } ++refusals; ++plans; continue; }
+      std::vector<int64_t> problems((size_t)sizes[0] * 4), packs((size_t)sizes[1] * 33);
+      std::vector<int32_t> groups((size_t)sizes[2] * 2);
+      rc = dcp_stage_plan_of(nw, wins.data(), 7, &prof[0][0], 5, seq_off, row_off, arena, addr.data(), it % 5 != 0, it % 7 != 0,
+                             &shapes[0][0], sizes, problems.data(), packs.data(), groups.data(), cb, cw, cp, pk, pg, NULL, NULL,
+                             NULL, NULL);
+      if (rc || cb[12] != sizes[0] || pk[11] != sizes[1] || pg[11] != sizes[2]) { printf("stage: rc %d, shares and sizes differ\n", rc); return 1; }
+      for (int s = 0; s < 11; ++s)
+        for (int g = pg[s]; g < pg[s + 1]; ++g)
+          if (groups[2 * (size_t)g] < 0 || groups[2 * (size_t)g] + groups[2 * (size_t)g + 1] > pk[s + 1] - pk[s])
+          { printf("stage: a group leaves its shape's packs\n"); return 1; }
+      int32_t rows[36][6];
+      for (int narrow = 0; narrow < 2; ++narrow)
+      {
+        int const nl = dcp_cost_schedule_of(cb, cw, cp, pk, pg, narrow, 36, &rows[0][0]);
+        if (nl < 0 || nl > 36) { printf("schedule: %d launches\n", nl); return 1; }
+        int64_t covered = 0;
+        for (int i = 0; i < nl; ++i) covered += rows[i][0] >= 1 && rows[i][0] <= 3 ? rows[i][3] : 0;
+        if (covered != sizes[0]) { printf("schedule: %lld of %lld problems launched\n", (long long)covered, (long long)sizes[0]); return 1; }
+      }
+      ++plans;
+    }
+    if (!refusals || refusals == plans) { printf("stage: %ld refusals of %ld\n", refusals, plans); return 1; }
+    printf("stage done: %ld plans\n", plans);
   }
   /* truncated and corrupt files must fail cleanly */
   FILE *f = fopen(argv[1], "rb"); fseek(f, 0, SEEK_END); long sz = ftell(f); fseek(f, 0, SEEK_SET);

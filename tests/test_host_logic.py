@@ -184,7 +184,7 @@ def test_no_cpu_fallback():
 
 def test_host_reader_under_sanitizers(tmp_path):
     """The C++ host side that never touches the GPU (.dcp reader, windows, partitions, the scan's window walk, the path
-    pass's memory plan) built
+    pass's memory plan, the plan of a window list) built
     with -fsanitize=address,undefined and run over the golden database, truncated copies and
     200 randomly corrupted copies: every one must parse or fail with an error code."""
     import subprocess
@@ -195,7 +195,8 @@ def test_host_reader_under_sanitizers(tmp_path):
                     "-fno-omit-frame-pointer", "-I", csrc, "-I", os.path.join(ROOT, "include"),
                     os.path.join(ROOT, "tests", "c", "host_sanitize.cpp"), os.path.join(csrc, "host_logic.cpp"),
                     os.path.join(csrc, "dcp_db.cpp"), os.path.join(csrc, "host_capi.cpp"),
-                    os.path.join(csrc, "scan_walk.cpp"), os.path.join(csrc, "path_plan.cpp"), "-o", exe], check=True)
+                    os.path.join(csrc, "scan_walk.cpp"), os.path.join(csrc, "path_plan.cpp"),
+                    os.path.join(csrc, "stage_plan.cpp"), "-o", exe], check=True)
     r = subprocess.run([exe, os.path.join(GOLDEN, "minifam.dcp"), str(tmp_path / "cut.dcp")], capture_output=True,
                        text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
@@ -203,6 +204,7 @@ def test_host_reader_under_sanitizers(tmp_path):
     assert "window 1 [7959,10000)" in r.stdout  # c-core/window.c on a 10 kb read, K = 173
     assert "walk done" in r.stdout  # one short window walk (csrc/scan_walk.h)
     assert "plan done: 720 plans" in r.stdout  # memory plans of the path pass (csrc/path_plan.h)
+    assert "stage done: 400 plans" in r.stdout  # plans of window lists and their cost launches (csrc/stage_plan.h)
 
 
 def test_both_dcp_encodings_read_identically(tmp_path):
