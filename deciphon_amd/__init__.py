@@ -6,6 +6,7 @@ behind it: importing works anywhere, computing needs the built library and a GPU
 """
 from .press import DeciphonError, Press
 from .hip import Engine, HipError, Window, device_count, encode, error_string, library_path, load_library, xtrans
+from .scan import hit_on_read
 
 __all__ = ["DeciphonError", "Engine", "HipError", "Window", "device_count", "encode", "error_string", "library_path",
-           "load_library", "Press", "xtrans"]
+           "load_library", "Press", "xtrans", "hit_on_read"]

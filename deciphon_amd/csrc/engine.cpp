@@ -17,6 +17,7 @@
 //   out       float[]          (null, alt) per window
 //   arena     bytes            trellises of the path pass
 #include "engine_internal.h"
+#include <limits.h>
 
 namespace dcp_engine
 {
@@ -309,46 +310,78 @@ int dcp_hip_encode(char const *data, int64_t n, uint8_t *out)
   return dcp_encode_sequence(data, n, out);
 }
 
-int dcp_hip_set_sequences(struct dcp_hip *x, int nseq, uint8_t const *nt, int64_t const *offsets)
+// Plus strand: internal sequence i is read i.  Both: sequences 2s and 2s + 1 are read s and its reverse complement, which
+// exists only as code rows (dcp_encode_strands_kernel); seq_off and row_off count 2 nseq sequences, the device's copy of
+// the offsets stays the reads' (what the kernel walks nt by).
+int dcp_hip_set_sequences_strands(struct dcp_hip *x, int nseq, uint8_t const *nt, int64_t const *offsets, int strands)
 {
   if (!x || nseq < 0 || !offsets || (nseq > 0 && !nt)) return DCP_EFUNCUSE;
+  if (strands != DCP_STRANDS_PLUS && strands != DCP_STRANDS_BOTH) return fail(x, DCP_EFUNCUSE, "strands must be DCP_STRANDS_PLUS or DCP_STRANDS_BOTH");
+  bool const both = strands == DCP_STRANDS_BOTH;
+  if (both && nseq > INT_MAX / 2) return fail(x, DCP_EFUNCUSE, "more than INT_MAX / 2 reads on both strands");
   if (outstanding_batches(x)) return refuse_outstanding(x);
   HIP_TRY(x, hipSetDevice(x->device), DCP_EFUNCUSE);
   // everything is checked before anything is replaced: a refused call leaves the previous reads in force
-  std::vector<int64_t> row_off((size_t)nseq + 1);
-  int64_t max_len = 0, rows = 0;
+  int const per = both ? 2 : 1, nint = nseq * per; // internal sequences
+  std::vector<int64_t> seq_off((size_t)nint + 1), row_off((size_t)nint + 1);
+  int64_t max_len = 0, rows = 0, nts = 0;
   if (offsets[0] != 0) return fail(x, DCP_EFUNCUSE, "offsets[0] must be 0");
   for (int i = 0; i < nseq; ++i)
   {
     int64_t len = offsets[i + 1] - offsets[i];
     if (len < 0) return fail(x, DCP_EFUNCUSE, "offsets must not decrease");
     max_len = std::max(max_len, len);
-    row_off[(size_t)i] = rows;
-    rows += len + 1;
+    for (int k = 0; k < per; ++k)
+    {
+      seq_off[(size_t)i * per + k] = nts;
+      row_off[(size_t)i * per + k] = rows;
+      nts += len;
+      rows += len + 1;
+    }
   }
-  row_off[(size_t)nseq] = rows;
+  seq_off[(size_t)nint] = nts;
+  row_off[(size_t)nint] = rows;
   int64_t const total = offsets[nseq];
   for (int64_t i = 0; i < total; ++i)
     if (nt[i] > 3) return fail(x, DCP_ESEQABC, "nucleotide index above 3");
   ++x->gen;
-  x->seq_off.assign(offsets, offsets + nseq + 1);
+  x->seq_off = std::move(seq_off);
   x->row_off = std::move(row_off);
   HIP_TRY(x, hipStreamSynchronize(x->stream), DCP_EFUNCUSE);
   HIP_TRY(x, x->d_nt.reserve((size_t)std::max<int64_t>(total, 1)), DCP_ENOMEM);
   HIP_TRY(x, x->d_seq_off.reserve((size_t)nseq + 1), DCP_ENOMEM);
-  HIP_TRY(x, x->d_row_off.reserve((size_t)nseq + 1), DCP_ENOMEM);
+  HIP_TRY(x, x->d_row_off.reserve((size_t)nint + 1), DCP_ENOMEM);
   HIP_TRY(x, x->d_rows.reserve((size_t)std::max<int64_t>(rows, 1)), DCP_ENOMEM);
   if (total)
     HIP_TRY(x, hipMemcpyAsync(x->d_nt.p, nt, (size_t)total, hipMemcpyHostToDevice, x->stream), DCP_EFUNCUSE);
-  HIP_TRY(x, hipMemcpyAsync(x->d_seq_off.p, x->seq_off.data(), ((size_t)nseq + 1) * sizeof(int64_t),
+  // (the caller's offsets: on one strand they are x->seq_off; the call waits for the copy before it returns)
+  HIP_TRY(x, hipMemcpyAsync(x->d_seq_off.p, offsets, ((size_t)nseq + 1) * sizeof(int64_t), hipMemcpyHostToDevice, x->stream),
+          DCP_EFUNCUSE);
+  HIP_TRY(x, hipMemcpyAsync(x->d_row_off.p, x->row_off.data(), ((size_t)nint + 1) * sizeof(int64_t),
                             hipMemcpyHostToDevice, x->stream),
           DCP_EFUNCUSE);
-  HIP_TRY(x, hipMemcpyAsync(x->d_row_off.p, x->row_off.data(), ((size_t)nseq + 1) * sizeof(int64_t),
-                            hipMemcpyHostToDevice, x->stream),
-          DCP_EFUNCUSE);
-  HIP_TRY(x, dcp_launch_encode(x->d_nt.p, x->d_seq_off.p, x->d_row_off.p, nseq, max_len, x->d_rows.p, x->stream),
+  HIP_TRY(x, (both ? dcp_launch_encode_strands : dcp_launch_encode)(x->d_nt.p, x->d_seq_off.p, x->d_row_off.p, nseq, max_len,
+                                                                    x->d_rows.p, x->stream),
           DCP_EFUNCUSE);
   HIP_TRY(x, hipStreamSynchronize(x->stream), DCP_EFUNCUSE);
+  return 0;
+}
+
+int dcp_hip_set_sequences(struct dcp_hip *x, int nseq, uint8_t const *nt, int64_t const *offsets)
+{
+  return dcp_hip_set_sequences_strands(x, nseq, nt, offsets, DCP_STRANDS_PLUS);
+}
+
+int dcp_hip_num_sequences(struct dcp_hip const *x) { return x ? (int)x->seq_off.size() - 1 : 0; }
+
+int dcp_hip_code_rows_read(struct dcp_hip const *x, int seq, uint32_t *out, int64_t rows)
+{
+  if (!x || !out || seq < 0 || seq >= (int)x->seq_off.size() - 1) return DCP_EFUNCUSE;
+  int64_t const first = x->row_off[(size_t)seq];
+  if (rows != x->row_off[(size_t)seq + 1] - first) return DCP_EFUNCUSE;
+  // (dcp_hip_set_sequences_strands has waited for its kernel before it returned)
+  if (hipSetDevice(x->device) != hipSuccess) return DCP_EFUNCUSE;
+  if (hipMemcpy(out, x->d_rows.p + first, (size_t)rows * sizeof(DcpCodeRow), hipMemcpyDeviceToHost) != hipSuccess) return DCP_EFUNCUSE;
   return 0;
 }
 

@@ -12,6 +12,7 @@ namespace
 {
 
 char const HEADER[] = "sequence\twindow\twindow_start\twindow_stop\thit\thit_start\thit_stop\tprofile\tabc\tlrt\tevalue\tmatch\n";
+char const HEADER_STRAND[] = "sequence\twindow\twindow_start\twindow_stop\thit\thit_start\thit_stop\tprofile\tabc\tlrt\tevalue\tmatch\tstrand\n";
 
 // a row of a run file: this, then `len` bytes of text
 struct Record
@@ -65,8 +66,8 @@ struct DcpProductRuns::Source
   }
 };
 
-DcpProductRuns::DcpProductRuns(std::string dir, int64_t budget_bytes)
-    : dir_(std::move(dir)), budget_(std::max<int64_t>(budget_bytes, 0))
+DcpProductRuns::DcpProductRuns(std::string dir, int64_t budget_bytes, bool strand_column)
+    : dir_(std::move(dir)), budget_(std::max<int64_t>(budget_bytes, 0)), header_(strand_column ? HEADER_STRAND : HEADER)
 {
 }
 
@@ -189,8 +190,8 @@ int DcpProductRuns::close(std::string const &file)
     // product_close (c-core/product.c:34-88) of rows that were never on disk; the strings stay for row()
     FILE *fp = fopen(file.c_str(), "wb");
     if (!fp) return fail(DCP_EFOPEN);
-    bool ok = fputs(HEADER, fp) >= 0;
-    file_bytes_ = (int64_t)strlen(HEADER);
+    bool ok = fputs(header_, fp) >= 0;
+    file_bytes_ = (int64_t)strlen(header_);
     for (Row const &r : held_)
     {
       ok = ok && fwrite(r.text.data(), 1, r.text.size(), fp) == r.text.size() && fputc('\n', fp) != EOF;
@@ -218,8 +219,8 @@ int DcpProductRuns::close(std::string const &file)
   }
   FILE *fp = fopen(file.c_str(), "wb");
   if (!fp) return fail(DCP_EFOPEN);
-  bool const ok = fputs(HEADER, fp) >= 0;
-  file_bytes_ = (int64_t)strlen(HEADER);
+  bool const ok = fputs(header_, fp) >= 0;
+  file_bytes_ = (int64_t)strlen(header_);
   offsets_.reserve((size_t)rows_ + 1);
   int rc = merge(runs_, mem ? &held_ : nullptr, fp, true);
   offsets_.push_back(file_bytes_);

@@ -33,7 +33,8 @@ public:
     std::string text;
   };
 
-  DcpProductRuns(std::string dir, int64_t budget_bytes);
+  // strand_column: the header names a 13th column, `strand` (the rows of a scan of both strands end in it)
+  DcpProductRuns(std::string dir, int64_t budget_bytes, bool strand_column = false);
   ~DcpProductRuns();
   DcpProductRuns(DcpProductRuns const &) = delete;
   DcpProductRuns &operator=(DcpProductRuns const &) = delete;
@@ -64,6 +65,7 @@ private:
 
   std::string dir_;
   int64_t budget_;
+  char const *header_;
   mutable std::mutex mu_;
   std::vector<Row> held_;
   int64_t held_bytes_ = 0, peak_bytes_ = 0, rows_ = 0, runs_written_ = 0, file_bytes_ = 0;

@@ -55,6 +55,7 @@ struct dcp_scan
   // the rows read the distributions of the profiles with hits from it: the database, which stays mapped, or what a
   // load from a HMMER3 file left in memory
   std::unique_ptr<DcpDecoderSource> db;
+  int strands = DCP_STRANDS_PLUS; // dcp_scan_set_strands: what the next dcp_scan_run scans of every read
   DcpHmmDecoders *hmm = nullptr; // `db`, when dcp_scan_setup_hmm set it: the error rate moves with the tables (dcp_scan_set_epsilon)
 };
 
@@ -430,6 +431,18 @@ int dcp_scan_set_gencode(struct dcp_scan *x, int gencode_id)
   return 0;
 }
 
+int dcp_scan_set_strands(struct dcp_scan *x, int strands)
+{
+  // no engine is asked: the mode belongs to the scan and reaches the GPU with the reads of the next run
+  if (!x) return raise(DCP_EFUNCUSE, __func__);
+  if (strands != DCP_STRANDS_PLUS && strands != DCP_STRANDS_BOTH)
+    return raise(DCP_EFUNCUSE, __func__, "strands must be DCP_STRANDS_PLUS or DCP_STRANDS_BOTH");
+  x->strands = strands;
+  return 0;
+}
+
+int dcp_scan_strands(struct dcp_scan const *x) { return x ? x->strands : raise(DCP_EFUNCUSE, __func__); }
+
 int dcp_scan_partition_range(struct dcp_scan const *x, int *first, int *count)
 {
   if (!x || !first || !count) return DCP_EFUNCUSE;
@@ -456,19 +469,24 @@ int dcp_scan_run(struct dcp_scan *x, struct dcp_batch *batch, char const *produc
   Phase ph;
   Knobs const knobs;
 
-  // batch_encode (c-core/batch.c:60-70): every read goes to HBM once
-  int const nseq = (int)batch->seqs.size();
+  // batch_encode (c-core/batch.c:60-70): every read goes to HBM once -- on both strands too: the engine then holds
+  // `nseq` = 2 x reads sequences, 2s read s as given and 2s + 1 its reverse complement, and all that follows (chunks,
+  // walk, passes, the order of the rows) works on those.  The rows map a sequence back to (read, strand).
+  bool const both = x->strands == DCP_STRANDS_BOTH;
+  if (batch->seqs.size() > (size_t)(both ? INT_MAX / 2 : INT_MAX)) return raise(DCP_EFUNCUSE, __func__, "too many reads");
+  int const nreads = (int)batch->seqs.size(), per = both ? 2 : 1, nseq = nreads * per;
   for (dcp_batch::Seq const &s : batch->seqs) // c-core/sequence.c:61-72
   {
     if (x->abc_name == "dna" && s.has_u) return raise(DCP_EDBDNASEQRNA, __func__);
     if (x->abc_name == "rna" && s.has_t) return raise(DCP_EDBRNASEQDNA, __func__);
   }
-  std::vector<int64_t> off((size_t)nseq + 1, 0);
-  for (int i = 0; i < nseq; ++i) off[(size_t)i + 1] = off[(size_t)i] + (int64_t)batch->seqs[(size_t)i].nt.size();
-  std::vector<uint8_t> nt((size_t)off[(size_t)nseq]);
-  for (int i = 0; i < nseq; ++i)
+  std::vector<int64_t> off((size_t)nreads + 1, 0);
+  for (int i = 0; i < nreads; ++i) off[(size_t)i + 1] = off[(size_t)i] + (int64_t)batch->seqs[(size_t)i].nt.size();
+  std::vector<uint8_t> nt((size_t)off[(size_t)nreads]);
+  for (int i = 0; i < nreads; ++i)
     memcpy(nt.data() + off[(size_t)i], batch->seqs[(size_t)i].nt.data(), batch->seqs[(size_t)i].nt.size());
-  if ((rc = dcp_hip_set_sequences(x->eng, nseq, nt.data(), off.data()))) return raise(rc, __func__, dcp_hip_strerror(x->eng));
+  if ((rc = dcp_hip_set_sequences_strands(x->eng, nreads, nt.data(), off.data(), x->strands)))
+    return raise(rc, __func__, dcp_hip_strerror(x->eng));
 
   // product_open (c-core/product.c:14-32)
   std::string const file = std::string(product_dir) + "/products.tsv";
@@ -478,10 +496,10 @@ int dcp_scan_run(struct dcp_scan *x, struct dcp_batch *batch, char const *produc
   int const nprof = dcp_hip_num_profiles(x->eng);
   std::vector<int32_t> K((size_t)std::max(nprof, 0)), len((size_t)nseq);
   for (int p = 0; p < nprof; ++p) K[(size_t)p] = dcp_hip_profile_core_size(x->eng, p);
-  for (int s = 0; s < nseq; ++s)
+  for (int s = 0; s < nseq; ++s) // (both strands: each read's length twice)
   {
-    if (batch->seqs[(size_t)s].nt.size() > (size_t)INT_MAX) return raise(DCP_EFUNCUSE, __func__, "a read is longer than INT_MAX");
-    len[(size_t)s] = (int32_t)batch->seqs[(size_t)s].nt.size();
+    if (batch->seqs[(size_t)(s / per)].nt.size() > (size_t)INT_MAX) return raise(DCP_EFUNCUSE, __func__, "a read is longer than INT_MAX");
+    len[(size_t)s] = (int32_t)batch->seqs[(size_t)(s / per)].nt.size();
   }
   // chunks (dcp_plan_chunks: profiles [p0, p1) x reads [s0, s1)): small enough for the window table of a chunk (2^21
   // pairs; DECIPHON_HIP_CHUNK_WINDOWS windows, 4 Mi by default -- a chunk holds every window of its pairs' no-hit
@@ -502,9 +520,9 @@ int dcp_scan_run(struct dcp_scan *x, struct dcp_batch *batch, char const *produc
   DcpScanWalk walk(nprof, K.data(), nseq, len.data());
   // (bytes below 2^63; what atof makes of no number is 0)
   int64_t const budget = knobs.product_mb >= 1.0e12 ? INT64_MAX : knobs.product_mb > 0 ? (int64_t)(knobs.product_mb * 1048576.0) : 0;
-  x->runs.reset(new DcpProductRuns(product_dir, budget));
+  x->runs.reset(new DcpProductRuns(product_dir, budget, both));
   DropRuns drop{x};
-  DcpScanRows rows(x->eng, x->db.get(), x->index_offset, x->abc_name.c_str(), batch, x->runs.get()); // (after all that its threads read)
+  DcpScanRows rows(x->eng, x->db.get(), x->index_offset, x->abc_name.c_str(), batch, x->runs.get(), both); // (after all that its threads read)
   Run r{x, walk, rows, ph};
   if (knobs.speculate)
   {

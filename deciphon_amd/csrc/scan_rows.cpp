@@ -14,9 +14,11 @@ namespace
 // hit as "<nucleotides>,<state>,<codon>,<amino>", the last two from decoder_decode / imm_gencode_decode
 // (c-core/match.c:66-89, c-core/decoder.c:38-58) for the emitting states.  *rc receives DCP_EDECODON when a step
 // cannot be decoded (the reference fails the scan there).
-std::string format_row(dcp_batch::Seq const &seq, int window, int wstart, int wstop, DcpHit const &hit,
-                       char const *accession, char const *abc, float lrt, uint32_t const *steps,
-                       DcpDecoder const &dec, std::atomic<int> *rc)
+// text, nt: the scanned strand of the read (the read's own, or its reverse complement); strand: '+' or '-' for the 13th
+// column of a scan of both strands, 0 for none.
+std::string format_row(dcp_batch::Seq const &seq, std::string const &text, uint8_t const *nt, char strand, int window,
+                       int wstart, int wstop, DcpHit const &hit, char const *accession, char const *abc, float lrt,
+                       uint32_t const *steps, DcpDecoder const &dec, std::atomic<int> *rc)
 {
   // a step: state id in the low 16 bits, emission length above (dcp_hip_path_steps_packed)
   auto step_id = [&](int i) { return (int)(steps[i] & 0xffffu); };
@@ -35,7 +37,7 @@ std::string format_row(dcp_batch::Seq const &seq, int window, int wstart, int ws
     char name[8];
     int const n = step_size(i), id = step_id(i);
     dcp_state_name(id, name);
-    out.append(seq.text, (size_t)(wstart + pos), (size_t)n);
+    out.append(text, (size_t)(wstart + pos), (size_t)n);
     out += ',';
     out += name;
     out += ',';
@@ -52,13 +54,13 @@ std::string format_row(dcp_batch::Seq const &seq, int window, int wstart, int ws
         // the code of the n-mer (imm_eseq's indexing: SURVEY 8a row S) keys the decoder's memo
         static unsigned const code_off[6] = {0, 0, 4, 20, 84, 340};
         unsigned code = 0;
-        for (int t = 0; t < n; ++t) code = code * 4 + seq.nt[(size_t)(wstart + pos + t)];
+        for (int t = 0; t < n; ++t) code = code * 4 + nt[(size_t)(wstart + pos + t)];
         std::atomic<uint8_t> &slot = dec.memo[entry * DCP_TABLE_SIZE + code_off[n] + code];
         uint8_t m = slot.load(std::memory_order_relaxed);
         if (m == 0xFF)
         {
           bool const found = dcp_decode_codon_prob((double)dec.epsilon, dec.base.data() + 4 * entry, dec.prior.data() + 64 * entry,
-                                                   seq.nt.data() + wstart + pos, n, codon);
+                                                   nt + wstart + pos, n, codon);
           m = found ? (uint8_t)(codon[0] * 16 + codon[1] * 4 + codon[2]) : (uint8_t)0xFE;
           slot.store(m, std::memory_order_relaxed);
         }
@@ -86,6 +88,11 @@ std::string format_row(dcp_batch::Seq const &seq, int window, int wstart, int ws
     else
       out += ',';
     pos += n;
+  }
+  if (strand)
+  {
+    out += '\t';
+    out += strand;
   }
   return out;
 }
@@ -126,10 +133,30 @@ int DcpHmmDecoders::read_decoder(int i, DcpDecoder &x) const
 }
 
 DcpScanRows::DcpScanRows(dcp_hip const *eng, DcpDecoderSource const *db, int index_offset, char const *abc,
-                         dcp_batch const *batch, DcpProductRuns *runs)
-    : eng_(eng), db_(db), index_offset_(index_offset), abc_(abc), batch_(batch), runs_(runs),
-      decoders_((size_t)std::max(dcp_hip_num_profiles(eng), 0))
+                         dcp_batch const *batch, DcpProductRuns *runs, bool both_strands)
+    : eng_(eng), db_(db), index_offset_(index_offset), abc_(abc), batch_(batch), runs_(runs), both_(both_strands),
+      decoders_((size_t)std::max(dcp_hip_num_profiles(eng), 0)), minus_(both_strands ? batch->seqs.size() : 0)
 {
+}
+
+// The minus strand of a read: the reverse complement of the text and of the indices dcp_batch_add keeps (A<->T, or
+// A<->U in the text of an RNA read, C<->G; an index i becomes 3 - i), once per read that has a minus hit.
+DcpScanRows::MinusStrand const &DcpScanRows::minus_strand(size_t read) const
+{
+  MinusStrand &m = minus_[read];
+  std::call_once(m.once, [&]() {
+    dcp_batch::Seq const &s = batch_->seqs[read];
+    size_t const n = s.nt.size();
+    char const *sym = s.has_u ? "ACGU" : "ACGT";
+    m.text.resize(n);
+    m.nt.resize(n);
+    for (size_t i = 0; i < n; ++i)
+    {
+      m.nt[i] = (uint8_t)(3 - s.nt[n - 1 - i]);
+      m.text[i] = sym[m.nt[i]];
+    }
+  });
+  return m;
 }
 
 void DcpScanRows::fill(LazyDecoder &ld, int profile) const
@@ -211,8 +238,14 @@ void DcpScanRows::format(std::vector<dcp_walk_hit> const &hits)
         decode_rc_.compare_exchange_strong(expected, ld.rc);
         return;
       }
+      // on both strands the walk's sequence 2s is read s as given, 2s + 1 its reverse complement
+      size_t const read = both_ ? (size_t)j.at.seq / 2 : (size_t)j.at.seq;
+      bool const minus = both_ && (j.at.seq & 1);
+      dcp_batch::Seq const &seq = batch_->seqs[read];
+      MinusStrand const *m = minus ? &minus_strand(read) : nullptr;
       out[k] = DcpProductRuns::Row{j.at.profile, j.at.seq, j.at.window, serial + (int64_t)k,
-                                   format_row(batch_->seqs[(size_t)j.at.seq], j.at.window, j.at.start, j.at.stop, j.hit,
+                                   format_row(seq, m ? m->text : seq.text, m ? m->nt.data() : seq.nt.data(),
+                                              !both_ ? (char)0 : minus ? '-' : '+', j.at.window, j.at.start, j.at.stop, j.hit,
                                               dcp_hip_profile_accession(eng_, j.at.profile), abc_.c_str(), j.at.lrt,
                                               j.steps, ld.dec, &decode_rc_)};
     });

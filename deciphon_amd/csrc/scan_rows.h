@@ -75,8 +75,13 @@ private:
 class DcpScanRows
 {
 public:
+  // both_strands: the walk's sequences are 2 x reads (dcp_hip_set_sequences_strands: 2s is read s, 2s + 1 its reverse
+  // complement) and every row ends in a strand column.  A minus row takes its nucleotides, the text of its match column
+  // and its codons from the reverse complement of what dcp_batch_add keeps of the read (uppercased and disambiguated
+  // first, then reversed and complemented -- that is the definition of the minus strand), built once per read that has
+  // a minus hit; its coordinates are the walk's, on that strand.
   DcpScanRows(dcp_hip const *eng, DcpDecoderSource const *db, int index_offset, char const *abc, dcp_batch const *batch,
-              DcpProductRuns *runs);
+              DcpProductRuns *runs, bool both_strands = false);
   ~DcpScanRows() { join(); }
   // decoder_setup (c-core/decoder.c:21-36) for the profiles of this batch -- reading a profile's distributions out of
   // the database and exponentiating them (a fraction of a millisecond, times hundreds of profiles with hits) -- by host
@@ -120,7 +125,14 @@ private:
     std::vector<uint32_t> owned;
     std::shared_ptr<LazyDecoder> dec;
   };
+  struct MinusStrand
+  {
+    std::once_flag once;
+    std::string text;
+    std::vector<uint8_t> nt;
+  };
   void fill(LazyDecoder &ld, int profile) const;
+  MinusStrand const &minus_strand(size_t read) const;
 
   dcp_hip const *eng_;
   DcpDecoderSource const *db_;
@@ -128,8 +140,10 @@ private:
   std::string abc_;
   dcp_batch const *batch_;
   DcpProductRuns *runs_;
+  bool both_;
   int64_t batches_ = 0;                                // with hits, so far
   std::vector<std::shared_ptr<LazyDecoder>> decoders_; // by local profile
+  mutable std::vector<MinusStrand> minus_;             // by read, on both strands (empty otherwise)
   std::vector<Job> found_;                             // of the batch between spans and format
   std::future<void> steps_copied_;                     // of the last batch with hits
   std::atomic<int> decode_rc_{0};

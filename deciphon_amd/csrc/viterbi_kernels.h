@@ -98,3 +98,7 @@ hipError_t dcp_launch_cost_pack_lds(int shape, DcpLaunch const &a, DcpPack const
 hipError_t dcp_launch_cost_fused(DcpLaunch const &a);
 hipError_t dcp_launch_encode(unsigned char const *nt, int64_t const *seq_off, int64_t const *row_off, int nseq,
                              int64_t max_len, DcpCodeRow *rows, hipStream_t stream);
+// both strands of nreads reads: sequence 2s is read s, 2s + 1 its reverse complement; seq_off[nreads + 1] (the reads
+// in nt), row_off[2 nreads + 1] (the rows in front of each sequence)
+hipError_t dcp_launch_encode_strands(unsigned char const *nt, int64_t const *seq_off, int64_t const *row_off, int nreads,
+                                     int64_t max_len, DcpCodeRow *rows, hipStream_t stream);

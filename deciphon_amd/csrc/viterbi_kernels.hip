@@ -478,6 +478,53 @@ __global__ void dcp_encode_kernel(unsigned char const *__restrict__ nt, int64_t 
   }
 }
 
+// Code rows of both strands of every read from one pass over its nucleotides (dcp_code_rows_of, include/deciphon_host.h,
+// states the rows): read s becomes sequence 2s as given and sequence 2s + 1, its reverse complement y[i] = 3 - x[n-1-i],
+// which is never materialised.  Row j of the reverse complement holds the t-mers y[j-t..j-1] = 3 - x[n-j+t-1..n-j]: the
+// thread of position r = n - j extends them to the RIGHT of r on the given strand as it extends the plus strand's to
+// the left, so it reads x[r-5..r+4], writes plus row r and minus row n - r, each as two 16-byte stores.
+// seq_off[nreads + 1]: the reads in nt; row_off[2 nreads + 1]: the rows in front of each of the 2 nreads sequences.
+__global__ void dcp_encode_strands_kernel(unsigned char const *__restrict__ nt, int64_t const *__restrict__ seq_off,
+                                          int64_t const *__restrict__ row_off, int nreads, DcpCodeRow *__restrict__ rows)
+{
+  // gridDim.y is capped at 65535: stride over the reads
+  for (int s = (int)blockIdx.y; s < nreads; s += (int)gridDim.y)
+  {
+    int64_t const n = seq_off[s + 1] - seq_off[s];
+    unsigned char const *x = nt + seq_off[s];
+    uint4 *plus = reinterpret_cast<uint4 *>(rows + row_off[2 * (int64_t)s]); // (rows are 32 bytes from a 256-byte base)
+    uint4 *minus = reinterpret_cast<uint4 *>(rows + row_off[2 * (int64_t)s + 1]);
+    if (n == 0) // an empty read: row 0 of either strand, and nothing to load
+    {
+      if (blockIdx.x == 0 && threadIdx.x == 0) plus[0] = plus[1] = minus[0] = minus[1] = make_uint4(0u, 0u, 0u, 0u);
+      continue;
+    }
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r <= n; r += (int64_t)gridDim.x * blockDim.x)
+    {
+      unsigned const off[5] = {0u, 4u, 20u, 84u, 340u};
+      unsigned cp[5], cm[5], ip = 0, im = 0;
+#pragma unroll
+      for (int t = 1; t <= 5; ++t)
+      {
+        // either strand's new symbol is its t-mer's leftmost, the most significant digit
+        // (a symbol beyond either end is read from the nearest position inside, n > 0, and dropped: ten loads in
+        // flight at once, none behind a branch)
+        bool const okp = r - t >= 0, okm = r + t <= n;
+        unsigned const lp = x[okp ? r - t : 0], lm = x[okm ? r + t - 1 : n - 1];
+        unsigned const sp = okp ? lp : 0u, sm = okm ? 3u - lm : 0u;
+        ip += sp << (2 * (t - 1));
+        im += sm << (2 * (t - 1));
+        cp[t - 1] = okp ? off[t - 1] + ip : 0u;
+        cm[t - 1] = okm ? off[t - 1] + im : 0u;
+      }
+      plus[2 * r] = make_uint4(cp[0], cp[1], cp[2], cp[3]);
+      plus[2 * r + 1] = make_uint4(cp[4], 0u, 0u, 0u);
+      minus[2 * (n - r)] = make_uint4(cm[0], cm[1], cm[2], cm[3]);
+      minus[2 * (n - r) + 1] = make_uint4(cm[4], 0u, 0u, 0u);
+    }
+  }
+}
+
 // trellis_unzip on the device (dcp_trellis_step, dcp_states.h): one thread walks one problem's trellis from T at stage L
 // back to S at stage 0 and writes the steps, packed as state_id | seqsize << 16, from
 // the END of its buffer backwards, so that they read forwards in path order.
@@ -914,5 +961,17 @@ hipError_t dcp_launch_encode(unsigned char const *nt, int64_t const *seq_off, in
   if (bx > 1024) bx = 1024;
   hipLaunchKernelGGL(dcp_encode_kernel, dim3(bx, (unsigned)(nseq < 65535 ? nseq : 65535)), dim3(256), 0, stream, nt,
                      seq_off, row_off, nseq, rows);
+  return hipGetLastError();
+}
+
+hipError_t dcp_launch_encode_strands(unsigned char const *nt, int64_t const *seq_off, int64_t const *row_off, int nreads,
+                                     int64_t max_len, DcpCodeRow *rows, hipStream_t stream)
+{
+  if (nreads <= 0) return hipSuccess;
+  unsigned bx = (unsigned)((max_len + 1 + 255) / 256);
+  if (bx < 1) bx = 1;
+  if (bx > 1024) bx = 1024;
+  hipLaunchKernelGGL(dcp_encode_strands_kernel, dim3(bx, (unsigned)(nreads < 65535 ? nreads : 65535)), dim3(256), 0,
+                     stream, nt, seq_off, row_off, nreads, rows);
   return hipGetLastError();
 }

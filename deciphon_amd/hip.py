@@ -12,6 +12,16 @@ _LIB = None
 TABLE_SIZE = 1364
 NUM_TRANS = 8
 NUM_XTRANS = 13
+STRANDS = {"plus": 0, "both": 1}  # DCP_STRANDS_PLUS, DCP_STRANDS_BOTH
+
+
+def strands_code(strands) -> int:
+    """"plus" / "both" (or the C value itself) -> DCP_STRANDS_*; ValueError for a name that is neither."""
+    if isinstance(strands, str):
+        if strands not in STRANDS:
+            raise ValueError(f"strands must be 'plus' or 'both', not {strands!r}")
+        return STRANDS[strands]
+    return int(strands)
 
 
 class HipError(RuntimeError):
@@ -76,6 +86,9 @@ def load_library() -> C.CDLL:
     L.dcp_hip_clear_profiles.restype = None
     L.dcp_hip_encode.argtypes = [C.c_char_p, C.c_int64, vp]
     L.dcp_hip_set_sequences.argtypes = [vp, i32, vp, vp]
+    L.dcp_hip_set_sequences_strands.argtypes = [vp, i32, vp, vp, i32]
+    L.dcp_hip_num_sequences.argtypes = [vp]
+    L.dcp_hip_code_rows_read.argtypes = [vp, i32, vp, C.c_int64]
     L.dcp_hip_set_mode.argtypes = [vp, i32, i32]
     L.dcp_hip_set_xtrans_table.argtypes = [vp, i32, vp]
     L.dcp_hip_xtrans.argtypes = [i32, i32, i32, vp]
@@ -265,15 +278,32 @@ class Engine:
             raise HipError(8, self.lib.dcp_hip_strerror(self.h).decode())
 
     # ---- sequences ------------------------------------------------------------
-    def set_sequences(self, seqs) -> None:
-        """seqs: list of uint8 arrays of nucleotide indices 0..3."""
+    def set_sequences(self, seqs, strands="plus") -> None:
+        """seqs: list of uint8 arrays of nucleotide indices 0..3.  strands="both" (dcp_hip_set_sequences_strands): the
+        engine holds 2 len(seqs) sequences, 2s = seqs[s] and 2s + 1 = its reverse complement 3 - seqs[s][::-1], whose
+        code rows the GPU writes from the one upload; windows address those indices."""
+        code = strands_code(strands)
         seqs = [np.ascontiguousarray(s, dtype=np.uint8) for s in seqs]
         off = np.zeros(len(seqs) + 1, dtype=np.int64)
         np.cumsum([len(s) for s in seqs], out=off[1:])
         nt = np.concatenate(seqs) if seqs else np.zeros(0, dtype=np.uint8)
         nt = np.ascontiguousarray(nt)
-        self._check(self.lib.dcp_hip_set_sequences(self.h, len(seqs), _p(nt), _p(off)))
-        self._seq_lens = [len(s) for s in seqs]
+        self._check(self.lib.dcp_hip_set_sequences_strands(self.h, len(seqs), _p(nt), _p(off), code))
+        self._seq_lens = [len(s) for s in seqs for _ in range(2 if code == STRANDS["both"] else 1)]
+
+    @property
+    def num_sequences(self) -> int:
+        """Internal sequences: the reads of the last set_sequences, twice as many on both strands."""
+        return self.lib.dcp_hip_num_sequences(self.h)
+
+    def code_rows(self, seq: int) -> np.ndarray:
+        """The code rows of internal sequence `seq` as they lie in HBM, copied: uint32 [len + 1][8]
+        (host.code_rows_of states them)."""
+        if not 0 <= seq < len(self._seq_lens):
+            raise IndexError(seq)
+        out = np.empty((self._seq_lens[seq] + 1, 8), dtype=np.uint32)
+        self._check(self.lib.dcp_hip_code_rows_read(self.h, int(seq), _p(out), len(out)))
+        return out
 
     def set_mode(self, multi_hits: bool = True, hmmer3_compat: bool = False) -> None:
         self._check(self.lib.dcp_hip_set_mode(self.h, int(multi_hits), int(hmmer3_compat)))

@@ -44,6 +44,7 @@ def _lib():
     L.dcp_partition_size.restype = C.c_long
     L.dcp_window_count.argtypes = [C.c_int64, i32]
     L.dcp_window_count.restype = C.c_int64
+    L.dcp_code_rows_of.argtypes = [vp, C.c_int64, i32, vp]
     L.dcp_cost_order_map.argtypes = [i32, i32, vp]
     L.dcp_row_lane_offsets.argtypes = [i32, i32, i32, i32, vp]
     L.dcp_reemit_tiles.argtypes = [i32, vp, vp, vp, C.c_int64]
@@ -317,6 +318,17 @@ class WindowIter:
 
     def set_last_hit_position(self, pos: int) -> None:
         self.w.last_hit_pos = pos
+
+
+def code_rows_of(nt, minus: bool = False) -> np.ndarray:
+    """The code rows of one read of nucleotide indices 0..3 as the engine holds them, uint32 [len + 1][8]
+    (dcp_code_rows_of): of the read as given, or -- minus -- of its reverse complement 3 - nt[::-1]."""
+    nt = np.ascontiguousarray(nt, np.uint8)
+    rows = np.empty((len(nt) + 1, 8), np.uint32)
+    rc = _lib().dcp_code_rows_of(nt.ctypes.data_as(C.c_void_p), len(nt), int(bool(minus)), rows.ctypes.data_as(C.c_void_p))
+    if rc:
+        raise HipError(rc)
+    return rows
 
 
 def window_count(seq_size: int, core_size: int) -> int:

@@ -8,9 +8,9 @@ import dataclasses
 import os
 
 from .hip import HipError as DeciphonError
-from .hip import load_library
+from .hip import load_library, strands_code
 
-__all__ = ["Scan", "Batch", "Sequence", "DeciphonError"]
+__all__ = ["Scan", "Batch", "Sequence", "DeciphonError", "hit_on_read"]
 
 _CALLBACK = C.CFUNCTYPE(None, C.c_void_p)
 
@@ -29,6 +29,8 @@ def _lib():
     L.dcp_scan_setup_hmm.argtypes = [vp, C.c_char_p, i32, C.c_float, C.c_bool, C.c_bool, _CALLBACK, vp]
     L.dcp_scan_set_epsilon.argtypes = [vp, C.c_float]
     L.dcp_scan_set_gencode.argtypes = [vp, i32]
+    L.dcp_scan_set_strands.argtypes = [vp, i32]
+    L.dcp_scan_strands.argtypes = [vp]
     L.dcp_scan_partition_range.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
     L.dcp_scan_run.argtypes = [vp, vp, C.c_char_p]
     L.dcp_scan_interrupt.argtypes = [vp]
@@ -48,6 +50,22 @@ def _lib():
     L.dcp_batch_reset.restype = None
     L._scan_ready = True
     return L
+
+
+def hit_on_read(row, read_length: int):
+    """(start, stop, strand) of a product row's hit on the read AS GIVEN, 0-based and half-open.  `row`: a row of
+    products.tsv, the string or its fields; a 12-column row (a scan of the plus strand) is a "+" row.  The row's own
+    coordinates are on the scanned strand: a minus hit [ws + hs, ws + he) of the reverse complement of a read of L
+    nucleotides lies at [L - (ws + he), L - (ws + hs)) of the read."""
+    f = row.split("\t") if isinstance(row, str) else list(row)
+    ws, hs, he = int(f[2]), int(f[5]), int(f[6])
+    strand = f[12] if len(f) > 12 else "+"
+    if strand == "+":
+        return ws + hs, ws + he, "+"
+    if strand != "-":
+        raise ValueError(f"strand column {strand!r}")
+    L = int(read_length)
+    return L - (ws + he), L - (ws + hs), "-"
 
 
 @dataclasses.dataclass
@@ -84,12 +102,16 @@ class Batch:
 class Scan:
     """Same constructor and methods as python-core's Scan.  `partition=(device, index, nparts)`
     (not in the reference) makes this scan own one contiguous profile partition on one GPU;
-    `balanced=True` puts the partition boundaries where they balance the sum of core sizes."""
+    `balanced=True` puts the partition boundaries where they balance the sum of core sizes.
+    `strands="both"` (not in the reference either: dcp_scan_set_strands) scans the reverse complement of every read as
+    well: products.tsv gains a 13th column `strand`, and a "-" row's coordinates and match column are on the reverse
+    complement of the read as Batch.add keeps it (hit_on_read maps them back)."""
 
     def __init__(self, dbfile, port: int = 0, num_threads: int = 1, multi_hits: bool = True,
                  hmmer3_compat: bool = False, cache: bool = False, partition=None, on_window=None,
-                 balanced: bool = False, progress_callback: bool = True, _hmm=None):
+                 balanced: bool = False, progress_callback: bool = True, _hmm=None, strands="plus"):
         self._lib = _lib()
+        strands = strands_code(strands)
         self._cscan = self._lib.dcp_scan_new()
         if not self._cscan:
             raise MemoryError()
@@ -118,18 +140,29 @@ class Scan:
             device, index, nparts = partition
             setup = self._lib.dcp_scan_setup_partition_balanced if balanced else self._lib.dcp_scan_setup_partition
             rc = setup(self._cscan, path, device, index, nparts, multi_hits, hmmer3_compat, self._cb, None)
+        if not rc:
+            rc = self._lib.dcp_scan_set_strands(self._cscan, strands)
         if rc:
             self.free()
             raise DeciphonError(rc)
 
     @classmethod
     def from_hmm(cls, hmmfile, gencode: int = 1, epsilon: float = 0.01, multi_hits: bool = True,
-                 hmmer3_compat: bool = False, on_window=None, progress_callback: bool = True):
+                 hmmer3_compat: bool = False, on_window=None, progress_callback: bool = True, strands="plus"):
         """A scan straight from a HMMER3 text file (dcp_scan_setup_hmm, not in the reference): the tables are made
         on the GPU and stay there, no .dcp is written, and the rows are those of a scan of the file pressed at the
         same `gencode` and `epsilon`."""
         return cls(hmmfile, multi_hits=multi_hits, hmmer3_compat=hmmer3_compat, on_window=on_window,
-                   progress_callback=progress_callback, _hmm=(gencode, epsilon))
+                   progress_callback=progress_callback, _hmm=(gencode, epsilon), strands=strands)
+
+    def set_strands(self, strands):
+        """"plus" or "both" for every later run (dcp_scan_set_strands); allowed at any time between runs."""
+        if rc := self._lib.dcp_scan_set_strands(self._cscan, strands_code(strands)):
+            raise DeciphonError(rc)
+
+    @property
+    def strands(self) -> str:
+        return "both" if self._lib.dcp_scan_strands(self._cscan) == 1 else "plus"
 
     def set_epsilon(self, epsilon: float):
         """A scan made by from_hmm at another error rate (dcp_scan_set_epsilon): the next run writes the rows of a

@@ -184,6 +184,25 @@ int dcp_scan_set_epsilon(struct dcp_scan *, float epsilon);
  * held -- all checked before the GPU is touched, the scan left as it was.  Not to be called while dcp_scan_run runs on
  * that scan.  The rows of the last run (dcp_scan_product) stay valid. */
 int dcp_scan_set_gencode(struct dcp_scan *, int gencode_id);
+/* Not in the reference, which scans every read in the orientation it was given and no other (its GFF writer has
+ * strand "+" for every hit): DCP_STRANDS_BOTH makes every later dcp_scan_run scan both strands of every read.  The reads
+ * go to the GPU once; the code rows of the reverse complements are written there (dcp_hip_set_sequences_strands), and
+ * the scan walks 2 x reads sequences.  The MINUS STRAND of a read is the reverse complement of the text dcp_batch_add
+ * keeps -- uppercased and disambiguated first, then reversed with A<->T (A<->U for an RNA read) and C<->G -- not the
+ * disambiguation of the reverse complement: the two differ only where c-core/disambiguate.c breaks a tie.
+ * products.tsv then has a 13th column `strand`, + or -, and its rows are in (profile, read, strand with + first,
+ * window) order.  window_start, window_stop, hit_start, hit_stop and the match column of a - row are on the scanned
+ * strand, 0-based from the 5' end of the reverse complement: exactly what a plain scan of the reverse-complemented
+ * read prints.  On the read as given a hit of a read of L nucleotides spans
+ * [L - (window_start + hit_stop), L - (window_start + hit_start)).  DCP_STRANDS_PLUS, the default, is the reference's
+ * behaviour and its 12 columns.  Allowed before or after any setup call and between runs; DCP_EFUNCUSE for NULL or
+ * another value, without touching a GPU.  dcp_scan_strands: the mode a scan is in (DCP_EFUNCUSE for NULL). */
+#ifndef DCP_STRANDS_PLUS /* (include/deciphon_hip.h has the same two) */
+#define DCP_STRANDS_PLUS 0
+#define DCP_STRANDS_BOTH 1
+#endif
+int dcp_scan_set_strands(struct dcp_scan *, int strands);
+int dcp_scan_strands(struct dcp_scan const *);
 /* Number of product rows the last dcp_scan_run wrote, and row i (without newline).  The pointer stands until the next
  * dcp_scan_run or dcp_scan_del of that scan.  Once the scan has spilled rows to run files (dcp_scan_product_stats:
  * runs > 0; DECIPHON_HIP_PRODUCT_MB) it stands only until the next dcp_scan_product on that scan, and

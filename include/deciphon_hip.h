@@ -140,6 +140,25 @@ void dcp_hip_clear_profiles(struct dcp_hip *);
  * and writes n indices. */
 int dcp_hip_encode(char const *data, int64_t n, uint8_t *out);
 int dcp_hip_set_sequences(struct dcp_hip *, int nseq, uint8_t const *nt, int64_t const *offsets);
+/* Not in the reference, which scans a read only as given: the same with both strands of every read.  DCP_STRANDS_PLUS
+ * is dcp_hip_set_sequences.  With DCP_STRANDS_BOTH the engine holds 2 * nseq sequences: sequence 2s is read s as given,
+ * sequence 2s + 1 its reverse complement rc[i] = 3 - nt[n-1-i].  The reads go up once; the code rows of both strands are
+ * written by one kernel from them, and no reverse-complemented copy exists on either side of the bus.  struct
+ * dcp_hip_window.seq addresses these internal indices, coordinates of sequence 2s + 1 counting from the 5' end of the
+ * reverse complement; every cost and path entry point then works as on 2 * nseq plain reads.  The contract is that of
+ * dcp_hip_set_sequences: everything is checked before anything is replaced, DCP_ESEQABC for an index above 3,
+ * DCP_EFUNCUSE while batches are outstanding; and DCP_EFUNCUSE for nseq above INT_MAX / 2 or another value of strands. */
+#ifndef DCP_STRANDS_PLUS /* (include/deciphon.h has the same two) */
+#define DCP_STRANDS_PLUS 0
+#define DCP_STRANDS_BOTH 1
+#endif
+int dcp_hip_set_sequences_strands(struct dcp_hip *, int nseq, uint8_t const *nt, int64_t const *offsets, int strands);
+/* The number of internal sequences: nseq of the last dcp_hip_set_sequences, twice that on both strands. */
+int dcp_hip_num_sequences(struct dcp_hip const *);
+/* test hook, a read-only query like dcp_hip_profile_read: the code rows of internal sequence `seq` as they lie in HBM,
+ * out[rows * 8] (struct DcpCodeRow, csrc/dcp_types.h; dcp_code_rows_of, include/deciphon_host.h, states them); rows
+ * must be its length + 1. */
+int dcp_hip_code_rows_read(struct dcp_hip const *, int seq, uint32_t *out, int64_t rows);
 
 /* ---- special transitions (replaces work_reset -> xtrans_setup, c-core/work.c:47-51) ---- */
 int dcp_hip_set_mode(struct dcp_hip *, int multi_hits, int hmmer3_compat);
