@@ -42,7 +42,7 @@ int ensure_xt(dcp_hip *x, int rows_needed)
   return 0;
 }
 
-// a staged list goes up from pinned memory (see dcp_hip::Bank); dev has been reserved
+// a staged list goes up from pinned memory (see WindowLists); dev has been reserved
 template <class T> int upload(dcp_hip *x, DevBuf<T> &dev, PinBuf<T> &pinned, std::vector<T> const &v, hipStream_t stream)
 {
   if (v.empty()) return 0;
@@ -55,11 +55,13 @@ template <class T> int upload(dcp_hip *x, DevBuf<T> &dev, PinBuf<T> &pinned, std
 } // namespace
 
 // Ask for a plan, reserve, upload.
-int stage(dcp_hip *x, int n, dcp_hip_window const *w, ArenaKind arena_kind, Staged &st, hipStream_t origin)
+int stage(Pass const &ps, int n, dcp_hip_window const *w, ArenaKind arena_kind, Staged &st, hipStream_t origin)
 {
-  if (!origin) origin = x->stream;
+  dcp_hip *const x = ps.x;
+  WindowLists &B = ps.lists;
+  if (!origin) origin = ps.on.stream;
   if (n < 0 || (n > 0 && !w)) return fail(x, DCP_EFUNCUSE, "bad window array");
-  if (BK(x).n >= 0) return fail(x, DCP_EFUNCUSE, "a dcp_hip_cost_hits_begin is outstanding on these buffers: call dcp_hip_cost_hits_end first");
+  if (ps.batch && ps.batch->n >= 0) return fail(x, DCP_EFUNCUSE, "a dcp_hip_cost_hits_begin is outstanding on these buffers: call dcp_hip_cost_hits_end first");
   if (x->committed != x->profiles.size()) return fail(x, DCP_EFUNCUSE, "profiles not committed");
   // DECIPHON_HIP_PACK=0 keeps every window on the one-window-per-wavefront kernels, DECIPHON_HIP_PACK_LDS=0 every pack
   // on the kernels that read their rows from global memory (tests compare, and flip them between calls)
@@ -80,15 +82,14 @@ int stage(dcp_hip *x, int n, dcp_hip_window const *w, ArenaKind arena_kind, Stag
   Refusal const refused = plan_stage(in, st);
   if (refused.code) return fail(x, refused.code, refused.what);
   if (st.c_begin[DCP_STRIP_CLASS + 1] > st.c_begin[DCP_STRIP_CLASS])
-    HIP_TRY(x, BK(x).d_ring.reserve((size_t)DCP_RING_SLOTS * DCP_RING_FLOATS), DCP_ENOMEM);
+    HIP_TRY(x, B.d_ring.reserve((size_t)DCP_RING_SLOTS * DCP_RING_FLOATS), DCP_ENOMEM);
   int rc = ensure_xt(x, st.max_xt_row + 1);
   if (rc) return rc;
-  if (x->cur != 2) x->staged_n = -1; // a cost bank's problem list and results are about to be replaced
+  if (ps.batch) x->staged_n = -1; // a cost pass: a batch's problem list and results are about to be replaced
   // every allocation first: after the first copy is enqueued nothing below can fail but a copy itself
-  HIP_TRY(x, BK(x).d_problems.reserve(std::max(st.problems.size(), (size_t)1)), DCP_ENOMEM);
-  if (!st.packs.empty()) HIP_TRY(x, BK(x).d_packs.reserve(st.packs.size()), DCP_ENOMEM);
-  if (!st.pack_groups.empty()) HIP_TRY(x, BK(x).d_pack_groups.reserve(st.pack_groups.size()), DCP_ENOMEM);
-  dcp_hip::Bank &B = BK(x);
+  HIP_TRY(x, B.d_problems.reserve(std::max(st.problems.size(), (size_t)1)), DCP_ENOMEM);
+  if (!st.packs.empty()) HIP_TRY(x, B.d_packs.reserve(st.packs.size()), DCP_ENOMEM);
+  if (!st.pack_groups.empty()) HIP_TRY(x, B.d_pack_groups.reserve(st.pack_groups.size()), DCP_ENOMEM);
   if (B.up_pending) HIP_TRY(x, hipEventSynchronize(B.up_ev), DCP_EFUNCUSE); // the previous lists have gone up
   B.up_pending = false;
   if ((rc = upload(x, B.d_problems, B.h_problems, st.problems, origin))) return rc;
@@ -99,55 +100,33 @@ int stage(dcp_hip *x, int n, dcp_hip_window const *w, ArenaKind arena_kind, Stag
   return 0;
 }
 
-DcpLaunch launch_args(dcp_hip *x, StagedPlan const &st, int c)
+DcpLaunch launch_args(Pass const &ps, StagedPlan const &st, int c)
 {
+  dcp_hip const *const x = ps.x;
   DcpLaunch a;
   a.pool = x->d_pool.p;
   a.profiles = x->d_profiles.p;
-  a.problems = BK(x).d_problems.p + st.c_begin[c];
+  a.problems = ps.lists.d_problems.p + st.c_begin[c];
   a.code_rows = x->d_rows.p;
   a.xt_table = x->d_xt.p;
-  a.out = BK(x).d_out.p;
+  a.out = ps.lists.d_out.p;
   a.arena = x->d_trellis.p;
   a.nprob = st.c_begin[c + 1] - st.c_begin[c];
-  a.stream = x->stream;
-  a.ring = BK(x).d_ring.p;
+  a.stream = ps.on.stream;
+  a.ring = ps.lists.d_ring.p;
   return a;
-}
-
-// Launches the path (or cost) kernels of every class present: the classes run
-// concurrently on their own streams, forked from and joined back into x->stream.
-int launch_all(dcp_hip *x, StagedPlan const &st, bool path)
-{
-  int classes = 0;
-  for (int c = 0; c < DCP_NUM_CLASSES; ++c) classes += st.c_begin[c + 1] > st.c_begin[c];
-  Fork fk(x, classes > 1);
-  int rc = fk.begin(x->stream);
-  if (rc) return rc;
-  for (int c = 0; c < DCP_NUM_CLASSES; ++c)
-  {
-    DcpLaunch a = launch_args(x, st, c);
-    if (a.nprob <= 0) continue;
-    if (path && c == DCP_STRIP_CLASS) continue; // replayed from the DP table instead (path_literal)
-    if ((rc = fk.enter(x->cls_branch[c], a))) return rc;
-    HIP_TRY(x, path ? dcp_launch_path(c, a) : dcp_launch_cost(c, a), DCP_EFUNCUSE);
-    if ((rc = fk.leave(x->cls_branch[c]))) return rc;
-  }
-  return fk.join();
 }
 
 // the device sees a pack group as an int2 (dcp_launch_cost_pack_lds), the plan as two plain int32
 static_assert(sizeof(PackGroup) == sizeof(int2) && alignof(PackGroup) <= alignof(int2), "PackGroup goes up as int2");
 
 // Cost pass: ask for the schedule (cost_schedule, stage_plan.h: which kernels, in which order, on which branches), run
-// it.  Everything is forked from `origin` (the stream the window lists were uploaded on; x->stream by default) and
-// joined into x->stream.
-// reps > 1 (measurement): every kernel `reps` times in its own stream before the join -- the passes of a kernel class
-// follow each other without waiting for the other classes, exactly as the batches of a scan do when a second batch is
-// begun while the first is in flight (dcp_hip_cost_hits_begin): no kernel's tail leaves the GPU idle but the last's.
-int launch_cost_all(dcp_hip *x, StagedPlan const &st, hipStream_t origin, int reps)
+// it.  Everything is forked from `origin` (the stream the window lists were uploaded on; the pass's own by default) and
+// joined into the pass's stream.
+int launch_cost_all(Pass const &ps, StagedPlan const &st, hipStream_t origin)
 {
-  if (!origin) origin = x->stream;
+  dcp_hip *const x = ps.x;
+  if (!origin) origin = ps.on.stream;
   // DECIPHON_HIP_NARROW=0: the class's kernel for all its windows (tests compare)
   char const *narrow_env = getenv("DECIPHON_HIP_NARROW");
   // DECIPHON_HIP_XCD_PLACEMENT=plain | eighths: every class's cost kernel that way (measurements, tests); auto, or
@@ -160,40 +139,37 @@ int launch_cost_all(dcp_hip *x, StagedPlan const &st, hipStream_t origin, int re
     else if (strcmp(e, "auto")) return fail(x, DCP_EFUNCUSE, "DECIPHON_HIP_XCD_PLACEMENT is not plain, eighths or auto");
   }
   std::vector<CostLaunch> const schedule = cost_schedule(st, !(narrow_env && narrow_env[0] == '0'));
-  // x->stream joins the kernels only after the last launch (Fork::join): a wait is a barrier in x->stream's hardware
+  // the pass's stream joins the kernels only after the last launch (Fork::join): a wait is a barrier in its hardware
   // queue, and a stream that shares that queue would start its kernel behind every barrier issued before
   // (profiles/r02_step_timeline.txt)
-  Fork fk(x, schedule.size() > 1 || origin != x->stream);
+  Fork fk(ps, schedule.size() > 1 || origin != ps.on.stream);
   int rc = fk.begin(origin);
   if (rc) return rc;
-  dcp_hip::Bank &B = BK(x);
+  WindowLists &B = ps.lists;
   uint32_t const ncode_rows = (uint32_t)x->row_off.back();
   for (CostLaunch const &e : schedule)
   {
-    Branch const &branch = (e.branch == BRANCH_NARROW ? x->narrow_branch : e.branch == BRANCH_PACK ? x->pack_branch : x->cls_branch)[e.index];
-    DcpLaunch a = launch_args(x, st, 0);
+    Branch const &branch = (e.branch == BRANCH_NARROW ? x->narrow_branch : e.branch == BRANCH_PACK ? x->pack_branch : ps.on.cls_branch)[e.index];
+    DcpLaunch a = launch_args(ps, st, 0);
     if ((rc = fk.enter(branch, a))) return rc;
     a.problems = B.d_problems.p + e.first; // (the pack kernels do not read them)
     a.nprob = e.count;
     a.windows_per_profile = e.windows_per_profile;
     a.placement = placement;
-    for (int r = 0; r < reps; ++r)
+    hipError_t err = hipSuccess;
+    switch (e.kernel)
     {
-      hipError_t err = hipSuccess;
-      switch (e.kernel)
-      {
-      case COST_CLASS: err = dcp_launch_cost(e.index, a); break;
-      case COST_NARROW: err = dcp_launch_cost_narrow(e.index, a); break;
-      case COST_FUSED: err = dcp_launch_cost_fused(a); break;
-      case COST_PACK: err = dcp_launch_cost_pack(e.index, a, B.d_packs.p + e.first, e.count, ncode_rows); break;
-      case COST_PACK_LDS:
-        err = dcp_launch_cost_pack_lds(e.index, a, B.d_packs.p + st.pk_begin[e.index],
-                                       reinterpret_cast<int2 const *>(B.d_pack_groups.p + e.first), e.count, ncode_rows);
-        break;
-      default: break; // COST_NONE
-      }
-      if (err != hipSuccess) return fail(x, DCP_EFUNCUSE, "cost kernel launch", err);
+    case COST_CLASS: err = dcp_launch_cost(e.index, a); break;
+    case COST_NARROW: err = dcp_launch_cost_narrow(e.index, a); break;
+    case COST_FUSED: err = dcp_launch_cost_fused(a); break;
+    case COST_PACK: err = dcp_launch_cost_pack(e.index, a, B.d_packs.p + e.first, e.count, ncode_rows); break;
+    case COST_PACK_LDS:
+      err = dcp_launch_cost_pack_lds(e.index, a, B.d_packs.p + st.pk_begin[e.index],
+                                     reinterpret_cast<int2 const *>(B.d_pack_groups.p + e.first), e.count, ncode_rows);
+      break;
+    default: break; // COST_NONE
     }
+    if (err != hipSuccess) return fail(x, DCP_EFUNCUSE, "cost kernel launch", err);
     if ((rc = fk.leave(branch))) return rc;
   }
   return fk.join();
@@ -235,8 +211,8 @@ struct dcp_hip *dcp_hip_new(int device)
   if (hipSetDevice(device) != hipSuccess) return nullptr;
   dcp_hip *x = new dcp_hip;
   x->device = device;
-  bool ok = hipStreamCreateWithFlags(&x->stream, hipStreamNonBlocking) == hipSuccess;
-  ok = ok && hipEventCreateWithFlags(&x->fork_ev, hipEventDisableTiming) == hipSuccess;
+  bool ok = hipStreamCreateWithFlags(&x->cost_set.stream, hipStreamNonBlocking) == hipSuccess;
+  ok = ok && hipEventCreateWithFlags(&x->cost_set.fork_ev, hipEventDisableTiming) == hipSuccess;
   int prio_low = 0, prio_high = 0;
   ok = ok && hipDeviceGetStreamPriorityRange(&prio_low, &prio_high) == hipSuccess;
   // The multi-wave classes (K > 640) run on high-priority streams.  A workgroup of several wavefronts of 160-256
@@ -247,7 +223,7 @@ struct dcp_hip *dcp_hip_new(int device)
   // DECIPHON_HIP_PRIO_FROM: first class (viterbi_kernels.h) that gets one; 99 = none (experiments).
   int prio_from = 6;
   if (char const *e = getenv("DECIPHON_HIP_PRIO_FROM")) prio_from = atoi(e);
-  for (int c = 0; ok && c < DCP_NUM_CLASSES; ++c) ok = create_branch(x->cls_branch[c], c >= prio_from ? prio_high : 0);
+  for (int c = 0; ok && c < DCP_NUM_CLASSES; ++c) ok = create_branch(x->cost_set.cls_branch[c], c >= prio_from ? prio_high : 0);
   for (int s = 0; ok && s < DCP_NUM_PACK_SHAPES; ++s) ok = create_branch(x->pack_branch[s], 0);
   for (int c = 4; ok && c <= 6; ++c) ok = create_branch(x->narrow_branch[c], 0);
   // The path pass: streams of its own, alternately of high and of normal priority.  The runtime feeds four hardware
@@ -262,11 +238,12 @@ struct dcp_hip *dcp_hip_new(int device)
   ok = ok && hipEventCreateWithFlags(&x->path_set.fork_ev, hipEventDisableTiming) == hipSuccess;
   for (int c = 0; ok && c < DCP_NUM_CLASSES; ++c) ok = create_branch(x->path_set.cls_branch[c], c % 2 ? prio_high : 0);
   ok = ok && hipStreamCreateWithFlags(&x->upload_stream, hipStreamNonBlocking) == hipSuccess;
-  for (int b = 0; ok && b < 3; ++b)
+  for (Batch &b : x->batch)
   {
-    if (b < 2) ok = ok && hipEventCreateWithFlags(&x->bank[b].done_ev, hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&x->bank[b].up_ev, hipEventDisableTiming) == hipSuccess;
+    ok = ok && hipEventCreateWithFlags(&b.done_ev, hipEventDisableTiming) == hipSuccess;
+    ok = ok && hipEventCreateWithFlags(&b.up_ev, hipEventDisableTiming) == hipSuccess;
   }
+  ok = ok && hipEventCreateWithFlags(&x->path_lists.up_ev, hipEventDisableTiming) == hipSuccess;
   if (!ok)
   {
     dcp_hip_del(x);
@@ -284,7 +261,7 @@ void dcp_hip_del(struct dcp_hip *x)
   (void)hipDeviceSynchronize(); // batches begun and never ended included
   for (int c = 0; c < DCP_NUM_CLASSES; ++c)
   {
-    destroy_branch(x->cls_branch[c]);
+    destroy_branch(x->cost_set.cls_branch[c]);
     destroy_branch(x->narrow_branch[c]);
     destroy_branch(x->path_set.cls_branch[c]);
   }
@@ -292,13 +269,14 @@ void dcp_hip_del(struct dcp_hip *x)
   if (x->path_set.stream) (void)hipStreamDestroy(x->path_set.stream);
   if (x->path_set.fork_ev) (void)hipEventDestroy(x->path_set.fork_ev);
   if (x->upload_stream) (void)hipStreamDestroy(x->upload_stream);
-  for (int b = 0; b < 3; ++b)
+  for (Batch &b : x->batch)
   {
-    if (x->bank[b].done_ev) (void)hipEventDestroy(x->bank[b].done_ev);
-    if (x->bank[b].up_ev) (void)hipEventDestroy(x->bank[b].up_ev);
+    if (b.done_ev) (void)hipEventDestroy(b.done_ev);
+    if (b.up_ev) (void)hipEventDestroy(b.up_ev);
   }
-  if (x->fork_ev) (void)hipEventDestroy(x->fork_ev);
-  if (x->stream) (void)hipStreamDestroy(x->stream);
+  if (x->path_lists.up_ev) (void)hipEventDestroy(x->path_lists.up_ev);
+  if (x->cost_set.fork_ev) (void)hipEventDestroy(x->cost_set.fork_ev);
+  if (x->cost_set.stream) (void)hipStreamDestroy(x->cost_set.stream);
   delete x;
 }
 
@@ -347,23 +325,23 @@ int dcp_hip_set_sequences_strands(struct dcp_hip *x, int nseq, uint8_t const *nt
   ++x->gen;
   x->seq_off = std::move(seq_off);
   x->row_off = std::move(row_off);
-  HIP_TRY(x, hipStreamSynchronize(x->stream), DCP_EFUNCUSE);
+  HIP_TRY(x, hipStreamSynchronize(x->cost_set.stream), DCP_EFUNCUSE);
   HIP_TRY(x, x->d_nt.reserve((size_t)std::max<int64_t>(total, 1)), DCP_ENOMEM);
   HIP_TRY(x, x->d_seq_off.reserve((size_t)nseq + 1), DCP_ENOMEM);
   HIP_TRY(x, x->d_row_off.reserve((size_t)nint + 1), DCP_ENOMEM);
   HIP_TRY(x, x->d_rows.reserve((size_t)std::max<int64_t>(rows, 1)), DCP_ENOMEM);
   if (total)
-    HIP_TRY(x, hipMemcpyAsync(x->d_nt.p, nt, (size_t)total, hipMemcpyHostToDevice, x->stream), DCP_EFUNCUSE);
+    HIP_TRY(x, hipMemcpyAsync(x->d_nt.p, nt, (size_t)total, hipMemcpyHostToDevice, x->cost_set.stream), DCP_EFUNCUSE);
   // (the caller's offsets: on one strand they are x->seq_off; the call waits for the copy before it returns)
-  HIP_TRY(x, hipMemcpyAsync(x->d_seq_off.p, offsets, ((size_t)nseq + 1) * sizeof(int64_t), hipMemcpyHostToDevice, x->stream),
+  HIP_TRY(x, hipMemcpyAsync(x->d_seq_off.p, offsets, ((size_t)nseq + 1) * sizeof(int64_t), hipMemcpyHostToDevice, x->cost_set.stream),
           DCP_EFUNCUSE);
   HIP_TRY(x, hipMemcpyAsync(x->d_row_off.p, x->row_off.data(), ((size_t)nint + 1) * sizeof(int64_t),
-                            hipMemcpyHostToDevice, x->stream),
+                            hipMemcpyHostToDevice, x->cost_set.stream),
           DCP_EFUNCUSE);
   HIP_TRY(x, (both ? dcp_launch_encode_strands : dcp_launch_encode)(x->d_nt.p, x->d_seq_off.p, x->d_row_off.p, nseq, max_len,
-                                                                    x->d_rows.p, x->stream),
+                                                                    x->d_rows.p, x->cost_set.stream),
           DCP_EFUNCUSE);
-  HIP_TRY(x, hipStreamSynchronize(x->stream), DCP_EFUNCUSE);
+  HIP_TRY(x, hipStreamSynchronize(x->cost_set.stream), DCP_EFUNCUSE);
   return 0;
 }
 

@@ -4,13 +4,13 @@
 namespace
 {
 
-// (null, alt) of the n windows of the current bank's d_out, behind everything x->stream has been given
-int fetch_costs(dcp_hip *x, size_t n, float *null_cost, float *alt_cost)
+// (null, alt) of the n windows of the pass's d_out, behind everything its stream has been given
+int fetch_costs(Pass const &ps, size_t n, float *null_cost, float *alt_cost)
 {
   std::vector<float> out(2 * n);
-  HIP_TRY(x, hipMemcpyAsync(out.data(), BK(x).d_out.p, out.size() * sizeof(float), hipMemcpyDeviceToHost, x->stream),
+  HIP_TRY(ps.x, hipMemcpyAsync(out.data(), ps.lists.d_out.p, out.size() * sizeof(float), hipMemcpyDeviceToHost, ps.on.stream),
           DCP_EFUNCUSE);
-  HIP_TRY(x, hipStreamSynchronize(x->stream), DCP_EFUNCUSE);
+  HIP_TRY(ps.x, hipStreamSynchronize(ps.on.stream), DCP_EFUNCUSE);
   for (size_t i = 0; i < n; ++i)
   {
     null_cost[i] = out[2 * i];
@@ -19,7 +19,7 @@ int fetch_costs(dcp_hip *x, size_t n, float *null_cost, float *alt_cost)
   return 0;
 }
 
-// device time of what x->stream is given between start() and stop(); the events go with the object, whichever way
+// device time of what the pass's stream is given between start() and stop(); the events go with the object, whichever way
 // the function that holds it is left
 struct EventTimer
 {
@@ -32,18 +32,18 @@ struct EventTimer
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
   }
-  int start(dcp_hip *x)
+  int start(Pass const &ps)
   {
-    HIP_TRY(x, hipEventCreate(&e0), DCP_EFUNCUSE);
-    HIP_TRY(x, hipEventCreate(&e1), DCP_EFUNCUSE);
-    HIP_TRY(x, hipEventRecord(e0, x->stream), DCP_EFUNCUSE);
+    HIP_TRY(ps.x, hipEventCreate(&e0), DCP_EFUNCUSE);
+    HIP_TRY(ps.x, hipEventCreate(&e1), DCP_EFUNCUSE);
+    HIP_TRY(ps.x, hipEventRecord(e0, ps.on.stream), DCP_EFUNCUSE);
     return 0;
   }
-  int stop(dcp_hip *x, float &total) // ms
+  int stop(Pass const &ps, float &total) // ms
   {
-    HIP_TRY(x, hipEventRecord(e1, x->stream), DCP_EFUNCUSE);
-    HIP_TRY(x, hipEventSynchronize(e1), DCP_EFUNCUSE);
-    HIP_TRY(x, hipEventElapsedTime(&total, e0, e1), DCP_EFUNCUSE);
+    HIP_TRY(ps.x, hipEventRecord(e1, ps.on.stream), DCP_EFUNCUSE);
+    HIP_TRY(ps.x, hipEventSynchronize(e1), DCP_EFUNCUSE);
+    HIP_TRY(ps.x, hipEventElapsedTime(&total, e0, e1), DCP_EFUNCUSE);
     return 0;
   }
 };
@@ -70,16 +70,17 @@ int dcp_hip_cost(struct dcp_hip *x, int n, struct dcp_hip_window const *w, float
   if (!x || (n > 0 && (!null_cost || !alt_cost))) return DCP_EFUNCUSE;
   if (outstanding_batches(x)) return refuse_outstanding(x);
   HIP_TRY(x, hipSetDevice(x->device), DCP_EFUNCUSE);
-  Stopwatch sw(x->stream, worth_timing(n));
+  Pass const ps = cost_pass(x);
+  Stopwatch sw(ps.on.stream, worth_timing(n));
   Staged st;
-  int rc = stage(x, n, w, ARENA_NONE, st);
+  int rc = stage(ps, n, w, ARENA_NONE, st);
   if (rc) return rc;
   if (n == 0) return 0;
-  HIP_TRY(x, BK(x).d_out.reserve(2 * (size_t)n), DCP_ENOMEM);
+  HIP_TRY(x, ps.lists.d_out.reserve(2 * (size_t)n), DCP_ENOMEM);
   double const stage_ms = sw.lap();
-  if ((rc = launch_cost_all(x, st))) return rc;
+  if ((rc = launch_cost_all(ps, st))) return rc;
   double const kernels_ms = sw.lap();
-  if ((rc = fetch_costs(x, (size_t)n, null_cost, alt_cost))) return rc;
+  if ((rc = fetch_costs(ps, (size_t)n, null_cost, alt_cost))) return rc;
   if (sw.on)
     fprintf(stderr, "dcp_hip_cost: %d windows; stage %.1f ms, kernels %.1f ms, fetch %.1f ms\n", n, stage_ms, kernels_ms,
             sw.lap());
@@ -91,19 +92,14 @@ int dcp_hip_cost_hits_begin(struct dcp_hip *x, int n, struct dcp_hip_window cons
   if (!x) return DCP_EFUNCUSE;
   if (x->outstanding[1] >= 0) return fail(x, DCP_EFUNCUSE, "two batches are outstanding already: call dcp_hip_cost_hits_end first");
   HIP_TRY(x, hipSetDevice(x->device), DCP_EFUNCUSE);
-  int const bank = x->outstanding[0] == 0 ? 1 : 0; // the one the batch in flight (if any) does not use
-  x->cur = bank;
-  struct Restore
-  {
-    dcp_hip *x;
-    ~Restore() { x->cur = 0; }
-  } restore{x};
-  dcp_hip::Bank &B = x->bank[bank];
+  int const b = x->outstanding[0] == 0 ? 1 : 0; // the one the batch in flight (if any) does not use
+  Batch &B = x->batch[b];
+  Pass const ps = cost_pass(x, b);
   Staged st;
   // the lists go up on a stream of their own and the kernels fork from there: a batch begun while another is in
   // flight is ordered behind it only kernel class by kernel class (the class streams), not as a whole
   Stopwatch sw(nullptr, worth_timing(n)); // host time: nothing here waits for the device
-  int rc = stage(x, n, w, ARENA_NONE, st, x->upload_stream);
+  int rc = stage(ps, n, w, ARENA_NONE, st, x->upload_stream);
   if (rc) return rc;
   double const stage_ms = sw.lap();
   if (n > 0)
@@ -112,15 +108,15 @@ int dcp_hip_cost_hits_begin(struct dcp_hip *x, int n, struct dcp_hip_window cons
     HIP_TRY(x, B.d_hits.reserve(1 + 2 * (size_t)n), DCP_ENOMEM);
     HIP_TRY(x, B.h_hits.reserve(1 + 2 * (size_t)n), DCP_ENOMEM);
     HIP_TRY(x, hipMemsetAsync(B.d_hits.p, 0, sizeof(uint32_t), x->upload_stream), DCP_EFUNCUSE);
-    if ((rc = launch_cost_all(x, st, x->upload_stream))) return rc;
-    HIP_TRY(x, dcp_launch_lrt_filter(B.d_out.p, n, B.d_hits.p, x->stream), DCP_EFUNCUSE);
+    if ((rc = launch_cost_all(ps, st, x->upload_stream))) return rc;
+    HIP_TRY(x, dcp_launch_lrt_filter(B.d_out.p, n, B.d_hits.p, ps.on.stream), DCP_EFUNCUSE);
     // count and list together (8 B per window at most: nothing beside the kernels), into pinned memory
-    HIP_TRY(x, hipMemcpyAsync(B.h_hits.p, B.d_hits.p, (1 + 2 * (size_t)n) * sizeof(uint32_t), hipMemcpyDeviceToHost, x->stream),
+    HIP_TRY(x, hipMemcpyAsync(B.h_hits.p, B.d_hits.p, (1 + 2 * (size_t)n) * sizeof(uint32_t), hipMemcpyDeviceToHost, ps.on.stream),
             DCP_EFUNCUSE);
-    HIP_TRY(x, hipEventRecord(B.done_ev, x->stream), DCP_EFUNCUSE);
+    HIP_TRY(x, hipEventRecord(B.done_ev, ps.on.stream), DCP_EFUNCUSE);
   }
   B.n = n;
-  x->outstanding[x->outstanding[0] >= 0 ? 1 : 0] = bank;
+  x->outstanding[x->outstanding[0] >= 0 ? 1 : 0] = b;
   if (sw.on) fprintf(stderr, "dcp_hip_cost_hits_begin: %d windows; stage %.1f ms, enqueue %.1f ms\n", n, stage_ms, sw.lap());
   return 0;
 }
@@ -128,9 +124,9 @@ int dcp_hip_cost_hits_begin(struct dcp_hip *x, int n, struct dcp_hip_window cons
 int dcp_hip_cost_hits_end(struct dcp_hip *x, int *nhits, int32_t *hit_window, float *hit_lrt)
 {
   if (!x || !nhits) return DCP_EFUNCUSE;
-  int const bank = x->outstanding[0];
-  if (bank < 0) return fail(x, DCP_EFUNCUSE, "dcp_hip_cost_hits_end without dcp_hip_cost_hits_begin");
-  dcp_hip::Bank &B = x->bank[bank];
+  int const b = x->outstanding[0];
+  if (b < 0) return fail(x, DCP_EFUNCUSE, "dcp_hip_cost_hits_end without dcp_hip_cost_hits_begin");
+  Batch &B = x->batch[b];
   int const n = B.n;
   *nhits = 0;
   HIP_TRY(x, hipSetDevice(x->device), DCP_EFUNCUSE);
@@ -177,21 +173,22 @@ int dcp_hip_cost_bench(struct dcp_hip *x, int n, struct dcp_hip_window const *w,
   if (!x || n <= 0 || reps <= 0 || !ms || !cells) return DCP_EFUNCUSE;
   if (outstanding_batches(x)) return refuse_outstanding(x);
   HIP_TRY(x, hipSetDevice(x->device), DCP_EFUNCUSE);
+  Pass const ps = cost_pass(x);
   Staged st;
-  int rc = stage(x, n, w, ARENA_NONE, st);
+  int rc = stage(ps, n, w, ARENA_NONE, st);
   if (rc) return rc;
-  HIP_TRY(x, BK(x).d_out.reserve(2 * (size_t)n), DCP_ENOMEM);
+  HIP_TRY(x, ps.lists.d_out.reserve(2 * (size_t)n), DCP_ENOMEM);
   for (int i = 0; i < warmup; ++i)
-    if ((rc = launch_cost_all(x, st))) return rc;
+    if ((rc = launch_cost_all(ps, st))) return rc;
   EventTimer timer;
-  if ((rc = timer.start(x))) return rc;
+  if ((rc = timer.start(ps))) return rc;
   for (int i = 0; i < reps; ++i)
-    if ((rc = launch_cost_all(x, st))) return rc;
+    if ((rc = launch_cost_all(ps, st))) return rc;
   float total = 0;
-  if ((rc = timer.stop(x, total))) return rc;
+  if ((rc = timer.stop(ps, total))) return rc;
   *ms = total / (float)reps;
   *cells = st.cells;
-  return null_cost && alt_cost ? fetch_costs(x, (size_t)n, null_cost, alt_cost) : 0;
+  return null_cost && alt_cost ? fetch_costs(ps, (size_t)n, null_cost, alt_cost) : 0;
 }
 
 int dcp_hip_stage(struct dcp_hip *x, int n, struct dcp_hip_window const *w)
@@ -201,11 +198,12 @@ int dcp_hip_stage(struct dcp_hip *x, int n, struct dcp_hip_window const *w)
   x->staged_n = -1; // a failed stage leaves no list behind
   if (n <= 0) return fail(x, DCP_EFUNCUSE, "dcp_hip_stage needs at least one window");
   HIP_TRY(x, hipSetDevice(x->device), DCP_EFUNCUSE);
+  Pass const ps = cost_pass(x);
   Staged st;
-  int rc = stage(x, n, w, ARENA_NONE, st);
+  int rc = stage(ps, n, w, ARENA_NONE, st);
   if (rc) return rc;
-  HIP_TRY(x, BK(x).d_out.reserve(2 * (size_t)n), DCP_ENOMEM);
-  HIP_TRY(x, hipStreamSynchronize(x->stream), DCP_EFUNCUSE);
+  HIP_TRY(x, ps.lists.d_out.reserve(2 * (size_t)n), DCP_ENOMEM);
+  HIP_TRY(x, hipStreamSynchronize(ps.on.stream), DCP_EFUNCUSE);
   x->staged = st;
   x->staged_n = n;
   x->staged_ran = false;
@@ -219,20 +217,14 @@ int dcp_hip_run_staged(struct dcp_hip *x, int reps, float *ms, double *cells)
   int rc = check_staged(x);
   if (rc) return rc;
   HIP_TRY(x, hipSetDevice(x->device), DCP_EFUNCUSE);
+  Pass const ps = cost_pass(x);
   StagedPlan const &st = x->staged;
   EventTimer timer;
-  if ((rc = timer.start(x))) return rc;
-  // every pass joined before the next starts.  DECIPHON_HIP_STEP_JOIN=0 (experiment): the passes follow each other as
-  // the batches of a scan do (dcp_hip_cost_hits_begin while another batch is in flight), kernel class by kernel class --
-  // measured no faster on the bench's 0.4 s steps (profiles/r03_scan_pipeline.txt)
-  char const *join_env = getenv("DECIPHON_HIP_STEP_JOIN");
-  if (join_env && join_env[0] == '0' && reps > 0)
-    rc = launch_cost_all(x, st, nullptr, reps);
-  else
-    for (int i = 0; i < reps && !rc; ++i) rc = launch_cost_all(x, st);
+  if ((rc = timer.start(ps))) return rc;
+  for (int i = 0; i < reps && !rc; ++i) rc = launch_cost_all(ps, st); // every pass joined before the next starts
   if (rc) return rc;
   float total = 0;
-  if ((rc = timer.stop(x, total))) return rc;
+  if ((rc = timer.stop(ps, total))) return rc;
   if (ms) *ms = total;
   if (cells) *cells = st.cells;
   if (reps > 0) x->staged_ran = true;
@@ -245,7 +237,7 @@ int dcp_hip_fetch_staged(struct dcp_hip *x, float *null_cost, float *alt_cost)
   int rc = check_staged(x);
   if (rc) return rc;
   if (!x->staged_ran) return fail(x, DCP_EFUNCUSE, "dcp_hip_run_staged has not run the staged list yet");
-  return fetch_costs(x, (size_t)x->staged_n, null_cost, alt_cost);
+  return fetch_costs(cost_pass(x), (size_t)x->staged_n, null_cost, alt_cost);
 }
 
 } // extern "C"

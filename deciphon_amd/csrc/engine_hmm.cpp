@@ -65,7 +65,7 @@ struct HmmLoad
   StreamDrain drain; // (the last member: the stream is idle before the slots' buffers go)
   HmmLoad(dcp_hip *x_, int gencode_id, float eps)
       : x(x_), gencode(gencode_id), epsilon(eps), used(x_->pool_used), dist_used(x_->dist_used),
-        models_at(x_->dist_models_used), drain{x_->stream}
+        models_at(x_->dist_models_used), drain{x_->cost_set.stream}
   {
   }
 
@@ -78,9 +78,9 @@ struct HmmLoad
     float *d_models = x->d_dist_models.p + models_at * DCP_PRESS_IN_STRIDE;
     dcp_press_put_entry(h_models.p, reader.null_dist());
     dcp_press_put_entry(h_models.p + DCP_PRESS_IN_STRIDE, reader.bg_dist());
-    HIP_TRY(x, hipMemcpyAsync(d_models, h_models.p, 2 * DCP_PRESS_IN_STRIDE * sizeof(float), hipMemcpyHostToDevice, x->stream),
+    HIP_TRY(x, hipMemcpyAsync(d_models, h_models.p, 2 * DCP_PRESS_IN_STRIDE * sizeof(float), hipMemcpyHostToDevice, x->cost_set.stream),
             DCP_EFUNCUSE);
-    if (dcp_press_emission_launch(d_models, d_nullbg.p, 2, epsilon, x->stream))
+    if (dcp_press_emission_launch(d_models, d_nullbg.p, 2, epsilon, x->cost_set.stream))
       return fail(x, DCP_EFUNCUSE, "the emission kernel could not be launched");
     for (HmmSlot &s : slot)
       for (Event &e : s.ev) HIP_TRY(x, e.create(), DCP_ENOMEM);
@@ -168,7 +168,7 @@ struct HmmLoad
   {
     size_t const n = s.profiles.size(), entries = (size_t)s.entries;
     float *const d_in = x->d_dist.p + dist_used * DCP_PRESS_IN_STRIDE;
-    hipStream_t const q = x->stream;
+    hipStream_t const q = x->cost_set.stream;
     HIP_TRY(x, hipEventRecord(s.ev[0].e, q), DCP_EFUNCUSE);
     HIP_TRY(x, hipMemcpyAsync(d_in, s.h_in.p, entries * DCP_PRESS_IN_STRIDE * sizeof(float), hipMemcpyHostToDevice, q), DCP_EFUNCUSE);
     HIP_TRY(x, hipMemcpyAsync(s.d_trans.p, s.h_trans.p, trans_floats * sizeof(float), hipMemcpyHostToDevice, q), DCP_EFUNCUSE);
@@ -302,7 +302,7 @@ struct Reemit
   // queues the kernels of every group on the engine's stream, from the kept distributions as they are by then
   int run()
   {
-    hipStream_t const q = x->stream;
+    hipStream_t const q = x->cost_set.stream;
     size_t const models = x->dist_models_used;
     HIP_TRY(x, hipEventRecord(ker[0].e, q), DCP_EFUNCUSE);
     for (size_t g = 0; g < groups.size(); ++g)
@@ -395,7 +395,7 @@ int dcp_hip_load_hmm_sink(struct dcp_hip *x, char const *hmm, int gencode_id, fl
   for (HmmSlot &s : load.slot)
     if (int const wrc = load.wait(s))
       if (!rc) rc = wrc;
-  if (!rc) HIP_TRY(x, hipStreamSynchronize(x->stream), DCP_EFUNCUSE); // (the null and background tables of an empty range)
+  if (!rc) HIP_TRY(x, hipStreamSynchronize(x->cost_set.stream), DCP_EFUNCUSE); // (the null and background tables of an empty range)
   if (!rc && bad_first) rc = fail(x, DCP_EINVALPART, "first profile out of range");
   if (rc) return rc; // nothing of this load is kept: pool_used and the profiles are what they were
   if (getenv("DECIPHON_HIP_TIMING"))
@@ -457,10 +457,10 @@ int dcp_hip_set_gencode_sink(struct dcp_hip *x, int gencode_id, DcpGencodeSink *
     HIP_TRY(x, up0[b].create(), DCP_ENOMEM);
     HIP_TRY(x, up1[b].create(), DCP_ENOMEM);
   }
-  StreamDrain drain{x->stream}; // (until the stream is idle the pinned buffers stay: an early return below waits for what it queued)
+  StreamDrain drain{x->cost_set.stream}; // (until the stream is idle the pinned buffers stay: an early return below waits for what it queued)
 
   // from here on the kept distributions change
-  hipStream_t const q = x->stream;
+  hipStream_t const q = x->cost_set.stream;
   if (sink) sink->regencoded(gencode_id, null, bg);
   for (size_t m = 0; m + 1 < models; m += 2)
   {
@@ -538,7 +538,7 @@ int dcp_hip_set_epsilon(struct dcp_hip *x, float epsilon)
   Reemit reemit(x, std::move(all));
   if (int rc = reemit.prepare()) return rc;
   if (int rc = reemit.run()) return rc;
-  HIP_TRY(x, hipStreamSynchronize(x->stream), DCP_EFUNCUSE);
+  HIP_TRY(x, hipStreamSynchronize(x->cost_set.stream), DCP_EFUNCUSE);
   if (getenv("DECIPHON_HIP_TIMING"))
   {
     // (the seconds are Reemit's: with the emission kernel over the loads' null models and backgrounds in front)

@@ -274,6 +274,42 @@ struct Branch
   hipEvent_t joined = nullptr;
 };
 
+// The streams a pass runs on: the one its work is ordered on, and one side stream per kernel class, so that the kernels
+// of different classes (few problems each in small scans) share the GPU instead of queueing.  The engine has two sets
+// (dcp_hip::cost_set, path_set).
+struct StreamSet
+{
+  hipStream_t stream = nullptr;
+  hipEvent_t fork_ev = nullptr; // what the branches wait for (struct Fork)
+  Branch cls_branch[DCP_NUM_CLASSES];
+};
+
+// The window lists of a pass and the results of its kernels, on the device; stage() fills the lists.
+struct WindowLists
+{
+  DevBuf<DcpProblem> d_problems;
+  DevBuf<DcpPack> d_packs;         // cost pass: windows of short profiles, several per wavefront
+  DevBuf<PackGroup> d_pack_groups; // ... and, for four-lane groups, the packs of one profile that share a workgroup
+  DevBuf<float> d_out;             // (null, alt) per window
+  DevBuf<float> d_ring;            // strip class (K > 4096): the rings of folded rows, one per workgroup in flight
+  // the lists go up from pinned memory: a copy from PAGEABLE memory waits for everything the device has been given
+  // (the upload of a batch begun while another was in flight took as long as the rest of that batch's cost pass)
+  PinBuf<DcpProblem> h_problems;
+  PinBuf<DcpPack> h_packs;
+  PinBuf<PackGroup> h_groups;
+  hipEvent_t up_ev = nullptr; // recorded behind the uploads: the pinned lists are not rewritten before
+  bool up_pending = false;
+};
+
+// The lists of a cost pass, and what dcp_hip_cost_hits_begin / _end keep of a batch between them
+struct Batch : WindowLists
+{
+  DevBuf<uint32_t> d_hits;      // count, then (window, lrt bits) pairs
+  PinBuf<uint32_t> h_hits;      // ... on the host: the whole list comes back behind the filter
+  hipEvent_t done_ev = nullptr; // recorded behind the batch's last device operation
+  int n = -1;                   // windows of the outstanding batch, -1: none
+};
+
 } // namespace dcp_engine
 
 using namespace dcp_engine; // for the engine's own files only: nothing else includes this
@@ -281,11 +317,9 @@ using namespace dcp_engine; // for the engine's own files only: nothing else inc
 struct dcp_hip
 {
   int device = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t fork_ev = nullptr;
-  // one side stream per kernel class, so that the kernels of different
-  // classes (few problems each in small scans) share the GPU instead of queueing
-  Branch cls_branch[DCP_NUM_CLASSES];
+  // The cost passes' streams (the loads and dcp_hip_set_sequences* work on cost_set.stream too) and the path pass's own,
+  // which may run while cost batches are in flight.  A pass is handed its set (struct Pass).
+  StreamSet cost_set, path_set;
   Branch pack_branch[DCP_NUM_PACK_SHAPES]; // the packed cost kernels, one stream per shape
   Branch narrow_branch[DCP_NUM_CLASSES];   // the narrow cost kernels of classes 4..6
   std::string err;
@@ -322,40 +356,13 @@ struct dcp_hip
   int xt_rows = 0;
   std::vector<float> xt_override; // [rows][DCP_XT_STRIDE], dcp_hip_set_xtrans_table
 
-  // problems / results.  Three sets of window lists and result buffers ("banks"): 0 and 1 for cost passes -- two
-  // batches may be outstanding at once (dcp_hip_cost_hits_begin / _end), the second queued behind the first on the same
-  // kernel streams so that the GPU never drains between them -- and 2 for the path pass, which has its own streams too
-  // (path_set) and may run while cost batches are in flight.  `cur` is the bank the code below works on.
-  struct Bank
-  {
-    DevBuf<DcpProblem> d_problems;
-    DevBuf<DcpPack> d_packs;         // cost pass: windows of short profiles, several per wavefront
-    DevBuf<PackGroup> d_pack_groups;     // ... and, for four-lane groups, the packs of one profile that share a workgroup
-    DevBuf<float> d_out;             // (null, alt) per window
-    DevBuf<uint32_t> d_hits;         // dcp_hip_cost_hits: count, then (window, lrt bits) pairs
-    DevBuf<float> d_ring;            // strip class (K > 4096): the rings of folded rows, one per workgroup in flight
-    PinBuf<uint32_t> h_hits;         // ... on the host: the whole list comes back behind the filter
-    hipEvent_t done_ev = nullptr;    // an outstanding batch: recorded behind its last device operation
-    int n = -1;                      // windows of the outstanding batch, -1: none
-    // the lists go up from pinned memory: a copy from PAGEABLE memory waits for everything the device has been given
-    // (the upload of a batch begun while another was in flight took as long as the rest of that batch's cost pass)
-    PinBuf<DcpProblem> h_problems;
-    PinBuf<DcpPack> h_packs;
-    PinBuf<PackGroup> h_groups;
-    hipEvent_t up_ev = nullptr; // recorded behind the uploads: the pinned lists are not rewritten before
-    bool up_pending = false;
-  };
-  Bank bank[3];
-  int cur = 0;
-  int outstanding[2] = {-1, -1}; // banks of the batches begun and not yet ended, oldest first
+  // problems / results.  Two batches of cost passes may be outstanding at once (dcp_hip_cost_hits_begin / _end), the
+  // second queued behind the first on the same kernel streams so that the GPU never drains between them; every other
+  // cost call works on batch[0].  The path pass has lists of its own.
+  Batch batch[2];
+  WindowLists path_lists;
+  int outstanding[2] = {-1, -1}; // indices into batch[] of those begun and not yet ended, oldest first
   hipStream_t upload_stream = nullptr;
-  // the path pass's own streams and events, swapped with stream / fork_ev / cls_branch for its duration
-  struct StreamSet
-  {
-    hipStream_t stream = nullptr;
-    hipEvent_t fork_ev = nullptr;
-    Branch cls_branch[DCP_NUM_CLASSES];
-  } path_set;
   DevBuf<int64_t> d_aux;           // strip class, literal path pass: table and scratch addresses per window
   DevBuf<int64_t> d_ckpt_addr;     // fast path pass: checkpoint address per window
   DevBuf<DcpTraceState> d_trace;   // fast path pass: where each window's traceback stands between blocks
@@ -380,7 +387,7 @@ struct dcp_hip
   DevBuf<int32_t> d_nsteps;
   std::vector<std::vector<unsigned char>> host_trellis; // fetched on demand, one per window
   std::vector<PathResult> paths;
-  StagedPlan staged; // dcp_hip_stage: the list itself stays in bank 0's device buffers
+  StagedPlan staged; // dcp_hip_stage: the list itself stays in batch[0]'s device buffers
   int staged_n = -1;
   bool staged_ran = false; // a dcp_hip_run_staged with reps > 0 has filled d_out since the dcp_hip_stage
 
@@ -391,8 +398,6 @@ struct dcp_hip
   uint64_t staged_gen = 0;
   uint64_t path_gen = UINT64_MAX; // UINT64_MAX: the last dcp_hip_path failed or there was none
 };
-
-#define BK(x) ((x)->bank[(x)->cur])
 
 namespace dcp_engine
 {
@@ -415,31 +420,43 @@ inline int fail(dcp_hip *x, int rc, char const *what, hipError_t e = hipSuccess)
     if (e_ != hipSuccess) return fail((x), (rc), #call, e_);                   \
   } while (0)
 
-// Kernels that run side by side: each on a branch that waits for fork_ev, recorded on the stream they all come behind;
-// x->stream waits for every branch that was used.  Not forking, everything stays on x->stream and these do nothing.
+// What a pass works on: its window lists and its streams, named by the C entry point that begins it.
+struct Pass
+{
+  dcp_hip *x;
+  WindowLists &lists;
+  StreamSet const &on;
+  Batch *batch; // the cost passes: lists is *batch; nullptr: the path pass
+};
+inline Pass cost_pass(dcp_hip *x, int b = 0) { return Pass{x, x->batch[b], x->cost_set, &x->batch[b]}; }
+inline Pass path_pass(dcp_hip *x) { return Pass{x, x->path_lists, x->path_set, nullptr}; }
+
+// Kernels that run side by side: each on a branch that waits for on.fork_ev, recorded on the stream they all come
+// behind; on.stream waits for every branch that was used.  Not forking, everything stays on on.stream and these do nothing.
 struct Fork
 {
   dcp_hip *x;
-  bool on;
+  StreamSet const &on;
+  bool forking;
   std::vector<hipEvent_t> joins;
-  Fork(dcp_hip *x_, bool on_) : x(x_), on(on_) {}
+  Fork(Pass const &ps, bool forking_) : x(ps.x), on(ps.on), forking(forking_) {}
   int begin(hipStream_t origin)
   {
-    if (on) HIP_TRY(x, hipEventRecord(x->fork_ev, origin), DCP_EFUNCUSE);
+    if (forking) HIP_TRY(x, hipEventRecord(on.fork_ev, origin), DCP_EFUNCUSE);
     return 0;
   }
   // a's launches go to b
   int enter(Branch const &b, DcpLaunch &a)
   {
-    if (!on) return 0;
+    if (!forking) return 0;
     a.stream = b.stream;
-    HIP_TRY(x, hipStreamWaitEvent(a.stream, x->fork_ev, 0), DCP_EFUNCUSE);
+    HIP_TRY(x, hipStreamWaitEvent(a.stream, on.fork_ev, 0), DCP_EFUNCUSE);
     return 0;
   }
   // b has had its last launch
   int leave(Branch const &b)
   {
-    if (!on) return 0;
+    if (!forking) return 0;
     HIP_TRY(x, hipEventRecord(b.joined, b.stream), DCP_EFUNCUSE);
     joins.push_back(b.joined);
     return 0;
@@ -447,7 +464,7 @@ struct Fork
   // after the last launch of all (see launch_cost_all)
   int join()
   {
-    for (hipEvent_t ev : joins) HIP_TRY(x, hipStreamWaitEvent(x->stream, ev, 0), DCP_EFUNCUSE);
+    for (hipEvent_t ev : joins) HIP_TRY(x, hipStreamWaitEvent(on.stream, ev, 0), DCP_EFUNCUSE);
     return 0;
   }
 };
@@ -480,12 +497,11 @@ struct Stopwatch
 };
 
 // Plans the window list (plan_stage, stage_plan.h: the checks, the lists, their order and shares) and brings the lists
-// to the device, into the current bank
-// (origin: the stream the lists are uploaded on -- x->stream unless a batch is begun asynchronously)
-int stage(dcp_hip *x, int n, dcp_hip_window const *w, ArenaKind arena_kind, Staged &st, hipStream_t origin = nullptr);
-DcpLaunch launch_args(dcp_hip *x, StagedPlan const &st, int c);
-int launch_all(dcp_hip *x, StagedPlan const &st, bool path);
-int launch_cost_all(dcp_hip *x, StagedPlan const &st, hipStream_t origin = nullptr, int reps = 1);
+// to the device, into the pass's
+// (origin: the stream the lists are uploaded on -- the pass's own unless a batch is begun asynchronously)
+int stage(Pass const &ps, int n, dcp_hip_window const *w, ArenaKind arena_kind, Staged &st, hipStream_t origin = nullptr);
+DcpLaunch launch_args(Pass const &ps, StagedPlan const &st, int c);
+int launch_cost_all(Pass const &ps, StagedPlan const &st, hipStream_t origin = nullptr);
 
 // batches begun and not ended
 inline int outstanding_batches(dcp_hip const *x) { return (x->outstanding[0] >= 0) + (x->outstanding[1] >= 0); }

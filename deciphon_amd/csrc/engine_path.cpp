@@ -14,35 +14,13 @@ int ckpt_rows()
   return B - B % 5;
 }
 
-// the path pass works on its own bank and streams (see dcp_hip::bank): swapped in for the duration of a call
-struct PathContext
-{
-  dcp_hip *x;
-  int saved_cur;
-  static void swap_streams(dcp_hip *x)
-  {
-    std::swap(x->stream, x->path_set.stream);
-    std::swap(x->fork_ev, x->path_set.fork_ev);
-    std::swap(x->cls_branch, x->path_set.cls_branch);
-  }
-  explicit PathContext(dcp_hip *x_) : x(x_), saved_cur(x_->cur)
-  {
-    swap_streams(x);
-    x->cur = 2;
-  }
-  ~PathContext()
-  {
-    swap_streams(x);
-    x->cur = saved_cur;
-  }
-};
-
 // step buffers: a path has at most L emitting steps; mute steps (S, B, E, T, D runs) are few
 // in practice.  DECIPHON_HIP_UNZIP_CAP (steps) overrides the capacity: a test hook for the
 // overflow fallbacks.
 // step_off (the caller keeps it until the stream has passed the copy) goes to the device with the buffers it describes.
-int stage_steps(dcp_hip *x, Staged const &st, int n, std::vector<int64_t> &step_off)
+int stage_steps(Pass const &ps, Staged const &st, int n, std::vector<int64_t> &step_off)
 {
+  dcp_hip *const x = ps.x;
   int64_t cap_override = 0;
   if (char const *e = getenv("DECIPHON_HIP_UNZIP_CAP")) cap_override = atoll(e);
   step_off.assign((size_t)n + 1, 0);
@@ -54,7 +32,7 @@ int stage_steps(dcp_hip *x, Staged const &st, int n, std::vector<int64_t> &step_
   HIP_TRY(x, x->d_step_off.reserve((size_t)n + 1), DCP_ENOMEM);
   HIP_TRY(x, x->d_nsteps.reserve((size_t)n), DCP_ENOMEM);
   HIP_TRY(x, hipMemcpyAsync(x->d_step_off.p, step_off.data(), ((size_t)n + 1) * sizeof(int64_t),
-                            hipMemcpyHostToDevice, x->stream),
+                            hipMemcpyHostToDevice, ps.on.stream),
           DCP_EFUNCUSE);
   return 0;
 }
@@ -70,15 +48,16 @@ struct PathFetched
 };
 
 // Brings the scores, the step counts and then only the steps actually written to the host.
-int fetch_results(dcp_hip *x, int n, size_t nout, PathFetched &f)
+int fetch_results(Pass const &ps, int n, size_t nout, PathFetched &f)
 {
+  dcp_hip *const x = ps.x;
   HIP_TRY(x, x->h_out.reserve(nout), DCP_ENOMEM);
-  HIP_TRY(x, hipMemcpyAsync(x->h_out.p, BK(x).d_out.p, nout * sizeof(float), hipMemcpyDeviceToHost, x->stream), DCP_EFUNCUSE);
+  HIP_TRY(x, hipMemcpyAsync(x->h_out.p, ps.lists.d_out.p, nout * sizeof(float), hipMemcpyDeviceToHost, ps.on.stream), DCP_EFUNCUSE);
   f.out = x->h_out.p;
   HIP_TRY(x, x->h_nsteps.reserve((size_t)std::max(n, 1)), DCP_ENOMEM);
-  HIP_TRY(x, hipMemcpyAsync(x->h_nsteps.p, x->d_nsteps.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, x->stream),
+  HIP_TRY(x, hipMemcpyAsync(x->h_nsteps.p, x->d_nsteps.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ps.on.stream),
           DCP_EFUNCUSE);
-  HIP_TRY(x, hipStreamSynchronize(x->stream), DCP_EFUNCUSE);
+  HIP_TRY(x, hipStreamSynchronize(ps.on.stream), DCP_EFUNCUSE);
   int32_t const *const nsteps = f.nsteps = x->h_nsteps.p;
   std::vector<int64_t> &compact = f.compact;
   compact.assign((size_t)n + 1, 0);
@@ -92,29 +71,60 @@ int fetch_results(dcp_hip *x, int n, size_t nout, PathFetched &f)
   PinBuf<uint32_t> &h_steps = x->h_steps[x->h_steps_used++];
   HIP_TRY(x, h_steps.reserve(total), DCP_ENOMEM);
   HIP_TRY(x, hipMemcpyAsync(x->d_compact_off.p, compact.data(), ((size_t)n + 1) * sizeof(int64_t), hipMemcpyHostToDevice,
-                            x->stream),
+                            ps.on.stream),
           DCP_EFUNCUSE);
-  HIP_TRY(x, dcp_launch_compact_steps(x->d_steps.p, x->d_step_off.p, x->d_compact_off.p, x->d_compact.p, n, x->stream),
+  HIP_TRY(x, dcp_launch_compact_steps(x->d_steps.p, x->d_step_off.p, x->d_compact_off.p, x->d_compact.p, n, ps.on.stream),
           DCP_EFUNCUSE);
-  HIP_TRY(x, hipMemcpyAsync(h_steps.p, x->d_compact.p, total * sizeof(uint32_t), hipMemcpyDeviceToHost, x->stream),
+  HIP_TRY(x, hipMemcpyAsync(h_steps.p, x->d_compact.p, total * sizeof(uint32_t), hipMemcpyDeviceToHost, ps.on.stream),
           DCP_EFUNCUSE);
-  HIP_TRY(x, hipStreamSynchronize(x->stream), DCP_EFUNCUSE);
+  HIP_TRY(x, hipStreamSynchronize(ps.on.stream), DCP_EFUNCUSE);
   f.steps = h_steps.p;
   return 0;
 }
 
-int fetch_trellis(dcp_hip *x, int i)
+int fetch_trellis(Pass const &ps, int i)
 {
+  dcp_hip *const x = ps.x;
   PathResult &r = x->paths[(size_t)i];
   if (r.trellis_on_host) return 0;
   std::vector<unsigned char> &buf = x->host_trellis[(size_t)i];
   size_t const bytes = trellis_bytes(r.L, r.K);
   buf.resize(bytes);
-  HIP_TRY(x, hipMemcpyAsync(buf.data(), x->d_trellis.p + r.trellis_off, bytes, hipMemcpyDeviceToHost, x->stream),
+  HIP_TRY(x, hipMemcpyAsync(buf.data(), x->d_trellis.p + r.trellis_off, bytes, hipMemcpyDeviceToHost, ps.on.stream),
           DCP_EFUNCUSE);
-  HIP_TRY(x, hipStreamSynchronize(x->stream), DCP_EFUNCUSE);
+  HIP_TRY(x, hipStreamSynchronize(ps.on.stream), DCP_EFUNCUSE);
   r.trellis_on_host = true;
   return 0;
+}
+
+// The kernels of every class of a staged list but `skip`: the classes of a slice are each too small to fill the GPU and
+// each lasts as long as its longest window, so they go out on their own streams, forked from and joined back into the
+// pass's.  launch(c, a) queues class c's on a.stream.
+template <class Launch> int each_class(Pass const &ps, StagedPlan const &st, int skip, Launch launch)
+{
+  int classes = 0;
+  for (int c = 0; c < DCP_NUM_CLASSES; ++c) classes += st.c_begin[c + 1] > st.c_begin[c];
+  Fork fk(ps, classes > 1);
+  int rc = fk.begin(ps.on.stream);
+  if (rc) return rc;
+  for (int c = 0; c < DCP_NUM_CLASSES; ++c)
+  {
+    DcpLaunch a = launch_args(ps, st, c);
+    if (a.nprob <= 0 || c == skip) continue;
+    if ((rc = fk.enter(ps.on.cls_branch[c], a))) return rc;
+    if ((rc = launch(c, a))) return rc;
+    if ((rc = fk.leave(ps.on.cls_branch[c]))) return rc;
+  }
+  return fk.join();
+}
+
+// The literal pass's path kernels; the strip class is replayed from the DP table instead (literal_strips)
+int launch_all(Pass const &ps, StagedPlan const &st)
+{
+  return each_class(ps, st, DCP_STRIP_CLASS, [&](int c, DcpLaunch const &a) {
+    HIP_TRY(ps.x, dcp_launch_path(c, a), DCP_EFUNCUSE);
+    return 0;
+  });
 }
 
 // HBM the fast pass fills with DP tables.  A slice takes as long as its longest window however
@@ -174,9 +184,10 @@ size_t place_slice(dcp_hip *x, DcpPathPlan const &plan, size_t b, size_t budget)
 // budget; where they do not -- and the budget is not strict -- the table comes a block at a time from checkpoints, G
 // blocks side by side, and a block serves the rows of the traceback's partition (dcp_types.h): DCP_PATH_LITERAL.
 // count_blocked: the windows taken in blocks go into x->path_blocked (a dcp_hip_path whose fast pass was skipped).
-int literal_strips(dcp_hip *x, std::vector<dcp_hip_window> const &w, std::vector<int> const &sl,
+int literal_strips(Pass const &ps, std::vector<dcp_hip_window> const &w, std::vector<int> const &sl,
                    std::vector<size_t> const &trel_off, bool count_blocked)
 {
+  dcp_hip *const x = ps.x;
   int const n = (int)w.size();
   size_t const budget = path_budget(x);
   std::vector<dcp_hip_window> strips;
@@ -195,7 +206,7 @@ int literal_strips(dcp_hip *x, std::vector<dcp_hip_window> const &w, std::vector
     if (se == sb) return fail(x, DCP_ENOMEM, "no device memory for the DP table of a long profile's path pass");
     int const ns = (int)(se - sb);
     Staged ss;
-    int rc = stage(x, ns, strips.data() + sb, ARENA_TABLE, ss);
+    int rc = stage(ps, ns, strips.data() + sb, ARENA_TABLE, ss);
     if (rc) return rc;
     std::vector<int64_t> aux(4 * (size_t)ns); // [4][windows of the slice]: trellis, scratch, checkpoints, score slot
     int max_rows = 0, max_blocks = 0;
@@ -210,9 +221,9 @@ int literal_strips(dcp_hip *x, std::vector<dcp_hip_window> const &w, std::vector
       max_rows = std::max(max_rows, p.replay_rows);
       if (p.in_blocks) max_blocks = std::max(max_blocks, p.blocks);
     }
-    HIP_TRY(x, hipMemcpyAsync(x->d_aux.p, aux.data(), aux.size() * sizeof(int64_t), hipMemcpyHostToDevice, x->stream),
+    HIP_TRY(x, hipMemcpyAsync(x->d_aux.p, aux.data(), aux.size() * sizeof(int64_t), hipMemcpyHostToDevice, ps.on.stream),
             DCP_EFUNCUSE);
-    DcpLaunch a = launch_args(x, ss, DCP_STRIP_CLASS);
+    DcpLaunch a = launch_args(ps, ss, DCP_STRIP_CLASS);
     a.arena = nullptr;
     // (null, alt) of the slice's windows go behind the n scores of the pass
     DcpLaunch store = a;
@@ -226,7 +237,7 @@ int literal_strips(dcp_hip *x, std::vector<dcp_hip_window> const &w, std::vector
       HIP_TRY(x, dcp_launch_strip_store(store, d_ckpt, B, G, it), DCP_EFUNCUSE);
       HIP_TRY(x, dcp_launch_replay(a, x->d_aux.p, B, G, it, max_rows), DCP_EFUNCUSE);
     }
-    HIP_TRY(x, hipStreamSynchronize(x->stream), DCP_EFUNCUSE); // aux is read by the copy above; the next slice reuses the tables
+    HIP_TRY(x, hipStreamSynchronize(ps.on.stream), DCP_EFUNCUSE); // aux is read by the copy above; the next slice reuses the tables
     sb = se;
   }
   return 0;
@@ -234,8 +245,9 @@ int literal_strips(dcp_hip *x, std::vector<dcp_hip_window> const &w, std::vector
 
 // The literal path pass (viterbi_path as the reference runs it, pass by pass, with the
 // trellis in HBM) + trellis_unzip on the device, for the windows path_wins[idx[..]].
-int path_literal(dcp_hip *x, std::vector<int> const &idx, bool count_blocked = false)
+int path_literal(Pass const &ps, std::vector<int> const &idx, bool count_blocked = false)
 {
+  dcp_hip *const x = ps.x;
   int const n = (int)idx.size();
   if (n == 0) return 0;
   std::vector<dcp_hip_window> w((size_t)n);
@@ -245,25 +257,25 @@ int path_literal(dcp_hip *x, std::vector<int> const &idx, bool count_blocked = f
   std::vector<int> sl; // the windows of the strip class
   for (int j = 0; j < n; ++j)
     if (x->profiles[(size_t)w[(size_t)j].profile].cls == DCP_STRIP_CLASS) sl.push_back(j);
-  HIP_TRY(x, BK(x).d_out.reserve(3 * (size_t)n), DCP_ENOMEM);
+  HIP_TRY(x, ps.lists.d_out.reserve(3 * (size_t)n), DCP_ENOMEM);
   HIP_TRY(x, x->d_trellis.reserve(trel_off[(size_t)n]), DCP_ENOMEM);
   int rc = 0;
   // the strip class first: the problem list below replaces its lists on the device
-  if (!sl.empty() && (rc = literal_strips(x, w, sl, trel_off, count_blocked))) return rc;
+  if (!sl.empty() && (rc = literal_strips(ps, w, sl, trel_off, count_blocked))) return rc;
   Staged st;
-  if ((rc = stage(x, n, w.data(), ARENA_TRELLIS, st))) return rc;
-  if ((rc = launch_all(x, st, true))) return rc; // (not the strip class)
+  if ((rc = stage(ps, n, w.data(), ARENA_TRELLIS, st))) return rc;
+  if ((rc = launch_all(ps, st))) return rc; // (not the strip class)
 
   std::vector<int64_t> step_off;
-  if ((rc = stage_steps(x, st, n, step_off))) return rc;
+  if ((rc = stage_steps(ps, st, n, step_off))) return rc;
   {
-    DcpLaunch a = launch_args(x, st, 0);
-    a.problems = BK(x).d_problems.p;
+    DcpLaunch a = launch_args(ps, st, 0);
+    a.problems = ps.lists.d_problems.p;
     a.nprob = n;
     HIP_TRY(x, dcp_launch_unzip(a, x->d_steps.p, x->d_step_off.p, x->d_nsteps.p), DCP_EFUNCUSE);
   }
   PathFetched f;
-  if ((rc = fetch_results(x, n, (size_t)n, f))) return rc;
+  if ((rc = fetch_results(ps, n, (size_t)n, f))) return rc;
   // every earlier trellis offset pointed into the arena that was just rewritten
   for (PathResult &r : x->paths) r.has_trellis = r.trellis_on_host = false;
   for (DcpProblem const &p : st.problems)
@@ -291,7 +303,7 @@ int path_literal(dcp_hip *x, std::vector<int> const &idx, bool count_blocked = f
     else
     {
       // the device buffer was too small for this path: fetch the trellis and unzip here
-      if ((rc = fetch_trellis(x, i))) return rc;
+      if ((rc = fetch_trellis(ps, i))) return rc;
       uint32_t const *xn = reinterpret_cast<uint32_t const *>(x->host_trellis[(size_t)i].data());
       uint16_t const *nd = reinterpret_cast<uint16_t const *>(xn + (r.L + 1));
       std::vector<int32_t> ids, sizes;
@@ -310,19 +322,20 @@ int path_literal(dcp_hip *x, std::vector<int> const &idx, bool count_blocked = f
 // traceback meets an exact tie the values alone cannot resolve come back in `redo`.
 // DECIPHON_HIP_TIMING=1: phase times of the path pass on stderr (synchronises between phases)
 // windows [b, e) of x->path_sorted (window i there is window x->path_order[i] of the request)
-int path_fast(dcp_hip *x, int b, int e, std::vector<int> &redo)
+int path_fast(Pass const &ps, int b, int e, std::vector<int> &redo)
 {
+  dcp_hip *const x = ps.x;
   int const n = e - b;
-  Stopwatch tm(x->stream);
+  Stopwatch tm(ps.on.stream);
   Staged st;
-  int rc = stage(x, n, x->path_sorted.data() + b, ARENA_TABLE, st);
+  int rc = stage(ps, n, x->path_sorted.data() + b, ARENA_TABLE, st);
   if (rc) return rc;
   tm.lap("stage");
-  HIP_TRY(x, BK(x).d_out.reserve(2 * (size_t)n), DCP_ENOMEM);
+  HIP_TRY(x, ps.lists.d_out.reserve(2 * (size_t)n), DCP_ENOMEM);
   int const B = x->path_plan.B, G = x->path_plan.G;
   // checkpoints sit behind each window's block tables (DcpPathPlace::ckpt_off)
   std::vector<int64_t> ckpt_addr((size_t)n, 0), step_off;
-  StreamDrain drain{x->stream}; // destroyed before the two: an early return does not pull them from under a copy
+  StreamDrain drain{ps.on.stream}; // destroyed before the two: an early return does not pull them from under a copy
   int max_blocks = 1, strip_blocks = 0; // strip_blocks > 0: windows of the strip class that go in blocks
   for (DcpProblem const &p : st.problems)
   {
@@ -333,65 +346,53 @@ int path_fast(dcp_hip *x, int b, int e, std::vector<int> &redo)
     most = std::max(most, pl.blocks);
   }
   HIP_TRY(x, x->d_ckpt_addr.reserve((size_t)n), DCP_ENOMEM);
-  HIP_TRY(x, hipMemcpyAsync(x->d_ckpt_addr.p, ckpt_addr.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, x->stream),
+  HIP_TRY(x, hipMemcpyAsync(x->d_ckpt_addr.p, ckpt_addr.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, ps.on.stream),
           DCP_EFUNCUSE);
   HIP_TRY(x, x->d_trace.reserve((size_t)n), DCP_ENOMEM);
-  HIP_TRY(x, hipMemsetAsync(x->d_trace.p, 0, (size_t)n * sizeof(DcpTraceState), x->stream), DCP_EFUNCUSE);
-  if ((rc = stage_steps(x, st, n, step_off))) return rc;
-  // the classes of a slice are each too small to fill the GPU and each lasts as long as its longest window:
-  // they go out on their own streams, forked from and joined back into x->stream
-  int classes = 0;
-  for (int c = 0; c < DCP_NUM_CLASSES; ++c) classes += st.c_begin[c + 1] > st.c_begin[c];
-  Fork fk(x, classes > 1);
+  HIP_TRY(x, hipMemsetAsync(x->d_trace.p, 0, (size_t)n * sizeof(DcpTraceState), ps.on.stream), DCP_EFUNCUSE);
+  if ((rc = stage_steps(ps, st, n, step_off))) return rc;
   // The checkpoints of the windows that have more than one block, then the blocks from the last to the first.
-  // Every class does that on its own stream -- checkpoints, then per block its rows and the traceback through it --
-  // without waiting for the others: a class's windows are done when ITS slowest is, and the store kernel of one
-  // class runs beside the traceback of another (one join at the end).
-  {
-    char const *fused_env = getenv("DECIPHON_HIP_PATH_FUSED");
-    bool const fused = !(fused_env && fused_env[0] == '0');
-    if ((rc = fk.begin(x->stream))) return rc;
-    for (int c = 0; c < DCP_NUM_CLASSES; ++c)
+  // Every class does that on its own stream (each_class) -- checkpoints, then per block its rows and the traceback
+  // through it -- without waiting for the others: a class's windows are done when ITS slowest is, and the store kernel
+  // of one class runs beside the traceback of another (one join at the end).
+  char const *fused_env = getenv("DECIPHON_HIP_PATH_FUSED");
+  bool const fused = !(fused_env && fused_env[0] == '0');
+  rc = each_class(ps, st, -1, [&](int c, DcpLaunch a) {
+    a.arena = nullptr; // DcpProblem::trellis holds the table's address
+    if (c == DCP_STRIP_CLASS)
     {
-      DcpLaunch a = launch_args(x, st, c);
-      if (a.nprob <= 0) continue;
-      a.arena = nullptr; // DcpProblem::trellis holds the table's address
-      if ((rc = fk.enter(x->cls_branch[c], a))) return rc;
-      if (c == DCP_STRIP_CLASS)
+      // the checkpoints of those that go in blocks, then G blocks at a time; a window that keeps its whole table (no
+      // checkpoint address) is one block of the first round
+      if (strip_blocks > 0) HIP_TRY(x, dcp_launch_strip_ckpt(a, x->d_ckpt_addr.p, B), DCP_EFUNCUSE);
+      for (int it = 0; it == 0 || it * G < strip_blocks; ++it)
       {
-        // the checkpoints of those that go in blocks, then G blocks at a time; a window that keeps its whole table (no
-        // checkpoint address) is one block of the first round
-        if (strip_blocks > 0) HIP_TRY(x, dcp_launch_strip_ckpt(a, x->d_ckpt_addr.p, B), DCP_EFUNCUSE);
-        for (int it = 0; it == 0 || it * G < strip_blocks; ++it)
-        {
-          HIP_TRY(x, dcp_launch_strip_store(a, x->d_ckpt_addr.p, B, G, it), DCP_EFUNCUSE);
-          HIP_TRY(x, dcp_launch_traceback(a, x->d_steps.p, x->d_step_off.p, x->d_nsteps.p, x->d_trace.p, B, G, it,
-                                          x->d_ckpt_addr.p),
-                  DCP_EFUNCUSE);
-        }
-      }
-      else if (G <= 1 && fused) // one launch: every window walks its own blocks (dcp_path_blocks_kernel)
-        HIP_TRY(x, dcp_launch_path_blocks(c, a, x->d_ckpt_addr.p, B, x->d_steps.p, x->d_step_off.p, x->d_nsteps.p, x->d_trace.p),
+        HIP_TRY(x, dcp_launch_strip_store(a, x->d_ckpt_addr.p, B, G, it), DCP_EFUNCUSE);
+        HIP_TRY(x, dcp_launch_traceback(a, x->d_steps.p, x->d_step_off.p, x->d_nsteps.p, x->d_trace.p, B, G, it,
+                                        x->d_ckpt_addr.p),
                 DCP_EFUNCUSE);
-      else
-      {
-        // The checkpoints; then, G blocks at a time from the last to the first, the rows of those blocks of every
-        // window -- a workgroup per (window, block): G times the wavefronts, each walking 1 / blocks of the rows --
-        // and the traceback through them.  (G = 1 with DECIPHON_HIP_PATH_FUSED=0: a launch per block and phase.)
-        if (max_blocks > 1) HIP_TRY(x, dcp_launch_cost_ckpt(c, a, x->d_ckpt_addr.p, B), DCP_EFUNCUSE);
-        for (int it = 0; it * G < max_blocks; ++it)
-        {
-          HIP_TRY(x, dcp_launch_cost_store(c, a, x->d_ckpt_addr.p, B, G, it), DCP_EFUNCUSE);
-          HIP_TRY(x, dcp_launch_traceback(a, x->d_steps.p, x->d_step_off.p, x->d_nsteps.p, x->d_trace.p, B, G, it), DCP_EFUNCUSE);
-        }
       }
-      if ((rc = fk.leave(x->cls_branch[c]))) return rc;
     }
-    if ((rc = fk.join())) return rc;
-  }
+    else if (G <= 1 && fused) // one launch: every window walks its own blocks (dcp_path_blocks_kernel)
+      HIP_TRY(x, dcp_launch_path_blocks(c, a, x->d_ckpt_addr.p, B, x->d_steps.p, x->d_step_off.p, x->d_nsteps.p, x->d_trace.p),
+              DCP_EFUNCUSE);
+    else
+    {
+      // The checkpoints; then, G blocks at a time from the last to the first, the rows of those blocks of every
+      // window -- a workgroup per (window, block): G times the wavefronts, each walking 1 / blocks of the rows --
+      // and the traceback through them.  (G = 1 with DECIPHON_HIP_PATH_FUSED=0: a launch per block and phase.)
+      if (max_blocks > 1) HIP_TRY(x, dcp_launch_cost_ckpt(c, a, x->d_ckpt_addr.p, B), DCP_EFUNCUSE);
+      for (int it = 0; it * G < max_blocks; ++it)
+      {
+        HIP_TRY(x, dcp_launch_cost_store(c, a, x->d_ckpt_addr.p, B, G, it), DCP_EFUNCUSE);
+        HIP_TRY(x, dcp_launch_traceback(a, x->d_steps.p, x->d_step_off.p, x->d_nsteps.p, x->d_trace.p, B, G, it), DCP_EFUNCUSE);
+      }
+    }
+    return 0;
+  });
+  if (rc) return rc;
   tm.lap("traceback");
   PathFetched f;
-  if ((rc = fetch_results(x, n, 2 * (size_t)n, f))) return rc;
+  if ((rc = fetch_results(ps, n, 2 * (size_t)n, f))) return rc;
   tm.lap("fetch");
   for (DcpProblem const &p : st.problems)
   {
@@ -414,10 +415,10 @@ int path_fast(dcp_hip *x, int b, int e, std::vector<int> &redo)
   return 0;
 }
 
-int path_run(dcp_hip *x, int n, dcp_hip_window const *w)
+int path_run(Pass const &ps, int n, dcp_hip_window const *w)
 {
+  dcp_hip *const x = ps.x;
   HIP_TRY(x, hipSetDevice(x->device), DCP_EFUNCUSE);
-  PathContext ctx(x); // its own window lists, result buffers and streams: cost batches may be in flight
   // (as stage() would: the literal pass lays its trellises out by the committed profiles before it stages)
   if (x->committed != x->profiles.size()) return fail(x, DCP_EFUNCUSE, "profiles not committed");
   // every window is checked here, whichever pass takes it (path_literal indexes x->profiles before stage() looks)
@@ -459,14 +460,14 @@ int path_run(dcp_hip *x, int n, dcp_hip_window const *w)
     {
       int const e = (int)place_slice(x, x->path_plan, (size_t)b, budget);
       if (e == b) return fail(x, DCP_ENOMEM, "a window's DP table does not fit the device memory left");
-      int rc = path_fast(x, b, e, redo);
+      int rc = path_fast(ps, b, e, redo);
       if (rc) return rc;
       b = e;
     }
     std::sort(redo.begin(), redo.end());
   }
   x->path_redone = (int)redo.size();
-  return path_literal(x, redo, literal_only);
+  return path_literal(ps, redo, literal_only);
 }
 
 } // namespace
@@ -484,7 +485,8 @@ int dcp_hip_path(struct dcp_hip *x, int n, struct dcp_hip_window const *w)
   x->host_trellis.clear();
   x->path_table_bytes = 0;
   x->path_blocked = 0;
-  int const rc = path_run(x, n, w);
+  // its own window lists, result buffers and streams: cost batches may be in flight
+  int const rc = path_run(path_pass(x), n, w);
   if (rc)
   {
     x->paths.clear();
@@ -546,17 +548,17 @@ int dcp_hip_path_trellis(struct dcp_hip const *cx, int i, uint32_t const **xnode
                                                             : "the profiles, sequences, mode or xtrans table changed since "
                                                               "dcp_hip_path: call it again");
   HIP_TRY(x, hipSetDevice(x->device), DCP_EFUNCUSE);
-  PathContext ctx(x);
+  Pass const ps = path_pass(x);
   if (!x->paths[(size_t)i].has_trellis)
   {
     // The fast path pass keeps no trellis.  Somebody wants one: run the literal pass for the
     // whole batch once (its paths replace the fast ones; they are the same steps).
     std::vector<int> all((size_t)x->paths.size());
     for (size_t j = 0; j < all.size(); ++j) all[j] = (int)j;
-    int rc = path_literal(x, all);
+    int rc = path_literal(ps, all);
     if (rc) return rc;
   }
-  int rc = fetch_trellis(x, i);
+  int rc = fetch_trellis(ps, i);
   if (rc) return rc;
   uint32_t const *xn = reinterpret_cast<uint32_t const *>(x->host_trellis[(size_t)i].data());
   *xnodes = xn;

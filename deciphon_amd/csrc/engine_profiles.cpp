@@ -89,7 +89,7 @@ int describe(dcp_hip *x, int K, char const *accession, HostProfile &hp)
 int grow_keeping(dcp_hip *x, DevBuf<float> &buf, size_t floats, size_t keep)
 {
   if (floats <= buf.cap) return 0;
-  HIP_TRY(x, hipStreamSynchronize(x->stream), DCP_EFUNCUSE);
+  HIP_TRY(x, hipStreamSynchronize(x->cost_set.stream), DCP_EFUNCUSE);
   DevBuf<float> bigger;
   HIP_TRY(x, bigger.reserve(std::max(floats, buf.cap + buf.cap / 2)), DCP_ENOMEM);
   if (keep) HIP_TRY(x, hipMemcpy(bigger.p, buf.p, keep * sizeof(float), hipMemcpyDeviceToDevice), DCP_EFUNCUSE);
@@ -159,7 +159,7 @@ static int stage_chunks(dcp_hip *x, DcpDbReader &db, int first, std::vector<Host
     if (stage[b].reserve_exact(std::min(chunk_floats, off[(size_t)n])) != hipSuccess ||
         done[b].create(hipEventDisableTiming) != hipSuccess)
       return fail(x, DCP_ENOMEM, "cannot allocate pinned staging buffers");
-  StreamDrain drain{x->stream}; // (whichever way this ends: before the staging buffers go)
+  StreamDrain drain{x->cost_set.stream}; // (whichever way this ends: before the staging buffers go)
   int b = 0;
   for (int i0 = 0; i0 < n;)
   {
@@ -192,8 +192,8 @@ static int stage_chunks(dcp_hip *x, DcpDbReader &db, int first, std::vector<Host
     if (bad) return fail(x, bad, "cannot read protein");
     size_t const floats = off[(size_t)i1] - off[(size_t)i0];
     if (hipMemcpyAsync(x->d_pool.p + x->pool_used + off[(size_t)i0], buf, floats * sizeof(float), hipMemcpyHostToDevice,
-                       x->stream) != hipSuccess ||
-        hipEventRecord(done[b].e, x->stream) != hipSuccess)
+                       x->cost_set.stream) != hipSuccess ||
+        hipEventRecord(done[b].e, x->cost_set.stream) != hipSuccess)
       return fail(x, DCP_EFUNCUSE, "staging copy failed");
     busy[b] = true;
     b ^= 1;
@@ -342,7 +342,7 @@ int dcp_hip_commit_profiles(struct dcp_hip *x)
   ++x->gen; // even when there is nothing new to publish (the header: every accepted commit)
   if (x->committed == x->profiles.size()) return 0;
   // the tables are already in HBM; what is published here are the profile descriptors
-  HIP_TRY(x, hipStreamSynchronize(x->stream), DCP_EFUNCUSE);
+  HIP_TRY(x, hipStreamSynchronize(x->cost_set.stream), DCP_EFUNCUSE);
   std::vector<DcpProfileDev> dev(x->profiles.size());
   for (size_t i = 0; i < dev.size(); ++i)
   {
@@ -359,9 +359,9 @@ int dcp_hip_commit_profiles(struct dcp_hip *x)
   }
   HIP_TRY(x, x->d_profiles.reserve(dev.size()), DCP_ENOMEM);
   HIP_TRY(x, hipMemcpyAsync(x->d_profiles.p, dev.data(), dev.size() * sizeof(DcpProfileDev), hipMemcpyHostToDevice,
-                            x->stream),
+                            x->cost_set.stream),
           DCP_EFUNCUSE);
-  HIP_TRY(x, hipStreamSynchronize(x->stream), DCP_EFUNCUSE);
+  HIP_TRY(x, hipStreamSynchronize(x->cost_set.stream), DCP_EFUNCUSE);
   x->committed = x->profiles.size();
   x->plan_profiles.assign(x->profiles.begin(), x->profiles.end());
   return 0;
