@@ -139,6 +139,7 @@ int launch_cost_all(Pass const &ps, StagedPlan const &st, hipStream_t origin)
     else if (strcmp(e, "auto")) return fail(x, DCP_EFUNCUSE, "DECIPHON_HIP_XCD_PLACEMENT is not plain, eighths or auto");
   }
   std::vector<CostLaunch> const schedule = cost_schedule(st, !(narrow_env && narrow_env[0] == '0'));
+  x->last_cost_launches = schedule; // what dcp_hip_last_cost_launches reports: the loop below runs exactly this
   // the pass's stream joins the kernels only after the last launch (Fork::join): a wait is a barrier in its hardware
   // queue, and a stream that shares that queue would start its kernel behind every barrier issued before
   // (profiles/r02_step_timeline.txt)

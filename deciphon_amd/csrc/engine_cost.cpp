@@ -240,4 +240,16 @@ int dcp_hip_fetch_staged(struct dcp_hip *x, float *null_cost, float *alt_cost)
   return fetch_costs(cost_pass(x), (size_t)x->staged_n, null_cost, alt_cost);
 }
 
+int dcp_hip_last_cost_launches(struct dcp_hip const *x, int cap, int32_t *out)
+{
+  if (!x || cap < 0 || (cap > 0 && !out)) return -1;
+  std::vector<CostLaunch> const &s = x->last_cost_launches;
+  for (size_t i = 0; i < s.size() && i < (size_t)cap; ++i)
+  {
+    int32_t const row[5] = {s[i].kernel, s[i].index, s[i].first, s[i].count, s[i].windows_per_profile};
+    memcpy(out + 5 * i, row, sizeof row);
+  }
+  return (int)s.size();
+}
+
 } // extern "C"

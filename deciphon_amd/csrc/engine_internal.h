@@ -390,6 +390,7 @@ struct dcp_hip
   StagedPlan staged; // dcp_hip_stage: the list itself stays in batch[0]'s device buffers
   int staged_n = -1;
   bool staged_ran = false; // a dcp_hip_run_staged with reps > 0 has filled d_out since the dcp_hip_stage
+  std::vector<CostLaunch> last_cost_launches; // the schedule launch_cost_all ran last (dcp_hip_last_cost_launches)
 
   // Input generation: moves with every accepted change of the profiles, sequences, mode or xtrans override.  The
   // staged list and the path results remember the generation they were made under; dcp_hip_run_staged /

@@ -101,6 +101,7 @@ def load_library() -> C.CDLL:
     L.dcp_hip_stage.argtypes = [vp, i32, vp]
     L.dcp_hip_run_staged.argtypes = [vp, i32, f32p, C.POINTER(C.c_double)]
     L.dcp_hip_fetch_staged.argtypes = [vp, vp, vp]
+    L.dcp_hip_last_cost_launches.argtypes = [vp, i32, vp]
     L.dcp_hip_path.argtypes = [vp, i32, vp]
     L.dcp_hip_path_redone.argtypes = [vp]
     L.dcp_hip_path_table_bytes.argtypes = [vp]
@@ -390,6 +391,20 @@ class Engine:
         alt = np.zeros(self._staged_n, dtype=np.float32)
         self._check(self.lib.dcp_hip_fetch_staged(self.h, _p(nul), _p(alt)))
         return nul, alt
+
+    def last_cost_launches(self):
+        """The launches of this engine's most recent cost pass (cost, cost_hits, cost_hits_begin -- of the batch begun
+        last --, cost_bench, run_staged), in launch order: the dicts of host.cost_schedule, as the engine ran them."""
+        from .host import COST_BRANCHES, COST_KERNELS
+
+        n = self.lib.dcp_hip_last_cost_launches(self.h, 0, None)
+        rows = np.zeros((max(n, 1), 5), np.int32)
+        if n < 0 or self.lib.dcp_hip_last_cost_launches(self.h, len(rows), _p(rows)) != n:
+            raise HipError(8)
+        # a launch's branch follows from its kernel (csrc/stage_plan.cpp cost_schedule)
+        branch = {"narrow": COST_BRANCHES[1], "pack": COST_BRANCHES[2], "pack_lds": COST_BRANCHES[2]}
+        return [dict(kernel=COST_KERNELS[k], index=int(i), first=int(f), count=int(c), windows_per_profile=int(wpp),
+                     branch=branch.get(COST_KERNELS[k], COST_BRANCHES[0])) for k, i, f, c, wpp in rows[:n]]
 
     def path_reserve(self, nbytes: int):
         """Set HBM aside for the path pass's DP tables now (its clearing overlaps what follows)."""

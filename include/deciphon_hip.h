@@ -285,6 +285,14 @@ int dcp_hip_cost_bench(struct dcp_hip *, int n, struct dcp_hip_window const *, i
 int dcp_hip_stage(struct dcp_hip *, int n, struct dcp_hip_window const *);
 int dcp_hip_run_staged(struct dcp_hip *, int reps, float *ms, double *cells);
 int dcp_hip_fetch_staged(struct dcp_hip *, float *null_cost, float *alt_cost);
+/* test hook, a read-only query like dcp_hip_profile_read (allowed while batches are outstanding): the launches of the
+ * most recent cost pass of this engine (dcp_hip_cost, dcp_hip_cost_hits[_begin], dcp_hip_cost_bench,
+ * dcp_hip_run_staged; with two batches in flight, of the one begun last), in launch order.  Returns their number (0
+ * before the first pass, -1 for a null engine, a negative cap or cap > 0 without out) and writes up to cap records of
+ * five int32 {kernel, index, first, count, windows_per_profile}, kernel coded as dcp_cost_schedule_of
+ * (include/deciphon_host.h) codes it.  What the pass launched, not what a plan says it would: the tests of the cost
+ * kernels read from it which kernel gave the scores they compare. */
+int dcp_hip_last_cost_launches(struct dcp_hip const *, int cap, int32_t *out);
 
 #ifdef __cplusplus
 }

@@ -2,7 +2,13 @@
 1 .. K - 2 positions (tests/delete_run_cases.py) -- through Engine.cost, bit for bit against the oracle: every
 single-wave kernel (1..8 and 10 positions per lane) at both ends of the profiles it serves, and every pack shape
 with windows of different lengths in one pack, packed with and without the LDS tables and one window per wavefront.
-One path call per class: the table-writing kernels of the path pass share the cost kernels' row()."""
+One path call per class: the table-writing kernels of the path pass share the cost kernels' row().
+
+Which kernels that is: test_single_wave_shapes sends one core size per request, so it runs the class kernels
+dcp_cost_kernel<1..4,1>, <6,1>, <8,1> and the narrow kernels <5,1>, <7,1>, <10,1>, never the fused kernel and never the
+class kernel of 513..640 positions, <6,2>; the "plain" requests of test_pack_shapes_with_mixed_window_lengths mix classes
+0 and 1 and are small, so they run in the fused kernel, not in <1,1> and <2,1>.  Every kernel by itself on these runs,
+with the engine saying which one ran: tests/test_gpu_cost_routes.py."""
 import numpy as np
 import pytest
 

@@ -1,7 +1,13 @@
 """GPU: the cases of tests/test_emul_row_loop_ends.py through Engine.cost and Engine.path, bit for bit: short windows
-(every length up to twelve rows, every residue of L mod 5 around larger lengths) through every single-wave kernel
+(every length up to twelve rows, every residue of L mod 5 around larger lengths) through every single-wave shape
 and every pack shape, packs whose windows end at different rows, and finite junk at k = 0 of MM, MD, IM, DM, DD,
-which must leave scores and paths what they are with +inf there."""
+which must leave scores and paths what they are with +inf there.
+
+Which kernels that is: every request here that runs one window per wavefront mixes the single-wave classes and is
+small, so its windows of up to 256 positions (Q = 1..4) all run in the fused kernel, dcp_cost_kernel_fused -- never in
+dcp_cost_kernel<1..4,1> -- and those above in the narrow kernels <5,1>, <7,1>, <10,1> and the class kernels <6,1>,
+<8,1>.  The same windows through each class kernel by itself, with the engine saying which kernel ran:
+tests/test_gpu_cost_routes.py."""
 import numpy as np
 import pytest
 
@@ -43,6 +49,7 @@ def check_paths(orc, profs, reads, wins, res, what):
 
 
 def test_short_windows_single_wave_shapes(engine, orc, monkeypatch):
+    """all 18 profiles in one request: a small mix of classes, so Q = 1..4 run in the fused kernel (see above)"""
     monkeypatch.setenv("DECIPHON_HIP_PACK", "0")  # K <= 124 too on a wavefront of its own
     rng = np.random.default_rng(801)
     profs = [synth_profile(rng, K, [None, 2.0][Q % 2]) for Q, K in SINGLE_WAVE]
