@@ -107,7 +107,7 @@ int ensure_pool(dcp_hip *x, size_t floats, size_t keep)
 }
 
 // The kernels take E_l = min_k M_l[k] (viterbi_body.h) and bound what a delete run can carry across a
-// wavefront (CostWave::row): both need the delete costs MD, DD to be non-negative, which -log-probabilities
+// wavefront (dcp_exchange_publish): both need the delete costs MD, DD to be non-negative, which -log-probabilities
 // are.  Anything else (a positive log-probability in a corrupt file, a hand-made table) is refused.
 bool delete_costs_ok(float const *trans, int K, int Kp)
 {

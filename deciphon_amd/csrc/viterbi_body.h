@@ -1,6 +1,6 @@
 // viterbi_body.h -- the quasi-codon Viterbi recurrences, one wavefront per
 // (profile x window) problem, written against the lane vocabulary of
-// lane_ops_gpu.h (tests/emul/ re-instantiates it with 64-wide arrays).
+// lane_ops_gpu.h (tests/emul/ re-instantiates it on a lock-step emulator, a vector of 64 lanes per wavefront).
 //
 // Layout: lane e of the wave owns the Q consecutive profile positions
 // k = e*Q + q (the reference's striping k = e*Q + q, c-core/viterbi.c:220-221,
@@ -8,9 +8,12 @@
 // needs E of row l, c-core/viterbi.c:582); the five emission lengths t = 1..5 of
 // a row and the K positions are the parallel work.
 //
-//   CostWave<Q>  viterbi_null + viterbi_cost (c-core/viterbi.c:696-724): scores only.
-//   PathWave<Q>  viterbi_path (c-core/viterbi.c:726-732): back-pointers, pass by
-//                pass exactly as the reference orders its strict-< updates.
+//   CostWave<Q, W>   viterbi_null + viterbi_cost (c-core/viterbi.c:696-724): scores only, W wavefronts per window.
+//   StripWave<Q, W>  the same for profiles beyond one workgroup's registers (K > 4096), strip by strip.
+//   PackWave<Q, S>   the same for several short windows per wavefront (viterbi_pack.h).
+//   PathWave<Q, W>   viterbi_path (c-core/viterbi.c:726-732): back-pointers, pass by
+//                    pass exactly as the reference orders its strict-< updates.
+// What the three score-only waves share of a row's arithmetic stands once, below ("The recurrences of a row").
 #pragma once
 #include "dcp_types.h"
 
@@ -116,6 +119,160 @@ DCP_FN lf lane_shift_up_again(lf &x) { return lane_shift_up(x, 0.0f); }
 
 // dcp_row_source_lane (dcp_types.h) in the lane vocabulary: of `real` lanes that own a position, the one lane reads as
 DCP_FN lu row_source_lane(lu lane, int real) { return lminu(lane, lu_splat((uint32_t)real - 1u)); }
+
+// =============================================================================
+// The recurrences of a row, once for CostWave, StripWave and PackWave (viterbi_pack.h).  The bits of a score depend on
+// the association and the operand order of these additions and minima: what stands here stands nowhere else.
+// The fold and a lane's own delete chain are stated per position and looped over where they are used: helpers that
+// take the arrays moved registers and schedules of single-wave kernels (profiles/r27_row_recurrences.txt).  For the
+// same reason M and I of a row (the minimum over five emission lengths, dcp_row_min's association), the special lanes
+// at row 0 and the row loop by ring phase stay written out in CostWave, StripWave and PackWave.
+// (Unnamed namespace: every translation unit takes its own instances, as the wave emulator's units need.)
+// =============================================================================
+namespace
+{
+// X_l = min_t (Xpre_{l-t} + e[c_t]) of a row in ring phase P, the longest emission first (the special states:
+// c-core/viterbi.c:492-502, :713)
+template <int P, class T> DCP_FN lf dcp_row_min(lf const (&pre)[5], T const (&e)[5])
+{
+  return lmin3(lmin3(pre[DCP_SL(P, 5)] + e[4], pre[DCP_SL(P, 4)] + e[3], pre[DCP_SL(P, 3)] + e[2]),
+               pre[DCP_SL(P, 2)] + e[1], pre[DCP_SL(P, 1)] + e[0]);
+}
+
+// D_l[k] = min(M_l[k-1] + MD[k], D_l[k-1] + DD[k])  (c-core/viterbi.c:538,553-580)
+DCP_FN lf dcp_delete(lf Ml, lf md, lf Dl, lf dd) { return lmin(Ml + md, Dl + dd); }
+// ... inside a lane: its own chain, with Msh0 = M of the k-1 neighbour of its position 0 and no D entering it
+template <int Q>
+DCP_FN void dcp_own_chain(lf (&D)[Q], lf Msh0, lf const (&M)[Q], lf const (&MD)[Q], lf const (&DD)[Q])
+{
+  D[0] = Msh0 + MD[0];
+#pragma unroll
+  for (int q = 1; q < Q; ++q) D[q] = dcp_delete(M[q - 1], MD[q], D[q - 1], DD[q]);
+}
+// ... and on through a lane whose D[0] has fallen
+template <int Q> DCP_FN void dcp_chain_on(lf (&D)[Q], lf const (&DD)[Q])
+{
+#pragma unroll
+  for (int q = 1; q < Q; ++q) D[q] = lmin(D[q], D[q - 1] + DD[q]);
+}
+
+// The chain carried from lane to lane inside each wave while any lane improves; `fill` stands in front of each wave's
+// first lane.  Returns what was shifted into every lane's position 0 last.
+template <int Q, int W> DCP_FN lf dcp_seg_turns(Group<W> &g, lf (&D)[Q], lf const (&DD)[Q], lf fill)
+{
+  lf Dsh = g.seg_shift_up(D[Q - 1], fill);
+  lf x = Dsh + DD[0];
+  lm better = llt(x, D[0]);
+  while (g.seg_any(better))
+  {
+    D[0] = lmin(D[0], x);
+    dcp_chain_on(D, DD);
+    Dsh = g.seg_shift_up(D[Q - 1], fill);
+    x = Dsh + DD[0];
+    better = llt(x, D[0]);
+  }
+  return Dsh;
+}
+
+// The k-1 neighbour of a lane's position q: its own position q - 1, or sh0, what was shifted in from the lane before.
+// (The strips only: in dcp_path_blocks_kernel<6, 1> and <8, 1> the fold worded with it takes 12 and 10 registers more.)
+template <int Q> DCP_FN lf dcp_left(int q, lf const (&A)[Q], lf sh0) { return q ? A[q ? q - 1 : 0] : sh0; }
+
+// A position of a finished row folded into its ring slot (the header of this section), Ml, Il, Dl being M, I, D of
+// position k-1:  Mpre[k] = min(B + BM[k], Ml + MM[k], min(Il + IM[k], Dl + DM[k])),
+//                Ipre[k] = min(I[k] + II[k], M[k] + MI[k])
+DCP_FN lf dcp_fold_m(lf B, lf bm, lf Ml, lf mm, lf Il, lf im, lf Dl, lf dm)
+{
+  return lmin3(B + bm, Ml + mm, lmin(Il + im, Dl + dm));
+}
+DCP_FN lf dcp_fold_i(lf I, lf ii, lf M, lf mi) { return lmin(I + ii, M + mi); }
+
+// Row 0 of the ring (c-core/viterbi.c:471-473): B = SB, so Mpre_0 = SB + BM, everything else +inf
+template <int Q> DCP_FN void dcp_ring_row0(lf (&Mpre)[5][Q], lf (&Ipre)[5][Q], lf SB, lf const (&BM)[Q])
+{
+#pragma unroll
+  for (int s = 0; s < 5; ++s)
+  {
+#pragma unroll
+    for (int q = 0; q < Q; ++q)
+    {
+      Mpre[s][q] = s ? lf_splat(DCP_INF) : SB + BM[q];
+      Ipre[s][q] = lf_splat(DCP_INF);
+    }
+  }
+}
+
+// The D chain of a row over W wavefronts, ONE barrier per row.  Before it every wave finishes what it can alone: its D
+// chain with nothing entering at its first lane.  It publishes one record {M, I, D of its last position, min of its M};
+// after the barrier the first lane of each wave takes M, I, D of the previous wave's last position as its k-1 neighbour
+// (in front of wave 0 stands +inf, or the last position of the strip before: StripWave).  That is exact provided the D
+// published by every wave is already final, i.e. nothing entering a wave at its first lane can run through ALL its
+// positions and still arrive below the published value.  Whatever enters costs at least E (it is some M of this row
+// plus non-negative costs) and running through wave w adds tdd(w) = sum of DD over its positions but the first, so
+// E + tdd(w) >= D_last(w)  for every w (with a margin for the order of the fp32 additions) proves it -- every wave
+// evaluates the same test on the same records.  If it fails (profiles whose delete runs are nearly free) the row falls
+// back to the exchange-until-stable protocol, barriers and all.
+// The margin: fp32 addition is monotonic and MD, DD >= 0, so what arrives is no less than the chain
+// fl(..fl(fl(E + DD) + DD)..) over the wave's n <= 511 positions but the first.  Every partial sum lies in
+// [-|E|, |E| + tdd(w)], so each step rounds by at most 2^-24 (|E| + tdd(w)) and the chain is at least
+// E + tdd(w) - 511 * 2^-24 (|E| + tdd(w)) = E + tdd(w) - 3.1e-5 (|E| + tdd(w)); the butterfly sum of tdd
+// (Q + 5 additions deep), the sum s and the product add less than 2e-6 of the same.  The test is therefore
+// s - 1e-4 (|E| + tdd(w)) >= D_last(w)  (get_e_could), NOT s (1 - 1e-4): match costs may be negative, and
+// with E = -996, tdd = 998 the chain rounds 5e-3 below s = 2 (tests/test_emul_wave_exchange.py,
+// test_a_run_that_cancels_what_entered_it).  For E >= 0 the two are the same number.
+// In two halves, for what stands between them differs from caller to caller: the barrier (before it a whole row
+// publishes its special states as well), then get_prev for the previous wave's Mp, Ip, Dp and the test on the records
+// -- `could`: something entering a wave might still lower its D (get_e_could for a whole row, get_e_could_row for a
+// strip of one).  m is the lane's min over its M.  Out: the final D, and the k-1 neighbours of every lane's position 0.
+template <int Q, int W>
+DCP_FN void dcp_exchange_publish(Group<W> &g, int par, lf const (&M)[Q], lf const (&I)[Q], lf m, lf const (&MD)[Q],
+                                 lf const (&DD)[Q], lf (&D)[Q])
+{
+  lf const inf = lf_splat(DCP_INF);
+  dcp_own_chain(D, g.seg_shift_up(M[Q - 1], inf), M, MD, DD);
+  dcp_seg_turns(g, D, DD, inf);
+  g.put_rec(par, M[Q - 1], I[Q - 1], D[Q - 1], m);
+}
+template <int Q, int W>
+DCP_FN void dcp_exchange_finish(Group<W> &g, bool could, lf Mp, lf Ip, lf Dp, lf const (&M)[Q], lf const (&I)[Q],
+                                lf const (&MD)[Q], lf const (&DD)[Q], lf (&D)[Q], lf &Msh0, lf &Ish0, lf &Dsh0)
+{
+  Msh0 = g.seg_shift_up(M[Q - 1], Mp);
+  Ish0 = g.seg_shift_up(I[Q - 1], Ip);
+  if (!could)
+  {
+    // the first lane of each wave: D[0] = min(M[k-1] + MD, D[k-1] + DD) with the neighbour's
+    // values; then on through the wave while it improves anything
+    D[0] = lsel(g.seg_first(), lmin(Mp + MD[0], Dp + DD[0]), D[0]);
+    dcp_chain_on(D, DD);
+    Dsh0 = dcp_seg_turns(g, D, DD, Dp);
+  }
+  else
+  {
+    g.note_fallback();
+    dcp_own_chain(D, Msh0, M, MD, DD);
+    g.put_last(GS_D, D[Q - 1]);
+    g.sync();
+    Dsh0 = g.get_shift_carry(GS_D, D[Q - 1], Dp);
+    lf x = Dsh0 + DD[0];
+    lm better = llt(x, D[0]);
+    g.put_any(GS_F, better);
+    g.sync();
+    while (g.get_any(GS_F, better))
+    {
+      D[0] = lmin(D[0], x);
+      dcp_chain_on(D, DD);
+      g.put_last(GS_D, D[Q - 1]);
+      g.sync();
+      Dsh0 = g.get_shift_carry(GS_D, D[Q - 1], Dp);
+      x = Dsh0 + DD[0];
+      better = llt(x, D[0]);
+      g.put_any(GS_F, better);
+      g.sync();
+    }
+  }
+}
+} // namespace
 
 // STORE = true additionally writes every row's final values to a DP table in HBM
 // (cells[l][{M,I,D}][Kp] and specials[l][8] = N,B,J,E,C) for the traceback of
@@ -319,18 +476,8 @@ template <int Q, int W, bool STORE = false, int POLICY = DCP_SHAPE_POLICY(Q, W)>
               lsel(l1, lf_splat(xt[DCP_JJ]), lsel(l2, lf_splat(xt[DCP_CC]), lsel(l3, lf_splat(RR), inf))));
     // row 0 (c-core/viterbi.c:471-473, :703): S = 0, B = SB, R = -RR, rest +inf
 #pragma unroll
-    for (int s = 0; s < 5; ++s)
-    {
-      Spre[s] = inf;
-#pragma unroll
-      for (int q = 0; q < Q; ++q)
-      {
-        Mpre[s][q] = inf;
-        Ipre[s][q] = inf;
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < Q; ++q) Mpre[0][q] = lf_splat(SB) + BM[q];
+    for (int s = 0; s < 5; ++s) Spre[s] = inf;
+    dcp_ring_row0(Mpre, Ipre, lf_splat(SB), BM);
     Spre[0] = lsel(l0, lf_splat(0.0f + SN), lsel(l3, lf_splat(-RR + RR), inf));
     X = lsel(l3, lf_splat(-RR), inf);
     E = DCP_INF;
@@ -354,8 +501,7 @@ template <int Q, int W, bool STORE = false, int POLICY = DCP_SHAPE_POLICY(Q, W)>
                          Ipre[DCP_SL(P, 3)][q] + bgv[2]),
                    Ipre[DCP_SL(P, 2)][q] + bgv[1], Ipre[DCP_SL(P, 1)][q] + bgv[0]);
     }
-    X = lmin3(lmin3(Spre[DCP_SL(P, 5)] + nil[4], Spre[DCP_SL(P, 4)] + nil[3], Spre[DCP_SL(P, 3)] + nil[2]),
-              Spre[DCP_SL(P, 2)] + nil[1], Spre[DCP_SL(P, 1)] + nil[0]);
+    X = dcp_row_min<P>(Spre, nil);
 
     // emissions of this row are consumed: fetch the next row's behind the rest
     if constexpr (!LATE_FETCH) fetch(l + 2, L);
@@ -381,113 +527,26 @@ template <int Q, int W, bool STORE = false, int POLICY = DCP_SHAPE_POLICY(Q, W)>
       J = read_lane(X, 1);
       B = lmin3(N + NBv, E + EBv, J + JBv); // c-core/viterbi.c:495-496,582-583 (uniform)
 
-      // D_l[k] = min(M_l[k-1] + MD[k], D_l[k-1] + DD[k])  (c-core/viterbi.c:538,553-580):
       // serial inside a lane, then carried across lanes until no lane improves (the
       // reference's lazy D->D loop, c-core/viterbi.c:569-580)
       D[0] = Msh0 + MD[0];
 #pragma unroll
-      for (int q = 1; q < Q; ++q) D[q] = lmin(M[q - 1] + MD[q], D[q - 1] + DD[q]);
+      for (int q = 1; q < Q; ++q) D[q] = dcp_delete(M[q - 1], MD[q], D[q - 1], DD[q]);
       Dsh0 = dcp_lazy_turns_carry<Q, TURNS>(D, DD); // (unshifted yet)
     }
     else
     {
-      // W wavefronts, ONE barrier per row.  Before it every wave finishes what it can alone:
-      // its D chain with nothing entering at its first lane.  It publishes one record
-      // {M, I, D of its last position, min of its M}; after the barrier the first lane of
-      // each wave takes M, I, D of the previous wave's last position as its k-1 neighbour.
-      // That is exact provided the D published by every wave is already final, i.e. nothing
-      // entering a wave at its first lane can run through ALL its positions and still arrive
-      // below the published value.  Whatever enters costs at least E (it is some M of this row
-      // plus non-negative costs) and running through wave w adds tdd(w) = sum of DD over its
-      // positions but the first, so  E + tdd(w) >= D_last(w)  for every w (with a margin for the
-      // order of the fp32 additions) proves it -- every wave evaluates the same test on the
-      // same records.  If it fails (profiles whose delete runs are nearly free) the row falls
-      // back to the exchange-until-stable protocol below, barriers and all.
-      // The margin: fp32 addition is monotonic and MD, DD >= 0, so what arrives is no less than the chain
-      // fl(..fl(fl(E + DD) + DD)..) over the wave's n <= 511 positions but the first.  Every partial sum lies in
-      // [-|E|, |E| + tdd(w)], so each step rounds by at most 2^-24 (|E| + tdd(w)) and the chain is at least
-      // E + tdd(w) - 511 * 2^-24 (|E| + tdd(w)) = E + tdd(w) - 3.1e-5 (|E| + tdd(w)); the butterfly sum of tdd
-      // (Q + 5 additions deep), the sum s and the product add less than 2e-6 of the same.  The test is therefore
-      // s - 1e-4 (|E| + tdd(w)) >= D_last(w)  (get_e_could), NOT s (1 - 1e-4): match costs may be negative, and
-      // with E = -996, tdd = 998 the chain rounds 5e-3 below s = 2 (tests/test_emul_wave_exchange.py,
-      // test_a_run_that_cancels_what_entered_it).  For E >= 0 the two are the same number.
       int const par = l & 1;
-      lf const inf = lf_splat(DCP_INF);
-      lf x, Dsh;
-      lm better;
-      D[0] = g.seg_shift_up(M[Q - 1], inf) + MD[0];
-#pragma unroll
-      for (int q = 1; q < Q; ++q) D[q] = lmin(M[q - 1] + MD[q], D[q - 1] + DD[q]);
-      Dsh = g.seg_shift_up(D[Q - 1], inf);
-      x = Dsh + DD[0];
-      better = llt(x, D[0]);
-      while (g.seg_any(better))
-      {
-        D[0] = lmin(D[0], x);
-#pragma unroll
-        for (int q = 1; q < Q; ++q) D[q] = lmin(D[q], D[q - 1] + DD[q]);
-        Dsh = g.seg_shift_up(D[Q - 1], inf);
-        x = Dsh + DD[0];
-        better = llt(x, D[0]);
-      }
-      g.put_rec(par, M[Q - 1], I[Q - 1], D[Q - 1], m);
-      g.put_lanes4(GS_X0 + par, X);
-      g.sync();
       lf Mp, Ip, Dp;
       bool could;
+      dcp_exchange_publish(g, par, M, I, m, MD, DD, D);
+      g.put_lanes4(GS_X0 + par, X);
+      g.sync();
       g.get_prev(par, Mp, Ip, Dp);
       g.get_e_could(par, E, could);
       g.get_nj(GS_X0 + par, X, N, J);
-      Msh0 = g.seg_shift_up(M[Q - 1], Mp);
-      Ish0 = g.seg_shift_up(I[Q - 1], Ip);
       B = lmin3(N + NBv, E + EBv, J + JBv);
-      if (!could)
-      {
-        // the first lane of each wave: D[0] = min(M[k-1] + MD, D[k-1] + DD) with the neighbour's
-        // values; then on through the wave while it improves anything
-        D[0] = lsel(g.seg_first(), lmin(Mp + MD[0], Dp + DD[0]), D[0]);
-#pragma unroll
-        for (int q = 1; q < Q; ++q) D[q] = lmin(D[q], D[q - 1] + DD[q]);
-        Dsh0 = g.seg_shift_up(D[Q - 1], Dp);
-        x = Dsh0 + DD[0];
-        better = llt(x, D[0]);
-        while (g.seg_any(better))
-        {
-          D[0] = lmin(D[0], x);
-#pragma unroll
-          for (int q = 1; q < Q; ++q) D[q] = lmin(D[q], D[q - 1] + DD[q]);
-          Dsh0 = g.seg_shift_up(D[Q - 1], Dp);
-          x = Dsh0 + DD[0];
-          better = llt(x, D[0]);
-        }
-      }
-      else
-      {
-        g.note_fallback();
-        D[0] = Msh0 + MD[0];
-#pragma unroll
-        for (int q = 1; q < Q; ++q) D[q] = lmin(M[q - 1] + MD[q], D[q - 1] + DD[q]);
-        g.put_last(GS_D, D[Q - 1]);
-        g.sync();
-        Dsh0 = g.get_shift(GS_D, D[Q - 1], DCP_INF);
-        x = Dsh0 + DD[0];
-        better = llt(x, D[0]);
-        g.put_any(GS_F, better);
-        g.sync();
-        while (g.get_any(GS_F, better))
-        {
-          D[0] = lmin(D[0], x);
-#pragma unroll
-          for (int q = 1; q < Q; ++q) D[q] = lmin(D[q], D[q - 1] + DD[q]);
-          g.put_last(GS_D, D[Q - 1]);
-          g.sync();
-          Dsh0 = g.get_shift(GS_D, D[Q - 1], DCP_INF);
-          x = Dsh0 + DD[0];
-          better = llt(x, D[0]);
-          g.put_any(GS_F, better);
-          g.sync();
-        }
-      }
+      dcp_exchange_finish(g, could, Mp, Ip, Dp, M, I, MD, DD, D, Msh0, Ish0, Dsh0);
     }
 
     // fold row l into the ring (slot P held row l-5, no longer needed)
@@ -527,8 +586,8 @@ template <int Q, int W, bool STORE = false, int POLICY = DCP_SHAPE_POLICY(Q, W)>
           lf const Ml = q ? M[q ? q - 1 : 0] : Msh0;
           lf const Il = q ? I[q ? q - 1 : 0] : Ish0;
           lf const Dl = q ? D[q ? q - 1 : 0] : Dsh0;
-          Mpre[P][q] = lmin3(B + bm[i], Ml + mm[i], lmin(Il + im[i], Dl + dm[i]));
-          Ipre[P][q] = lmin(I[q] + ii[i], M[q] + mi[i]);
+          Mpre[P][q] = dcp_fold_m(B, bm[i], Ml, mm[i], Il, im[i], Dl, dm[i]);
+          Ipre[P][q] = dcp_fold_i(I[q], ii[i], M[q], mi[i]);
         }
         sched_fence(); // (the scheduler would bring every chunk's LDS reads up front: 36 registers more at the peak)
       }
@@ -553,8 +612,8 @@ template <int Q, int W, bool STORE = false, int POLICY = DCP_SHAPE_POLICY(Q, W)>
         lf const Ml = q ? M[q ? q - 1 : 0] : Msh0;
         lf const Il = q ? I[q ? q - 1 : 0] : Ish0;
         lf const Dl = q ? D[q ? q - 1 : 0] : Dsh0;
-        Mpre[P][q] = lmin3(B + BM[q], Ml + MM[q], lmin(Il + IM[q], Dl + DM[q]));
-        Ipre[P][q] = lmin(I[q] + II[q], M[q] + MI[q]);
+        Mpre[P][q] = dcp_fold_m(B, BM[q], Ml, MM[q], Il, IM[q], Dl, DM[q]);
+        Ipre[P][q] = dcp_fold_i(I[q], II[q], M[q], MI[q]);
       }
     }
     Spre[P] = lmin(lf_splat(E) + sa, X + sb);
@@ -629,7 +688,7 @@ template <int Q, int W, bool STORE = false, int POLICY = DCP_SHAPE_POLICY(Q, W)>
 // row is used: M_l[k] = min_t(min(B_{l-t} + BM[k], rest_{l-t}[k]) + match[c_t][k]), the same
 // fp32 values.  k-1 across a strip boundary and the D chain entering a strip come from the
 // previous strip of the same row, which is complete: its last position is "the record of the
-// wave before wave 0" of the one-barrier exchange (CostWave::row).
+// wave before wave 0" of the one-barrier exchange (dcp_exchange_publish / dcp_exchange_finish).
 // =============================================================================
 template <int Q, int W, bool STORE = false> struct StripWave
 {
@@ -768,8 +827,7 @@ template <int Q, int W, bool STORE = false> struct StripWave
       off[t] = cr.c[t] * stride_bytes;
       load_row_hdr(rows, off[t], nil[t], bgv[t]);
     }
-    X = lmin3(lmin3(Spre[DCP_SL(P, 5)] + nil[4], Spre[DCP_SL(P, 4)] + nil[3], Spre[DCP_SL(P, 3)] + nil[2]),
-              Spre[DCP_SL(P, 2)] + nil[1], Spre[DCP_SL(P, 1)] + nil[0]);
+    X = dcp_row_min<P>(Spre, nil);
     g.put_lanes4(GS_X0 + (l & 1), X); // visible after this row's first exchange
     float Erun = DCP_INF;
     for (int s = 0; s < S; ++s)
@@ -805,82 +863,17 @@ template <int Q, int W, bool STORE = false> struct StripWave
 #pragma unroll
       for (int q = 1; q < Q; ++q) m = lmin(m, M[q]);
 
-      // the one-barrier exchange of CostWave::row, with the previous strip's last position
-      // standing in front of wave 0
+      // the one-barrier exchange, with the previous strip's last position standing in front of wave 0
       int const par = tick;
       tick ^= 1;
-      lf x, Dsh;
-      lm better;
-      D[0] = g.seg_shift_up(M[Q - 1], inf) + MD[0];
-#pragma unroll
-      for (int q = 1; q < Q; ++q) D[q] = lmin(M[q - 1] + MD[q], D[q - 1] + DD[q]);
-      Dsh = g.seg_shift_up(D[Q - 1], inf);
-      x = Dsh + DD[0];
-      better = llt(x, D[0]);
-      while (g.seg_any(better))
-      {
-        D[0] = lmin(D[0], x);
-#pragma unroll
-        for (int q = 1; q < Q; ++q) D[q] = lmin(D[q], D[q - 1] + DD[q]);
-        Dsh = g.seg_shift_up(D[Q - 1], inf);
-        x = Dsh + DD[0];
-        better = llt(x, D[0]);
-      }
-      g.put_rec(par, M[Q - 1], I[Q - 1], D[Q - 1], m);
-      g.sync();
-      lf Mp, Ip, Dp;
       float Es;
+      lf Mp, Ip, Dp, Msh0, Ish0, Dsh0;
       bool could;
+      dcp_exchange_publish(g, par, M, I, m, MD, DD, D);
+      g.sync();
       g.get_prev(par, Mp, Ip, Dp);
       g.get_e_could_row(par, s, Erun, Es, could);
-      lf const Msh0 = g.seg_shift_up(M[Q - 1], Mp);
-      lf const Ish0 = g.seg_shift_up(I[Q - 1], Ip);
-      lf Dsh0;
-      if (!could)
-      {
-        D[0] = lsel(g.seg_first(), lmin(Mp + MD[0], Dp + DD[0]), D[0]);
-#pragma unroll
-        for (int q = 1; q < Q; ++q) D[q] = lmin(D[q], D[q - 1] + DD[q]);
-        Dsh0 = g.seg_shift_up(D[Q - 1], Dp);
-        x = Dsh0 + DD[0];
-        better = llt(x, D[0]);
-        while (g.seg_any(better))
-        {
-          D[0] = lmin(D[0], x);
-#pragma unroll
-          for (int q = 1; q < Q; ++q) D[q] = lmin(D[q], D[q - 1] + DD[q]);
-          Dsh0 = g.seg_shift_up(D[Q - 1], Dp);
-          x = Dsh0 + DD[0];
-          better = llt(x, D[0]);
-        }
-      }
-      else
-      {
-        g.note_fallback();
-        D[0] = Msh0 + MD[0];
-#pragma unroll
-        for (int q = 1; q < Q; ++q) D[q] = lmin(M[q - 1] + MD[q], D[q - 1] + DD[q]);
-        g.put_last(GS_D, D[Q - 1]);
-        g.sync();
-        Dsh0 = g.get_shift_carry(GS_D, D[Q - 1], Dp);
-        x = Dsh0 + DD[0];
-        better = llt(x, D[0]);
-        g.put_any(GS_F, better);
-        g.sync();
-        while (g.get_any(GS_F, better))
-        {
-          D[0] = lmin(D[0], x);
-#pragma unroll
-          for (int q = 1; q < Q; ++q) D[q] = lmin(D[q], D[q - 1] + DD[q]);
-          g.put_last(GS_D, D[Q - 1]);
-          g.sync();
-          Dsh0 = g.get_shift_carry(GS_D, D[Q - 1], Dp);
-          x = Dsh0 + DD[0];
-          better = llt(x, D[0]);
-          g.put_any(GS_F, better);
-          g.sync();
-        }
-      }
+      dcp_exchange_finish(g, could, Mp, Ip, Dp, M, I, MD, DD, D, Msh0, Ish0, Dsh0);
       Erun = __builtin_fminf(Erun, Es);
 
       // fold this strip of row l into ring slot P (it held row l-5, already consumed above)
@@ -888,11 +881,10 @@ template <int Q, int W, bool STORE = false> struct StripWave
 #pragma unroll
       for (int q = 0; q < Q; ++q)
       {
-        lf const Ml = q ? M[q ? q - 1 : 0] : Msh0;
-        lf const Il = q ? I[q ? q - 1 : 0] : Ish0;
-        lf const Dl = q ? D[q ? q - 1 : 0] : Dsh0;
-        rest[q] = lmin3(Ml + MM[q], Il + IM[q], Dl + DM[q]);
-        ipre[q] = lmin(I[q] + II[q], M[q] + MI[q]);
+        // (the B term joins when the row is used: above.  With Ml, Il, Dl named first as in CostWave's fold,
+        // dcp_strip_kernel<4, 8> takes 161 registers instead of 160, across an allocation granule)
+        rest[q] = lmin3(dcp_left(q, M, Msh0) + MM[q], dcp_left(q, I, Ish0) + IM[q], dcp_left(q, D, Dsh0) + DM[q]);
+        ipre[q] = dcp_fold_i(I[q], II[q], M[q], MI[q]);
       }
       store_q<Q>(ring + (size_t)P * Kp + col, lane, rest);
       store_q<Q>(ring + (size_t)(5 + P) * Kp + col, lane, ipre);

@@ -35,9 +35,6 @@
 #ifndef DCP_INF
 #error "include viterbi_body.h before viterbi_pack.h"
 #endif
-#ifndef DCP_SL
-#define DCP_SL(P, t) (((P) + 5 - (t)) % 5)
-#endif
 
 // A load costs the vector cache a cycle or two per 128-B line it touches, whatever it uses of the line, and a
 // pack touches G different table rows per load: the packed kernels are bound by lines, not by instructions
@@ -204,18 +201,8 @@ template <int Q, int S, int TURNS = dcp_lazy_turns(Q), int NLDS = 0, bool LATE =
     nbjb = lsel(l0, NB, lsel(l1, JB, inf));
     // row 0 (c-core/viterbi.c:471-473, :703): S = 0, B = SB, R = -RR, rest +inf
 #pragma unroll
-    for (int s = 0; s < 5; ++s)
-    {
-      Spre[s] = inf;
-#pragma unroll
-      for (int q = 0; q < Q; ++q)
-      {
-        Mpre[s][q] = inf;
-        Ipre[s][q] = inf;
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < Q; ++q) Mpre[0][q] = SB + BM[q];  // (BM still in registers here)
+    for (int s = 0; s < 5; ++s) Spre[s] = inf;
+    dcp_ring_row0(Mpre, Ipre, SB, BM); // (BM still in registers here)
     Spre[0] = lsel(l0, lf_splat(0.0f) + SN, lsel(l3, lneg(RR) + RR, inf));
     X = lsel(l3, lneg(RR), inf);
     E = inf;
@@ -262,11 +249,11 @@ template <int Q, int S, int TURNS = dcp_lazy_turns(Q), int NLDS = 0, bool LATE =
     PackFold fold;
     if constexpr (STASH) pack_unstash_issue(fold); // back from LDS while the D chain runs
 
-    // D_l[k] = min(M_l[k-1] + MD[k], D_l[k-1] + DD[k]) (c-core/viterbi.c:538,553-580): serial inside a
-    // lane, then carried across lanes until no lane improves (the reference's lazy loop, :569-580)
+    // serial inside a lane, then carried across lanes until no lane improves (the reference's lazy loop,
+    // c-core/viterbi.c:569-580)
     D[0] = Msh0 + MD[0];
 #pragma unroll
-    for (int q = 1; q < Q; ++q) D[q] = lmin(M[q - 1] + MD[q], D[q - 1] + DD[q]);
+    for (int q = 1; q < Q; ++q) D[q] = dcp_delete(M[q - 1], MD[q], D[q - 1], DD[q]);
     // (the separators' DD is +inf: nothing is carried from one group into the next)
     lf Dsh0 = dcp_lazy_turns_carry<Q, TURNS>(D, DD); // (unshifted yet)
 
@@ -289,8 +276,8 @@ template <int Q, int S, int TURNS = dcp_lazy_turns(Q), int NLDS = 0, bool LATE =
       lf const Ml = q ? M[q ? q - 1 : 0] : Msh0;
       lf const Il = q ? I[q ? q - 1 : 0] : Ish0;
       lf const Dl = q ? D[q ? q - 1 : 0] : Dsh0;
-      Mpre[P][q] = lmin3(B + BM[q], Ml + MM[q], lmin(Il + IM[q], Dl + DM[q]));
-      Ipre[P][q] = lmin(I[q] + II[q], M[q] + MI[q]);
+      Mpre[P][q] = dcp_fold_m(B, BM[q], Ml, MM[q], Il, IM[q], Dl, DM[q]);
+      Ipre[P][q] = dcp_fold_i(I[q], II[q], M[q], MI[q]);
     }
     Spre[P] = lmin(E + sa, X + sb);
     // the group's own last row: keep what its results are made of
