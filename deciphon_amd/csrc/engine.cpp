@@ -370,6 +370,7 @@ int dcp_hip_set_mode(struct dcp_hip *x, int multi_hits, int hmmer3_compat)
   if (outstanding_batches(x)) return refuse_outstanding(x);
   bool mh = multi_hits != 0, h3 = hmmer3_compat != 0;
   ++x->gen;
+  drop_calibration(x);
   if (x->mode_set && (mh != x->multi_hits || h3 != x->hmmer3_compat)) x->xt_rows = 0;
   x->multi_hits = mh;
   x->hmmer3_compat = h3;
@@ -382,6 +383,7 @@ int dcp_hip_set_xtrans_table(struct dcp_hip *x, int rows, float const *xt)
   if (!x || rows < 0 || (rows > 0 && !xt)) return DCP_EFUNCUSE;
   if (outstanding_batches(x)) return refuse_outstanding(x);
   ++x->gen;
+  drop_calibration(x);
   x->xt_override.assign((size_t)rows * DCP_XT_STRIDE, 0.0f);
   for (int r = 0; r < rows; ++r)
     memcpy(x->xt_override.data() + (size_t)r * DCP_XT_STRIDE, xt + (size_t)r * DCP_NUM_XTRANS,

@@ -510,6 +510,7 @@ int dcp_hip_set_gencode_sink(struct dcp_hip *x, int gencode_id, DcpGencodeSink *
   }
   for (HostProfile &hp : x->profiles) hp.gencode = gencode_id;
   ++x->gen;
+  drop_calibration(x);
   return 0;
 }
 
@@ -549,6 +550,7 @@ int dcp_hip_set_epsilon(struct dcp_hip *x, float epsilon)
   }
   for (HostProfile &hp : x->profiles) hp.epsilon = epsilon;
   ++x->gen;
+  drop_calibration(x);
   return 0;
 }
 

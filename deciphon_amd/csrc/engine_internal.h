@@ -1,5 +1,5 @@
 // engine_internal.h -- the engine's state and what its translation units share (engine.cpp, engine_profiles.cpp,
-// engine_hmm.cpp, engine_cost.cpp, engine_path.cpp).  Everything here but struct dcp_hip has C++ linkage in namespace dcp_engine, which
+// engine_hmm.cpp, engine_cost.cpp, engine_path.cpp, engine_calibrate.cpp).  Everything here but struct dcp_hip has C++ linkage in namespace dcp_engine, which
 // exports.map keeps inside the library.  What a staged window list holds (Staged, StagedPlan) and how it is planned:
 // stage_plan.h, host only.
 #pragma once
@@ -392,6 +392,15 @@ struct dcp_hip
   bool staged_ran = false; // a dcp_hip_run_staged with reps > 0 has filled d_out since the dcp_hip_stage
   std::vector<CostLaunch> last_cost_launches; // the schedule launch_cost_all ran last (dcp_hip_last_cost_launches)
 
+  // Calibration (engine_calibrate.cpp): the Gumbel location of profiles [0, calib_mu.size()) from the last
+  // dcp_hip_calibrate and the scores it left out of each fit, at calib_lambda.  A profile beyond them has none (NaN); so
+  // has every profile once something a score depends on has changed (drop_calibration).
+  std::vector<float> calib_mu;
+  std::vector<int32_t> calib_excluded;
+  float calib_lambda = NAN;
+  DevBuf<uint32_t> d_mu; // fp32 bits, as the fit kernel stores them
+  DevBuf<int32_t> d_excluded;
+
   // Input generation: moves with every accepted change of the profiles, sequences, mode or xtrans override.  The
   // staged list and the path results remember the generation they were made under; dcp_hip_run_staged /
   // _fetch_staged and dcp_hip_path_trellis (which recomputes) refuse once it has moved.
@@ -503,6 +512,15 @@ struct Stopwatch
 int stage(Pass const &ps, int n, dcp_hip_window const *w, ArenaKind arena_kind, Staged &st, hipStream_t origin = nullptr);
 DcpLaunch launch_args(Pass const &ps, StagedPlan const &st, int c);
 int launch_cost_all(Pass const &ps, StagedPlan const &st, hipStream_t origin = nullptr);
+
+// the scores are no longer what the profiles were calibrated on: dcp_hip_set_epsilon, _set_gencode, _set_mode,
+// _set_xtrans_table, _clear_profiles
+inline void drop_calibration(dcp_hip *x)
+{
+  x->calib_mu.clear();
+  x->calib_excluded.clear();
+  x->calib_lambda = NAN;
+}
 
 // batches begun and not ended
 inline int outstanding_batches(dcp_hip const *x) { return (x->outstanding[0] >= 0) + (x->outstanding[1] >= 0); }

@@ -376,6 +376,7 @@ void dcp_hip_clear_profiles(struct dcp_hip *x)
     return;
   }
   ++x->gen;
+  drop_calibration(x);
   x->pool_used = 0;
   x->profiles.clear();
   x->plan_profiles.clear();

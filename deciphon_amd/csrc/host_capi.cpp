@@ -1,5 +1,6 @@
 // host_capi.cpp -- C ABI of include/deciphon_host.h over dcp_db / host_logic / scan_walk / path_plan / stage_plan.
 #include "../../include/deciphon_host.h"
+#include "calibrate.h"
 #include "dcp_db.h"
 #include "dcp_errors.h"
 #include "dcp_types.h"
@@ -8,6 +9,7 @@
 #include "scan_walk.h"
 #include "stage_plan.h"
 
+#include <math.h>
 #include <string.h>
 #include <string>
 #include <vector>
@@ -409,5 +411,25 @@ int dcp_path_hit(int nsteps, int32_t const *state_ids, int32_t const *seqsizes, 
 void dcp_state_name_of(int state_id, char *name) { dcp_state_name(state_id, name); }
 int dcp_state_is_mute_id(int state_id) { return dcp_state_is_mute(state_id) ? 1 : 0; }
 float dcp_lrt_of(float null_loglik, float alt_loglik) { return dcp_lrt(null_loglik, alt_loglik); }
+
+// ---- the random reads of a calibration (calibrate.h) and the tail of the fitted distribution ----
+int dcp_random_thresholds(float const freq[4], uint32_t t[3])
+{
+  if (!t) return DCP_EFUNCUSE;
+  return dcp_random_thresholds_of(freq, t) ? 0 : DCP_EFUNCUSE;
+}
+
+int dcp_random_nt(uint64_t seed, uint32_t const t[3], int64_t first_idx, int64_t n, uint8_t *out)
+{
+  if (!t || first_idx < 0 || n < 0 || (n > 0 && !out)) return DCP_EFUNCUSE;
+  for (int64_t i = 0; i < n; ++i) out[i] = (uint8_t)dcp_random_base(seed, t[0], t[1], t[2], (uint64_t)first_idx + (uint64_t)i);
+  return 0;
+}
+
+double dcp_lrt_evalue(float lrt, float mu, float lambda, double z)
+{
+  if (isnan(mu)) return NAN;
+  return z * (-expm1(-exp(-(double)lambda * ((double)lrt - (double)mu))));
+}
 
 } // extern "C"

@@ -57,6 +57,9 @@ struct dcp_scan
   std::unique_ptr<DcpDecoderSource> db;
   int strands = DCP_STRANDS_PLUS; // dcp_scan_set_strands: what the next dcp_scan_run scans of every read
   DcpHmmDecoders *hmm = nullptr; // `db`, when dcp_scan_setup_hmm set it: the error rate moves with the tables (dcp_scan_set_epsilon)
+  // dcp_scan_set_evalue: the targets of the evalue column (<= 0: the sequences a run scans) and the limit of its rows.
+  // The calibration itself is the engine's (dcp_scan_calibrate), and goes with whatever changes its scores.
+  double evalue_z = 0, evalue_max = HUGE_VAL;
 };
 
 namespace
@@ -431,6 +434,24 @@ int dcp_scan_set_gencode(struct dcp_scan *x, int gencode_id)
   return 0;
 }
 
+int dcp_scan_calibrate(struct dcp_scan *x, int nseq, int len, uint64_t seed, float const freq[4], float lambda)
+{
+  if (!x) return raise(DCP_EFUNCUSE, __func__);
+  if (!x->eng) return raise(DCP_EFUNCUSE, __func__, "dcp_scan_setup has not succeeded");
+  if (int const rc = dcp_hip_calibrate(x->eng, nseq, len, seed, freq, lambda)) return raise(rc, __func__, dcp_hip_strerror(x->eng));
+  return 0;
+}
+
+int dcp_scan_set_evalue(struct dcp_scan *x, double z, double max)
+{
+  if (!x || isnan(z) || isnan(max)) return raise(DCP_EFUNCUSE, __func__);
+  x->evalue_z = z;
+  x->evalue_max = max;
+  return 0;
+}
+
+float dcp_scan_profile_mu(struct dcp_scan const *x, int i) { return x && x->eng ? dcp_hip_profile_mu(x->eng, i) : NAN; }
+
 int dcp_scan_set_strands(struct dcp_scan *x, int strands)
 {
   // no engine is asked: the mode belongs to the scan and reaches the GPU with the reads of the next run
@@ -522,7 +543,9 @@ int dcp_scan_run(struct dcp_scan *x, struct dcp_batch *batch, char const *produc
   int64_t const budget = knobs.product_mb >= 1.0e12 ? INT64_MAX : knobs.product_mb > 0 ? (int64_t)(knobs.product_mb * 1048576.0) : 0;
   x->runs.reset(new DcpProductRuns(product_dir, budget, both));
   DropRuns drop{x};
-  DcpScanRows rows(x->eng, x->db.get(), x->index_offset, x->abc_name.c_str(), batch, x->runs.get(), both); // (after all that its threads read)
+  // Z of the evalue column: the sequences this run scans (HMMER's Z, the number of targets) unless the caller set one
+  DcpEvalueRule const evalue{x->evalue_z > 0 ? x->evalue_z : (double)nseq, x->evalue_max};
+  DcpScanRows rows(x->eng, x->db.get(), x->index_offset, x->abc_name.c_str(), batch, x->runs.get(), both, evalue); // (after all that its threads read)
   Run r{x, walk, rows, ph};
   if (knobs.speculate)
   {

@@ -4,6 +4,7 @@
 #include "parallel_for.h"
 #include "press_kernel.h"
 #include <algorithm>
+#include <math.h>
 #include <stdio.h>
 #include <string.h>
 
@@ -18,15 +19,17 @@ namespace
 // column of a scan of both strands, 0 for none.
 std::string format_row(dcp_batch::Seq const &seq, std::string const &text, uint8_t const *nt, char strand, int window,
                        int wstart, int wstop, DcpHit const &hit, char const *accession, char const *abc, float lrt,
-                       uint32_t const *steps, DcpDecoder const &dec, std::atomic<int> *rc)
+                       double evalue, uint32_t const *steps, DcpDecoder const &dec, std::atomic<int> *rc)
 {
   // a step: state id in the low 16 bits, emission length above (dcp_hip_path_steps_packed)
   auto step_id = [&](int i) { return (int)(steps[i] & 0xffffu); };
   auto step_size = [&](int i) { return (int)(steps[i] >> 16); };
   char const *sym = seq.has_u ? "ACGU" : "ACGT";
-  char head[256];
-  snprintf(head, sizeof head, "%ld\t%d\t%d\t%d\t%d\t%d\t%d\t%s\t%s\t%.1f\tnan\t", seq.id, window, wstart, wstop, 0,
-           hit.hit_start, hit.hit_stop, accession, abc, (double)lrt);
+  // the evalue column: "nan" for a profile that is not calibrated, the literal string as ever; else c-core/product_thread.c:60
+  char head[256], ev[32] = "nan";
+  if (!isnan(evalue)) snprintf(ev, sizeof ev, "%.2g", evalue);
+  snprintf(head, sizeof head, "%ld\t%d\t%d\t%d\t%d\t%d\t%d\t%s\t%s\t%.1f\t%s\t", seq.id, window, wstart, wstop, 0,
+           hit.hit_start, hit.hit_stop, accession, abc, (double)lrt, ev);
   std::string out = head;
   out.reserve(out.size() + (size_t)(hit.end_step - hit.begin_step) * 12);
   int pos = 0;
@@ -133,8 +136,9 @@ int DcpHmmDecoders::read_decoder(int i, DcpDecoder &x) const
 }
 
 DcpScanRows::DcpScanRows(dcp_hip const *eng, DcpDecoderSource const *db, int index_offset, char const *abc,
-                         dcp_batch const *batch, DcpProductRuns *runs, bool both_strands)
+                         dcp_batch const *batch, DcpProductRuns *runs, bool both_strands, DcpEvalueRule evalue)
     : eng_(eng), db_(db), index_offset_(index_offset), abc_(abc), batch_(batch), runs_(runs), both_(both_strands),
+      evalue_(evalue),
       decoders_((size_t)std::max(dcp_hip_num_profiles(eng), 0)), minus_(both_strands ? batch->seqs.size() : 0)
 {
 }
@@ -228,8 +232,16 @@ void DcpScanRows::format(std::vector<dcp_walk_hit> const &hits)
     });
     copied.set_value();
     std::vector<DcpProductRuns::Row> out(jobs.size());
+    std::vector<uint8_t> dropped(jobs.size(), 0); // rows at or beyond the E-value limit (DcpEvalueRule)
+    float const lambda = dcp_hip_calib_lambda(eng_);
     dcp_parallel_for(jobs.size(), 16, 8, 1, [&](size_t k) {
       Job const &j = jobs[k];
+      double const evalue = dcp_lrt_evalue(j.at.lrt, dcp_hip_profile_mu(eng_, j.at.profile), lambda, evalue_.z);
+      if (evalue >= evalue_.max) // (never for NaN: a profile that is not calibrated keeps its rows)
+      {
+        dropped[k] = 1;
+        return;
+      }
       LazyDecoder &ld = *j.dec;
       fill(ld, j.at.profile); // decoder_setup, c-core/decoder.c:21-36, once per profile
       if (ld.rc)
@@ -247,9 +259,17 @@ void DcpScanRows::format(std::vector<dcp_walk_hit> const &hits)
                                    format_row(seq, m ? m->text : seq.text, m ? m->nt.data() : seq.nt.data(),
                                               !both_ ? (char)0 : minus ? '-' : '+', j.at.window, j.at.start, j.at.stop, j.hit,
                                               dcp_hip_profile_accession(eng_, j.at.profile), abc_.c_str(), j.at.lrt,
-                                              j.steps, ld.dec, &decode_rc_)};
+                                              evalue, j.steps, ld.dec, &decode_rc_)};
     });
     if (decode_rc_) return; // (the scan fails: its rows are not written)
+    size_t kept = 0;
+    for (size_t k = 0; k < out.size(); ++k)
+      if (!dropped[k])
+      {
+        if (kept != k) out[kept] = std::move(out[k]);
+        ++kept;
+      }
+    out.resize(kept);
     if (int const rc = runs_->add(std::move(out)))
     {
       int expected = 0;

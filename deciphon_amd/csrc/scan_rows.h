@@ -1,6 +1,6 @@
 // scan_rows.h -- from the walked paths of a scan to products.tsv: replaces the products.tsv writer (c-core/product.c,
-// product_thread.c) and the quasi-codon decoding of the match column (c-core/decoder.c, match.c), minus HMMER (the
-// evalue column is "nan" and HMMER's row filter does not run).
+// product_thread.c) and the quasi-codon decoding of the match column (c-core/decoder.c, match.c), minus HMMER: the
+// evalue column is "nan" and no row is dropped, unless the profiles are calibrated (DcpEvalueRule).
 #pragma once
 #include "../../include/deciphon_hip.h"
 #include "../../include/deciphon_host.h"
@@ -10,6 +10,7 @@
 #include "product_runs.h"
 #include <atomic>
 #include <future>
+#include <math.h>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -68,6 +69,16 @@ private:
   size_t at_profile = 0, at_node = 0; // where the next entry of a dcp_scan_set_gencode goes
 };
 
+// The evalue column of a run and its row filter.  A row whose profile has a Gumbel location (dcp_hip_profile_mu is not
+// NaN) prints E = dcp_lrt_evalue(lrt, mu, the engine's lambda, z) with %.2g, as c-core/product_thread.c:60 prints
+// HMMER's, and is left out when E >= max (c-core/thread.c:192-201 drops E >= 1).  Any other row prints "nan" and stays.
+// The walk has moved on by then either way: last_hit_pos does not depend on it (thread.c:162 against thread.c:201).
+struct DcpEvalueRule
+{
+  double z = 1;              // targets: the sequences the run scans, or what dcp_scan_set_evalue was given
+  double max = HUGE_VAL;     // +inf: every row stays
+};
+
 // The rows of one dcp_scan_run.  Per path batch, in this order: warm_decoders, wait_steps_copied, dcp_hip_path, spans,
 // format.  Its threads read the batch's sequences, the scan's decoder source and the engine -- the profiles' accessions, and
 // the step buffers of the last dcp_hip_path until they hold copies (wait_steps_copied) -- and hand their rows to
@@ -81,7 +92,7 @@ public:
   // first, then reversed and complemented -- that is the definition of the minus strand), built once per read that has
   // a minus hit; its coordinates are the walk's, on that strand.
   DcpScanRows(dcp_hip const *eng, DcpDecoderSource const *db, int index_offset, char const *abc, dcp_batch const *batch,
-              DcpProductRuns *runs, bool both_strands = false);
+              DcpProductRuns *runs, bool both_strands = false, DcpEvalueRule evalue = DcpEvalueRule());
   ~DcpScanRows() { join(); }
   // decoder_setup (c-core/decoder.c:21-36) for the profiles of this batch -- reading a profile's distributions out of
   // the database and exponentiating them (a fraction of a millisecond, times hundreds of profiles with hits) -- by host
@@ -141,6 +152,7 @@ private:
   dcp_batch const *batch_;
   DcpProductRuns *runs_;
   bool both_;
+  DcpEvalueRule evalue_;
   int64_t batches_ = 0;                                // with hits, so far
   std::vector<std::shared_ptr<LazyDecoder>> decoders_; // by local profile
   mutable std::vector<MinusStrand> minus_;             // by read, on both strands (empty otherwise)

@@ -102,3 +102,16 @@ hipError_t dcp_launch_encode(unsigned char const *nt, int64_t const *seq_off, in
 // in nt), row_off[2 nreads + 1] (the rows in front of each sequence)
 hipError_t dcp_launch_encode_strands(unsigned char const *nt, int64_t const *seq_off, int64_t const *row_off, int nreads,
                                      int64_t max_len, DcpCodeRow *rows, hipStream_t stream);
+
+// ---- calibrate.hip ----
+// the code rows of nseq random sequences of len nucleotides (calibrate.h states them), len + 1 rows each, back to back
+// from rows[0]: no nt buffer, no loads
+hipError_t dcp_launch_random_code_rows(int nseq, int len, uint64_t seed, uint32_t const t[3], DcpCodeRow *rows,
+                                       hipStream_t stream);
+// Gumbel location of nprof profiles by maximum likelihood at fixed lambda, one wavefront per profile: profile p's n score
+// pairs {null, alt} are out[2 n p ..); x = -2 * (null_loglik - alt_loglik) as dcp_lrt_filter_kernel forms it, non-finite
+// x left out and counted in excluded[p]; mu_bits[p] = the fp32 bits of
+//   m - (1 / lambda) * log((1 / n') * sum exp(-lambda * (x - m))),  m = min x,  over the n' kept scores, summed in fp64
+// (every term <= 1); NaN when n' = 0.
+hipError_t dcp_launch_gumbel_fit(float const *out, int nprof, int n, float lambda, uint32_t *mu_bits, int32_t *excluded,
+                                 hipStream_t stream);

@@ -89,6 +89,13 @@ def load_library() -> C.CDLL:
     L.dcp_hip_set_sequences_strands.argtypes = [vp, i32, vp, vp, i32]
     L.dcp_hip_num_sequences.argtypes = [vp]
     L.dcp_hip_code_rows_read.argtypes = [vp, i32, vp, C.c_int64]
+    L.dcp_hip_set_random_sequences.argtypes = [vp, i32, i32, C.c_uint64, vp]
+    L.dcp_hip_calibrate.argtypes = [vp, i32, i32, C.c_uint64, vp, C.c_float]
+    L.dcp_hip_profile_mu.argtypes = [vp, i32]
+    L.dcp_hip_profile_mu.restype = C.c_float
+    L.dcp_hip_profile_calib_excluded.argtypes = [vp, i32]
+    L.dcp_hip_calib_lambda.argtypes = [vp]
+    L.dcp_hip_calib_lambda.restype = C.c_float
     L.dcp_hip_set_mode.argtypes = [vp, i32, i32]
     L.dcp_hip_set_xtrans_table.argtypes = [vp, i32, vp]
     L.dcp_hip_xtrans.argtypes = [i32, i32, i32, vp]
@@ -291,6 +298,43 @@ class Engine:
         nt = np.ascontiguousarray(nt)
         self._check(self.lib.dcp_hip_set_sequences_strands(self.h, len(seqs), _p(nt), _p(off), code))
         self._seq_lens = [len(s) for s in seqs for _ in range(2 if code == STRANDS["both"] else 1)]
+
+    @staticmethod
+    def _freq(freq):
+        """freq[4] for the C call: None (uniform) stays NULL."""
+        if freq is None:
+            return None, None
+        f = _f32(freq).reshape(4)
+        return f, _p(f)
+
+    def set_random_sequences(self, nseq: int, length: int, seed: int, freq=None) -> None:
+        """nseq random sequences of `length` nucleotides whose code rows the GPU writes from a counter-based generator
+        (dcp_hip_set_random_sequences): no read exists on the host or crosses the bus.  host.random_nt gives the same
+        nucleotides.  freq: frequencies of A, C, G, T (None: uniform)."""
+        keep, ptr = self._freq(freq)
+        self._check(self.lib.dcp_hip_set_random_sequences(self.h, int(nseq), int(length), int(seed) & (2**64 - 1), ptr))
+        self._seq_lens = [int(length)] * int(nseq)
+
+    def calibrate(self, nseq: int, length: int, seed: int, freq=None, lam: float = 0.5) -> None:
+        """Scores every profile against nseq random sequences of `length` nucleotides and fits the location mu of a
+        Gumbel distribution of lrt at fixed lambda, all on the GPU (dcp_hip_calibrate).  lam = 0.5 is HMMER's conjectured
+        ln 2 per bit, lrt being twice the log-odds in nats.  The random sequences stay resident: set yours again."""
+        keep, ptr = self._freq(freq)
+        self._check(self.lib.dcp_hip_calibrate(self.h, int(nseq), int(length), int(seed) & (2**64 - 1), ptr, float(lam)))
+        self._seq_lens = [int(length)] * int(nseq)
+
+    def profile_mu(self, i: int) -> np.float32:
+        """The Gumbel location of profile i from the last calibrate(); NaN when it has none."""
+        return np.float32(self.lib.dcp_hip_profile_mu(self.h, int(i)))
+
+    def profile_calib_excluded(self, i: int) -> int:
+        """Scores of profile i that the fit of the last calibrate() left out as not finite."""
+        return int(self.lib.dcp_hip_profile_calib_excluded(self.h, int(i)))
+
+    @property
+    def calib_lambda(self) -> float:
+        """lambda of the calibration in force; NaN without one."""
+        return float(self.lib.dcp_hip_calib_lambda(self.h))
 
     @property
     def num_sequences(self) -> int:

@@ -96,6 +96,10 @@ def _lib():
     L.dcp_state_is_mute_id.argtypes = [i32]
     L.dcp_lrt_of.argtypes = [C.c_float, C.c_float]
     L.dcp_lrt_of.restype = C.c_float
+    L.dcp_random_thresholds.argtypes = [vp, vp]
+    L.dcp_random_nt.argtypes = [C.c_uint64, vp, C.c_int64, C.c_int64, vp]
+    L.dcp_lrt_evalue.argtypes = [C.c_float, C.c_float, C.c_float, C.c_double]
+    L.dcp_lrt_evalue.restype = C.c_double
     L.dcp_hmm_open.argtypes = [C.c_char_p, i32, C.POINTER(vp)]
     L.dcp_hmm_close.argtypes = [vp]
     L.dcp_hmm_close.restype = None
@@ -710,6 +714,35 @@ def state_is_mute(state_id: int) -> bool:
 
 def lrt(null_loglik, alt_loglik) -> np.float32:
     return np.float32(_lib().dcp_lrt_of(float(null_loglik), float(alt_loglik)))
+
+
+def random_thresholds(freq=None) -> np.ndarray:
+    """The three cumulative thresholds of the random reads' generator from the frequencies of A, C, G, T (None:
+    uniform), uint32 [3] (dcp_random_thresholds)."""
+    t = np.zeros(3, np.uint32)
+    f = None if freq is None else np.ascontiguousarray(freq, np.float32).reshape(4)
+    rc = _lib().dcp_random_thresholds(None if f is None else f.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p))
+    if rc:
+        raise HipError(rc)
+    return t
+
+
+def random_nt(seed: int, n: int, first_idx: int = 0, freq=None) -> np.ndarray:
+    """Nucleotides first_idx .. first_idx + n of the random reads of `seed` (dcp_random_nt), uint8 indices 0..3: sequence
+    s of a set of sequences of `length` nucleotides is random_nt(seed, length, s * length, freq), what
+    Engine.set_random_sequences leaves as code rows."""
+    t = random_thresholds(freq)
+    out = np.zeros(int(n), np.uint8)
+    rc = _lib().dcp_random_nt(int(seed) & (2**64 - 1), t.ctypes.data_as(C.c_void_p), int(first_idx), int(n),
+                              out.ctypes.data_as(C.c_void_p))
+    if rc:
+        raise HipError(rc)
+    return out
+
+
+def lrt_evalue(lrt, mu, lam, z) -> float:
+    """z * (1 - exp(-exp(-lam (lrt - mu)))), the Gumbel tail as dcp_lrt_evalue states it; NaN when mu is."""
+    return float(_lib().dcp_lrt_evalue(float(lrt), float(mu), float(lam), float(z)))
 
 
 def decode_quasi_codon(epsilon: float, nucltp, codonm, nt) -> np.ndarray:

@@ -7,6 +7,8 @@ import ctypes as C
 import dataclasses
 import os
 
+import numpy as np
+
 from .hip import HipError as DeciphonError
 from .hip import load_library, strands_code
 
@@ -29,6 +31,10 @@ def _lib():
     L.dcp_scan_setup_hmm.argtypes = [vp, C.c_char_p, i32, C.c_float, C.c_bool, C.c_bool, _CALLBACK, vp]
     L.dcp_scan_set_epsilon.argtypes = [vp, C.c_float]
     L.dcp_scan_set_gencode.argtypes = [vp, i32]
+    L.dcp_scan_calibrate.argtypes = [vp, i32, i32, C.c_uint64, vp, C.c_float]
+    L.dcp_scan_set_evalue.argtypes = [vp, C.c_double, C.c_double]
+    L.dcp_scan_profile_mu.argtypes = [vp, i32]
+    L.dcp_scan_profile_mu.restype = C.c_float
     L.dcp_scan_set_strands.argtypes = [vp, i32]
     L.dcp_scan_strands.argtypes = [vp]
     L.dcp_scan_partition_range.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
@@ -175,6 +181,25 @@ class Scan:
         rows of a fresh from_hmm at `gencode` and the error rate the scan is at.  Not while run() is running."""
         if rc := self._lib.dcp_scan_set_gencode(self._cscan, int(gencode)):
             raise DeciphonError(rc)
+
+    def calibrate(self, nseq: int = 200, length: int = 300, seed: int = 42, freq=None, lam: float = 0.5):
+        """Calibrates every profile on nseq random reads of `length` nucleotides, on the GPU (dcp_scan_calibrate): later
+        runs print an E-value in the evalue column instead of nan.  lam = 0.5 is HMMER's conjectured ln 2 per bit, lrt
+        being twice the log-odds in nats.  Wanted again after set_epsilon or set_gencode.  Not while run() is running."""
+        f = None if freq is None else np.ascontiguousarray(freq, np.float32).reshape(4)
+        ptr = None if f is None else f.ctypes.data_as(C.c_void_p)
+        if rc := self._lib.dcp_scan_calibrate(self._cscan, int(nseq), int(length), int(seed) & (2**64 - 1), ptr, float(lam)):
+            raise DeciphonError(rc)
+
+    def set_evalue(self, z: float = 0.0, max: float = float("inf")):
+        """Z of the evalue column (<= 0: the sequences a run scans, reads x strands) and the limit of its rows: a
+        calibrated run leaves out rows with E >= max (the reference's rule is max = 1).  dcp_scan_set_evalue."""
+        if rc := self._lib.dcp_scan_set_evalue(self._cscan, float(z), float(max)):
+            raise DeciphonError(rc)
+
+    def profile_mu(self, i: int) -> np.float32:
+        """The Gumbel location of this scan's profile i; NaN when the scan is not calibrated."""
+        return np.float32(self._lib.dcp_scan_profile_mu(self._cscan, int(i)))
 
     def run(self, snap, batch: Batch):
         self.interrupted = False

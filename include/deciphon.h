@@ -8,8 +8,12 @@
  *    accepted and ignored (one engine drives one GPU), `cache` likewise (profiles
  *    are always resident in HBM).
  *  - HMMER rescoring (the h3daemon TCP client of c-core/hmmer.c) is out of scope:
- *    `port` is ignored, no row is dropped for lack of a HMMER hit, the `evalue`
- *    column holds `nan` and no hmmer/ directory with .h3r files is written.
+ *    `port` is ignored, no row is dropped for lack of a HMMER hit and no hmmer/
+ *    directory with .h3r files is written.  The `evalue` column holds `nan` -- unless
+ *    the scan is calibrated (dcp_scan_calibrate, below): it then holds the E-value of
+ *    the row's own lrt under a Gumbel distribution fitted to the profile's scores on
+ *    random reads, as HMMER calibrates its own scores, and rows at or beyond a limit
+ *    are left out (dcp_scan_set_evalue).  That is not HMMER's E-value of the hit.
  *  - the codon and amino fields of the `match` column come from a restatement of third-party
  *    imm's imm_frame_cond_decode (csrc/host_logic.h), pinned by the reference's committed
  *    products.tsv only.
@@ -184,6 +188,24 @@ int dcp_scan_set_epsilon(struct dcp_scan *, float epsilon);
  * held -- all checked before the GPU is touched, the scan left as it was.  Not to be called while dcp_scan_run runs on
  * that scan.  The rows of the last run (dcp_scan_product) stay valid. */
 int dcp_scan_set_gencode(struct dcp_scan *, int gencode_id);
+/* Not in the reference, whose E-values come from a HMMER daemon: the profiles of a scan calibrated on the GPU
+ * (dcp_hip_calibrate, include/deciphon_hip.h, whose arguments and error codes these are): every profile is scored
+ * against nseq random reads of len nucleotides (seed, freq[4] = frequencies of A, C, G, T or NULL for uniform:
+ * csrc/calibrate.h) and the location mu of a Gumbel distribution of lrt is fitted at fixed lambda.  lrt is twice the
+ * log-odds in nats: pass lambda = 0.5, HMMER's conjectured ln 2 per bit (what has been measured).
+ * Valid after any setup and between runs, DCP_EFUNCUSE before; wanted again after dcp_scan_set_epsilon or
+ * dcp_scan_set_gencode, which make the scan uncalibrated again.  dcp_scan_profile_mu: mu of local profile i, NaN when it
+ * is not calibrated (or for a bad index or NULL).
+ * A calibrated scan prints dcp_lrt_evalue(row lrt, mu of its profile, lambda, Z) (include/deciphon_host.h) with %.2g in
+ * the evalue column, as c-core/product_thread.c:60 prints HMMER's, and leaves out the rows with E >= max.
+ * dcp_scan_set_evalue: z <= 0, the default, makes Z the number of sequences the run scans -- its reads, twice that on
+ * both strands: HMMER's Z, the number of targets; max is +inf by default, and the reference's rule is max = 1
+ * (c-core/thread.c:192-201).  The window walk does not depend on the filter (thread.c:162 against thread.c:201): the
+ * rows kept are, apart from that column, a subset in order of the unfiltered rows.  DCP_EFUNCUSE for NULL or NaN.
+ * A scan that is not calibrated writes `nan` and keeps every row, whatever max is. */
+int dcp_scan_calibrate(struct dcp_scan *, int nseq, int len, uint64_t seed, float const freq[4], float lambda);
+int dcp_scan_set_evalue(struct dcp_scan *, double z, double max);
+float dcp_scan_profile_mu(struct dcp_scan const *, int i);
 /* Not in the reference, which scans every read in the orientation it was given and no other (its GFF writer has
  * strand "+" for every hit): DCP_STRANDS_BOTH makes every later dcp_scan_run scan both strands of every read.  The reads
  * go to the GPU once; the code rows of the reverse complements are written there (dcp_hip_set_sequences_strands), and

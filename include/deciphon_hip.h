@@ -160,6 +160,37 @@ int dcp_hip_num_sequences(struct dcp_hip const *);
  * must be its length + 1. */
 int dcp_hip_code_rows_read(struct dcp_hip const *, int seq, uint32_t *out, int64_t rows);
 
+/* Not in the reference: a dcp_hip_set_sequences whose reads exist nowhere -- nseq random sequences of len nucleotides
+ * each, whose code rows a kernel writes straight from a counter-based generator (csrc/calibrate.h states it;
+ * dcp_random_nt, include/deciphon_host.h, gives the same nucleotides on the host).  freq[4]: the frequencies of A, C, G,
+ * T, normalised by their sum; NULL: uniform.  The contract is that of dcp_hip_set_sequences: a change of the inputs,
+ * DCP_EFUNCUSE while batches are outstanding, everything checked before anything is replaced -- nseq >= 0, len >= 0, a
+ * freq that is not negative, NaN or all zero, nseq * (len + 1) code rows below 2^32, each DCP_EFUNCUSE.  Afterwards
+ * dcp_hip_num_sequences, dcp_hip_code_rows_read and every cost and path entry point work as on nseq plain reads. */
+int dcp_hip_set_random_sequences(struct dcp_hip *, int nseq, int len, uint64_t seed, float const freq[4]);
+
+/* ---- calibration: what HMMER's p7_Calibrate does for its own scores, for lrt ------------------------------------
+ * Sets the random sequences above and scores every committed profile against every whole sequence under the mode and
+ * special transitions in force -- windows {p, s, 0, len}, profile-major, through the same stage, plan and launch path
+ * as dcp_hip_cost, in chunks of whole profiles of at most DECIPHON_HIP_CALIB_WINDOWS windows (default: the 4 Mi of a
+ * scan's chunk; one profile at the least) -- and fits, per profile, the location mu of a Gumbel distribution of
+ * lrt = -2 * (null_loglik - alt_loglik) with lambda fixed, by maximum likelihood, on the GPU:
+ *   mu = m - (1 / lambda) * log((1 / n') * sum exp(-lambda * (x_i - m))),  m = min x_i,
+ * over the n' finite scores (fp64 sum, mu kept as fp32); the others are counted (dcp_hip_profile_calib_excluded), and
+ * n' = 0 gives NaN.  lrt is twice the log-odds in nats, so HMMER's conjecture lambda = ln 2 per bit is lambda = 0.5:
+ * the value to pass unless a measurement says otherwise.
+ * DCP_EFUNCUSE, with nothing changed: batches outstanding, nseq < 1, len < 1, a bad freq, lambda <= 0, infinite or
+ * NaN, profiles not committed, no dcp_hip_set_mode yet.  Without profiles it sets the sequences and returns 0.  The
+ * random sequences stay resident: the caller sets its reads again.  DECIPHON_HIP_TIMING prints one line
+ * "dcp_hip_calibrate:" with profiles, windows, cells and the seconds of generation, cost pass and fit.
+ * dcp_hip_profile_mu: NaN for a profile never calibrated, a bad index or NULL.  mu of every profile goes back to NaN on
+ * whatever changes a score: dcp_hip_set_epsilon, _set_gencode, _set_mode, _set_xtrans_table, _clear_profiles; profiles
+ * added after a calibration have none.  dcp_hip_calib_lambda: the lambda of the calibration in force, NaN without. */
+int dcp_hip_calibrate(struct dcp_hip *, int nseq, int len, uint64_t seed, float const freq[4], float lambda);
+float dcp_hip_profile_mu(struct dcp_hip const *, int i);
+int dcp_hip_profile_calib_excluded(struct dcp_hip const *, int i);
+float dcp_hip_calib_lambda(struct dcp_hip const *);
+
 /* ---- special transitions (replaces work_reset -> xtrans_setup, c-core/work.c:47-51) ---- */
 int dcp_hip_set_mode(struct dcp_hip *, int multi_hits, int hmmer3_compat);
 /* Overrides the special-transition costs for amino lengths 0..rows-1 with the
@@ -177,7 +208,7 @@ void dcp_hip_xtrans(int seq_size, int multi_hits, int hmmer3_compat, float xt[DC
  *
  * The inputs: every accepted call of dcp_hip_add_profile, _add_protein, _load_dcp, _load_hmm, _set_epsilon and
  * _set_gencode (with profiles resident), _commit_profiles,
- * _clear_profiles, _set_sequences, _set_mode or _set_xtrans_table changes them, even one that sets what was
+ * _clear_profiles, _set_sequences, _set_random_sequences, _calibrate, _set_mode or _set_xtrans_table changes them, even one that sets what was
  * there already (a call refused for outstanding batches or for its arguments changes nothing).  Two things
  * outlive a call and are tied to the inputs they were made from: the staged window list (dcp_hip_stage) and the
  * trellis of the last dcp_hip_path, which is computed only when asked for.  Once the inputs have changed,

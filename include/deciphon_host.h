@@ -261,6 +261,24 @@ int dcp_state_is_mute_id(int state_id);
 /* lrt (c-core/lrt.h:6-9) */
 float dcp_lrt_of(float null_loglik, float alt_loglik);
 
+/* ---- the random reads of dcp_hip_set_random_sequences / dcp_hip_calibrate (csrc/calibrate.h is the one statement, for
+ * the host and the kernel).  Nucleotide i of sequence s of a set of sequences of len nucleotides has the 64-bit index
+ * idx = s * len + i, and
+ *   z = seed + (idx + 1) * 0x9E3779B97F4A7C15 (mod 2^64);  z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *   z = (z ^ z >> 27) * 0x94D049BB133111EB;  u = (z ^ z >> 31) >> 32;  base = (u >= t[0]) + (u >= t[1]) + (u >= t[2])
+ * -- splitmix64 addressed by position.  A seed gives the same reads in every later version.
+ * dcp_random_thresholds: t[j] = min(floor(cum_j * 2^32), 2^32 - 1) from the four frequencies (NULL: uniform),
+ * normalised by their sum, in double.  A frequency of 0 leaves its base no value of u (base 3 behind the clamp: the one
+ * value u = 2^32 - 1).  DCP_EFUNCUSE for a negative, NaN, infinite or all-zero freq, or NULL t.
+ * dcp_random_nt: out[i] = the base at index first_idx + i, i < n.  DCP_EFUNCUSE for NULL, first_idx < 0 or n < 0. */
+int dcp_random_thresholds(float const freq[4], uint32_t t[3]);
+int dcp_random_nt(uint64_t seed, uint32_t const t[3], int64_t first_idx, int64_t n, uint8_t *out);
+/* The E-value of a row: the tail of the Gumbel distribution (mu, lambda) a calibration fitted to its profile
+ * (dcp_hip_calibrate, include/deciphon_hip.h), times z targets:
+ *   z * (-expm1(-exp(-(double)lambda * ((double)lrt - mu))))
+ * -- the one place the tail is stated.  NaN when mu is NaN. */
+double dcp_lrt_evalue(float lrt, float mu, float lambda, double z);
+
 #ifdef __cplusplus
 }
 #endif
