@@ -1,15 +1,16 @@
-// engine.cpp -- device-resident state and the C ABI of include/deciphon_hip.h: the engine itself, its sequences and
-// mode, the upload of staged window lists and their launches.  What is staged and what a cost pass launches is decided in
-// stage_plan.cpp, host only (plan_stage, cost_schedule).  Profiles: engine_profiles.cpp, engine_hmm.cpp; cost passes:
-// engine_cost.cpp; path pass: engine_path.cpp; the state they share: engine_internal.h.
+// engine.cpp -- device-resident state and the C ABI of include/deciphon_hip.h: the engine itself, its mode, the upload
+// of staged window lists and their launches.  What is staged and what a cost pass launches is decided in
+// stage_plan.cpp, host only (plan_stage, cost_schedule).  Sequences: engine_sequences.cpp; profiles:
+// engine_profiles.cpp, engine_hmm.cpp; cost passes: engine_cost.cpp; path pass: engine_path.cpp; calibration:
+// engine_calibrate.cpp; the state they share: engine_internal.h.
 //
 // HBM layout (one engine = one GPU):
 //   pool      float[]          all profiles back to back; per profile
 //                              rows[1364][4+Kp] = {null, bg, 0, 0, match[0..Kp)} | trans[8][Kp],
 //                              Kp = 64*Q*W, padding = +inf (DcpProfileDev holds the offsets)
 //   profiles  DcpProfileDev[]
-//   code_rows DcpCodeRow[]     per sequence len+1 rows of 32 B (built on the GPU
-//                              from 1 B/nt by dcp_encode_kernel)
+//   code_rows DcpCodeRow[]     per sequence len+1 rows of 32 B (code_rows.h states a row; built on the GPU by
+//                              the kernels of code_rows.hip, from 1 B/nt or from a seed: engine_sequences.cpp)
 //   xt_table  float[S+1][16]   special transitions per amino length S (host-computed:
 //                              they need double-precision log, c-core/xtrans.c:26-45)
 //   problems  DcpProblem[]     sorted by (Q, profile) so that neighbouring
@@ -17,7 +18,6 @@
 //   out       float[]          (null, alt) per window
 //   arena     bytes            trellises of the path pass
 #include "engine_internal.h"
-#include <limits.h>
 
 namespace dcp_engine
 {
@@ -71,9 +71,9 @@ int stage(Pass const &ps, int n, dcp_hip_window const *w, ArenaKind arena_kind, 
   in.w = w;
   in.profiles = x->plan_profiles.data();
   in.nprofiles = (int)x->plan_profiles.size();
-  in.nseq = (int)x->seq_off.size() - 1;
-  in.seq_off = x->seq_off.data();
-  in.row_off = x->row_off.data();
+  in.nseq = x->seqs.count();
+  in.seq_off = x->seqs.seq_off.data();
+  in.row_off = x->seqs.row_off.data();
   in.arena = arena_kind;
   in.table_addr = x->table_addr.data(); // ARENA_TABLE: the addresses the caller placed (place_slice)
   in.pack = !(pack_env && pack_env[0] == '0');
@@ -107,7 +107,7 @@ DcpLaunch launch_args(Pass const &ps, StagedPlan const &st, int c)
   a.pool = x->d_pool.p;
   a.profiles = x->d_profiles.p;
   a.problems = ps.lists.d_problems.p + st.c_begin[c];
-  a.code_rows = x->d_rows.p;
+  a.code_rows = x->seqs.d_rows.p;
   a.xt_table = x->d_xt.p;
   a.out = ps.lists.d_out.p;
   a.arena = x->d_trellis.p;
@@ -147,7 +147,7 @@ int launch_cost_all(Pass const &ps, StagedPlan const &st, hipStream_t origin)
   int rc = fk.begin(origin);
   if (rc) return rc;
   WindowLists &B = ps.lists;
-  uint32_t const ncode_rows = (uint32_t)x->row_off.back();
+  uint32_t const ncode_rows = (uint32_t)x->seqs.code_rows();
   for (CostLaunch const &e : schedule)
   {
     Branch const &branch = (e.branch == BRANCH_NARROW ? x->narrow_branch : e.branch == BRANCH_PACK ? x->pack_branch : ps.on.cls_branch)[e.index];
@@ -250,8 +250,6 @@ struct dcp_hip *dcp_hip_new(int device)
     dcp_hip_del(x);
     return nullptr;
   }
-  x->seq_off.assign(1, 0);
-  x->row_off.assign(1, 0);
   return x;
 }
 
@@ -287,81 +285,6 @@ int dcp_hip_encode(char const *data, int64_t n, uint8_t *out)
 {
   if (n < 0 || (n > 0 && (!data || !out))) return DCP_EFUNCUSE;
   return dcp_encode_sequence(data, n, out);
-}
-
-// Plus strand: internal sequence i is read i.  Both: sequences 2s and 2s + 1 are read s and its reverse complement, which
-// exists only as code rows (dcp_encode_strands_kernel); seq_off and row_off count 2 nseq sequences, the device's copy of
-// the offsets stays the reads' (what the kernel walks nt by).
-int dcp_hip_set_sequences_strands(struct dcp_hip *x, int nseq, uint8_t const *nt, int64_t const *offsets, int strands)
-{
-  if (!x || nseq < 0 || !offsets || (nseq > 0 && !nt)) return DCP_EFUNCUSE;
-  if (strands != DCP_STRANDS_PLUS && strands != DCP_STRANDS_BOTH) return fail(x, DCP_EFUNCUSE, "strands must be DCP_STRANDS_PLUS or DCP_STRANDS_BOTH");
-  bool const both = strands == DCP_STRANDS_BOTH;
-  if (both && nseq > INT_MAX / 2) return fail(x, DCP_EFUNCUSE, "more than INT_MAX / 2 reads on both strands");
-  if (outstanding_batches(x)) return refuse_outstanding(x);
-  HIP_TRY(x, hipSetDevice(x->device), DCP_EFUNCUSE);
-  // everything is checked before anything is replaced: a refused call leaves the previous reads in force
-  int const per = both ? 2 : 1, nint = nseq * per; // internal sequences
-  std::vector<int64_t> seq_off((size_t)nint + 1), row_off((size_t)nint + 1);
-  int64_t max_len = 0, rows = 0, nts = 0;
-  if (offsets[0] != 0) return fail(x, DCP_EFUNCUSE, "offsets[0] must be 0");
-  for (int i = 0; i < nseq; ++i)
-  {
-    int64_t len = offsets[i + 1] - offsets[i];
-    if (len < 0) return fail(x, DCP_EFUNCUSE, "offsets must not decrease");
-    max_len = std::max(max_len, len);
-    for (int k = 0; k < per; ++k)
-    {
-      seq_off[(size_t)i * per + k] = nts;
-      row_off[(size_t)i * per + k] = rows;
-      nts += len;
-      rows += len + 1;
-    }
-  }
-  seq_off[(size_t)nint] = nts;
-  row_off[(size_t)nint] = rows;
-  int64_t const total = offsets[nseq];
-  for (int64_t i = 0; i < total; ++i)
-    if (nt[i] > 3) return fail(x, DCP_ESEQABC, "nucleotide index above 3");
-  ++x->gen;
-  x->seq_off = std::move(seq_off);
-  x->row_off = std::move(row_off);
-  HIP_TRY(x, hipStreamSynchronize(x->cost_set.stream), DCP_EFUNCUSE);
-  HIP_TRY(x, x->d_nt.reserve((size_t)std::max<int64_t>(total, 1)), DCP_ENOMEM);
-  HIP_TRY(x, x->d_seq_off.reserve((size_t)nseq + 1), DCP_ENOMEM);
-  HIP_TRY(x, x->d_row_off.reserve((size_t)nint + 1), DCP_ENOMEM);
-  HIP_TRY(x, x->d_rows.reserve((size_t)std::max<int64_t>(rows, 1)), DCP_ENOMEM);
-  if (total)
-    HIP_TRY(x, hipMemcpyAsync(x->d_nt.p, nt, (size_t)total, hipMemcpyHostToDevice, x->cost_set.stream), DCP_EFUNCUSE);
-  // (the caller's offsets: on one strand they are x->seq_off; the call waits for the copy before it returns)
-  HIP_TRY(x, hipMemcpyAsync(x->d_seq_off.p, offsets, ((size_t)nseq + 1) * sizeof(int64_t), hipMemcpyHostToDevice, x->cost_set.stream),
-          DCP_EFUNCUSE);
-  HIP_TRY(x, hipMemcpyAsync(x->d_row_off.p, x->row_off.data(), ((size_t)nint + 1) * sizeof(int64_t),
-                            hipMemcpyHostToDevice, x->cost_set.stream),
-          DCP_EFUNCUSE);
-  HIP_TRY(x, (both ? dcp_launch_encode_strands : dcp_launch_encode)(x->d_nt.p, x->d_seq_off.p, x->d_row_off.p, nseq, max_len,
-                                                                    x->d_rows.p, x->cost_set.stream),
-          DCP_EFUNCUSE);
-  HIP_TRY(x, hipStreamSynchronize(x->cost_set.stream), DCP_EFUNCUSE);
-  return 0;
-}
-
-int dcp_hip_set_sequences(struct dcp_hip *x, int nseq, uint8_t const *nt, int64_t const *offsets)
-{
-  return dcp_hip_set_sequences_strands(x, nseq, nt, offsets, DCP_STRANDS_PLUS);
-}
-
-int dcp_hip_num_sequences(struct dcp_hip const *x) { return x ? (int)x->seq_off.size() - 1 : 0; }
-
-int dcp_hip_code_rows_read(struct dcp_hip const *x, int seq, uint32_t *out, int64_t rows)
-{
-  if (!x || !out || seq < 0 || seq >= (int)x->seq_off.size() - 1) return DCP_EFUNCUSE;
-  int64_t const first = x->row_off[(size_t)seq];
-  if (rows != x->row_off[(size_t)seq + 1] - first) return DCP_EFUNCUSE;
-  // (dcp_hip_set_sequences_strands has waited for its kernel before it returned)
-  if (hipSetDevice(x->device) != hipSuccess) return DCP_EFUNCUSE;
-  if (hipMemcpy(out, x->d_rows.p + first, (size_t)rows * sizeof(DcpCodeRow), hipMemcpyDeviceToHost) != hipSuccess) return DCP_EFUNCUSE;
-  return 0;
 }
 
 int dcp_hip_set_mode(struct dcp_hip *x, int multi_hits, int hmmer3_compat)

@@ -1,44 +1,12 @@
-// engine_calibrate.cpp -- random reads whose code rows the device writes, and the calibration of the resident profiles on
-// them: a cost pass over profiles x random reads through the engine's own stage, plan and launch path, and a Gumbel fit
-// of every profile's scores (calibrate.hip).  The reads themselves: calibrate.h.
+// engine_calibrate.cpp -- the calibration of the resident profiles on random reads (install_random,
+// engine_sequences.cpp): a cost pass over profiles x random reads through the engine's own stage, plan and launch path,
+// and a Gumbel fit of every profile's scores (calibrate.hip).  The reads themselves: calibrate.h.
 #include "../../include/deciphon_host.h"
-#include "calibrate.h"
 #include "engine_internal.h"
 #include <limits.h>
 
 namespace
 {
-
-// what dcp_hip_set_random_sequences checks, before anything is replaced
-int check_random(dcp_hip *x, int nseq, int len, float const *freq, uint32_t t[3])
-{
-  if (outstanding_batches(x)) return refuse_outstanding(x);
-  if (nseq < 0 || len < 0) return fail(x, DCP_EFUNCUSE, "nseq and len must not be negative");
-  if (!dcp_random_thresholds_of(freq, t)) return fail(x, DCP_EFUNCUSE, "freq must hold four non-negative frequencies, not all zero");
-  if ((uint64_t)nseq * ((uint64_t)len + 1) >= ((uint64_t)1 << 32)) return fail(x, DCP_EFUNCUSE, "more than 2^32 - 1 code rows");
-  return 0;
-}
-
-// the checks have passed
-int set_random(dcp_hip *x, int nseq, int len, uint64_t seed, uint32_t const t[3])
-{
-  HIP_TRY(x, hipSetDevice(x->device), DCP_EFUNCUSE);
-  std::vector<int64_t> seq_off((size_t)nseq + 1), row_off((size_t)nseq + 1);
-  for (int64_t s = 0; s <= nseq; ++s)
-  {
-    seq_off[(size_t)s] = s * len;
-    row_off[(size_t)s] = s * ((int64_t)len + 1);
-  }
-  int64_t const rows = row_off[(size_t)nseq];
-  ++x->gen;
-  x->seq_off = std::move(seq_off);
-  x->row_off = std::move(row_off);
-  HIP_TRY(x, hipStreamSynchronize(x->cost_set.stream), DCP_EFUNCUSE);
-  HIP_TRY(x, x->d_rows.reserve((size_t)std::max<int64_t>(rows, 1)), DCP_ENOMEM);
-  HIP_TRY(x, dcp_launch_random_code_rows(nseq, len, seed, t, x->d_rows.p, x->cost_set.stream), DCP_EFUNCUSE);
-  HIP_TRY(x, hipStreamSynchronize(x->cost_set.stream), DCP_EFUNCUSE);
-  return 0;
-}
 
 // DECIPHON_HIP_CALIB_WINDOWS: the most windows of a calibration's cost pass (a chunk is whole profiles, one at the
 // least).  Unset: what a chunk of dcp_scan_run holds, DCP_SCAN_CHUNK_WINDOWS -- the list, its pinned copy and the
@@ -54,14 +22,6 @@ int64_t calib_windows()
 
 extern "C" {
 
-int dcp_hip_set_random_sequences(struct dcp_hip *x, int nseq, int len, uint64_t seed, float const freq[4])
-{
-  if (!x) return DCP_EFUNCUSE;
-  uint32_t t[3];
-  if (int rc = check_random(x, nseq, len, freq, t)) return rc;
-  return set_random(x, nseq, len, seed, t);
-}
-
 int dcp_hip_calibrate(struct dcp_hip *x, int nseq, int len, uint64_t seed, float const freq[4], float lambda)
 {
   if (!x) return DCP_EFUNCUSE;
@@ -76,7 +36,7 @@ int dcp_hip_calibrate(struct dcp_hip *x, int nseq, int len, uint64_t seed, float
     if (p.cls < 0 || p.cls >= DCP_NUM_CLASSES) return fail(x, DCP_ELARGECORESIZE, "profile outside every kernel class");
   Pass const ps = cost_pass(x);
   Stopwatch sw(ps.on.stream);
-  if (int rc = set_random(x, nseq, len, seed, t)) return rc;
+  if (int rc = install_random(x, nseq, len, seed, t)) return rc;
   if (nprof == 0) return 0;
   double const gen_ms = sw.lap();
   double cost_ms = 0, fit_ms = 0, cells = 0;

@@ -1,7 +1,7 @@
-// engine_internal.h -- the engine's state and what its translation units share (engine.cpp, engine_profiles.cpp,
-// engine_hmm.cpp, engine_cost.cpp, engine_path.cpp, engine_calibrate.cpp).  Everything here but struct dcp_hip has C++ linkage in namespace dcp_engine, which
-// exports.map keeps inside the library.  What a staged window list holds (Staged, StagedPlan) and how it is planned:
-// stage_plan.h, host only.
+// engine_internal.h -- the engine's state and what its translation units share (engine.cpp, engine_sequences.cpp,
+// engine_profiles.cpp, engine_hmm.cpp, engine_cost.cpp, engine_path.cpp, engine_calibrate.cpp).  Everything here but
+// struct dcp_hip has C++ linkage in namespace dcp_engine, which exports.map keeps inside the library.  What a staged
+// window list holds (Staged, StagedPlan) and how it is planned: stage_plan.h, host only.
 #pragma once
 #include "../../include/deciphon_hip.h"
 #include "dcp_db.h"
@@ -267,6 +267,20 @@ struct PathResult
   std::vector<uint32_t> owned;
 };
 
+// The sequences that windows name, as the engine holds them: internal sequence i has nucleotides seq_off[i] ..
+// seq_off[i + 1] and code rows row_off[i] .. row_off[i + 1], one more row than nucleotides, in d_rows.  Only
+// engine_sequences.cpp writes it, and the offsets become the engine's only once their rows are written: an install that
+// fails leaves none, {0}, so that every window is refused (check_window) instead of reading absent rows.
+struct Sequences
+{
+  std::vector<int64_t> seq_off{0}, row_off{0}; // [count() + 1]
+  DevBuf<unsigned char> d_nt;            // the reads as given, what the rows are made from (none for random sequences)
+  DevBuf<int64_t> d_seq_off, d_row_off;  // ... and the offsets the kernel walks them by
+  DevBuf<DcpCodeRow> d_rows;
+  int count() const { return (int)seq_off.size() - 1; }
+  int64_t code_rows() const { return row_off.back(); }
+};
+
 // a side stream for kernels that run beside others, and the event recorded behind its last launch (struct Fork)
 struct Branch
 {
@@ -343,11 +357,7 @@ struct dcp_hip
   // node, which do not depend on the translation table (80 bytes beside the 528 in HBM); [dist_used * 20].
   std::vector<float> lodds;
 
-  // sequences
-  std::vector<int64_t> seq_off, row_off;
-  DevBuf<unsigned char> d_nt;
-  DevBuf<int64_t> d_seq_off, d_row_off;
-  DevBuf<DcpCodeRow> d_rows;
+  Sequences seqs; // what dcp_hip_set_sequences*, _set_random_sequences installed last
 
   // mode
   bool mode_set = false;
@@ -529,6 +539,11 @@ inline int refuse_outstanding(dcp_hip *x)
 {
   return fail(x, DCP_EFUNCUSE, "cost batches are outstanding (dcp_hip_cost_hits_begin): end them first");
 }
+
+// engine_sequences.cpp, for dcp_hip_calibrate as well: what dcp_hip_set_random_sequences checks before anything is
+// replaced (t: the thresholds of freq, calibrate.h), and what it does once they have passed
+int check_random(dcp_hip *x, int nseq, int len, float const *freq, uint32_t t[3]);
+int install_random(dcp_hip *x, int nseq, int len, uint64_t seed, uint32_t const t[3]);
 
 // engine_profiles.cpp, for the loads of engine_hmm.cpp as well:
 // class, shape, padded size and cost-order shape of a profile of K positions (pool_off is left 0)

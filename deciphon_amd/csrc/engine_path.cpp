@@ -424,7 +424,7 @@ int path_run(Pass const &ps, int n, dcp_hip_window const *w)
   // every window is checked here, whichever pass takes it (path_literal indexes x->profiles before stage() looks)
   for (int i = 0; i < n; ++i)
   {
-    Refusal const bad = check_window(w[i], (int)x->profiles.size(), (int)x->seq_off.size() - 1, x->seq_off.data());
+    Refusal const bad = check_window(w[i], (int)x->profiles.size(), x->seqs.count(), x->seqs.seq_off.data());
     if (bad.code) return fail(x, bad.code, bad.what);
   }
   x->path_wins.assign(w, w + n);

@@ -1,6 +1,7 @@
 // host_logic.cpp -- see host_logic.h
 #include "host_logic.h"
 #include "../../include/deciphon_host.h"
+#include "code_rows.h"
 #include "dcp_errors.h"
 #include "dcp_states.h"
 
@@ -353,26 +354,17 @@ extern "C" int64_t dcp_window_count(int64_t seq_size, int core_size)
   return seq_size <= span ? 1 : 1 + (seq_size - span + step - 1) / step;
 }
 
-// The code rows of one read, on either strand: the statement the encode kernels are held to (viterbi_kernels.hip).
-// Row r of the strand's sequence y holds in c[t-1] the code of the t-mer y[r-t..r-1] (imm_eseq_get: off[t] +
-// sum y[i] 4^(t-1-i), the leftmost symbol the most significant digit), 0 where r < t; y = nt, or its reverse
-// complement y[i] = 3 - nt[n-1-i].
+// The code rows of one read, on either strand, by the statement the kernels are built from as well (code_rows.h;
+// code_rows.hip): the rows of the strand's sequence y = nt, or its reverse complement y[i] = 3 - nt[n-1-i].
 extern "C" int dcp_code_rows_of(uint8_t const *nt, int64_t n, int minus, uint32_t *rows)
 {
   if (n < 0 || (n > 0 && !nt) || !rows) return DCP_EFUNCUSE;
   for (int64_t i = 0; i < n; ++i)
     if (nt[i] > 3) return DCP_ESEQABC;
-  static uint32_t const off[5] = {0, 4, 20, 84, 340};
-  auto y = [&](int64_t i) -> uint32_t { return minus ? 3u - nt[n - 1 - i] : nt[i]; };
   for (int64_t r = 0; r <= n; ++r)
   {
     uint32_t *c = rows + r * 8;
-    for (int t = 1; t <= 5; ++t)
-    {
-      uint32_t code = 0;
-      for (int64_t i = r - t; i < r && r >= t; ++i) code = code * 4 + y(i);
-      c[t - 1] = r >= t ? off[t - 1] + code : 0;
-    }
+    dcp_code_row_words(r, [&](int t) -> uint32_t { return minus ? 3u - nt[n - 1 - (r - t)] : nt[r - t]; }, c);
     c[5] = c[6] = c[7] = 0;
   }
   return 0;

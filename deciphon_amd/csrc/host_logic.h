@@ -68,9 +68,6 @@ struct DcpWindow
   bool next();
 };
 
-// c-core/lrt.h:6-9
-inline float dcp_lrt(float null_loglik, float alt_loglik) { return -2 * (null_loglik - alt_loglik); }
-
 // Contiguous partitions of n profiles for nparts workers: first[p] .. first[p + 1] is partition p.
 // balanced = false: the reference's rule, ceil((n - p) / nparts) profiles each (c-core/partition_size.c:13-16
 // as c-core/protein_reader.c:112-128 applies it).  balanced = true: still contiguous and in order (the row

@@ -1,5 +1,6 @@
 // scan_rows.cpp -- see scan_rows.h
 #include "scan_rows.h"
+#include "code_rows.h"
 #include "dcp_errors.h"
 #include "parallel_for.h"
 #include "press_kernel.h"
@@ -55,10 +56,9 @@ std::string format_row(dcp_batch::Seq const &seq, std::string const &text, uint8
       if (ok)
       {
         // the code of the n-mer (imm_eseq's indexing: SURVEY 8a row S) keys the decoder's memo
-        static unsigned const code_off[6] = {0, 0, 4, 20, 84, 340};
         unsigned code = 0;
         for (int t = 0; t < n; ++t) code = code * 4 + nt[(size_t)(wstart + pos + t)];
-        std::atomic<uint8_t> &slot = dec.memo[entry * DCP_TABLE_SIZE + code_off[n] + code];
+        std::atomic<uint8_t> &slot = dec.memo[entry * DCP_TABLE_SIZE + dcp_code_off(n) + code];
         uint8_t m = slot.load(std::memory_order_relaxed);
         if (m == 0xFF)
         {

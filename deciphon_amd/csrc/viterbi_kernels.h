@@ -96,20 +96,21 @@ hipError_t dcp_launch_cost_pack_lds(int shape, DcpLaunch const &a, DcpPack const
                                     uint32_t ncode_rows);
 // every problem of classes 0..3 (single-wave) in one launch
 hipError_t dcp_launch_cost_fused(DcpLaunch const &a);
-hipError_t dcp_launch_encode(unsigned char const *nt, int64_t const *seq_off, int64_t const *row_off, int nseq,
-                             int64_t max_len, DcpCodeRow *rows, hipStream_t stream);
-// both strands of nreads reads: sequence 2s is read s, 2s + 1 its reverse complement; seq_off[nreads + 1] (the reads
-// in nt), row_off[2 nreads + 1] (the rows in front of each sequence)
-hipError_t dcp_launch_encode_strands(unsigned char const *nt, int64_t const *seq_off, int64_t const *row_off, int nreads,
-                                     int64_t max_len, DcpCodeRow *rows, hipStream_t stream);
 
-// ---- calibrate.hip ----
+// ---- code_rows.hip ----
+// the code rows (code_rows.h) of nreads reads, nt[seq_off[s] .. seq_off[s + 1]), max_len the longest: sequence s is read
+// s, row_off[nreads + 1] the rows in front of each; or, on both strands, sequence 2s is read s and 2s + 1 its reverse
+// complement, row_off[2 nreads + 1]
+hipError_t dcp_launch_encode(unsigned char const *nt, int64_t const *seq_off, int64_t const *row_off, int nreads,
+                             bool both, int64_t max_len, DcpCodeRow *rows, hipStream_t stream);
 // the code rows of nseq random sequences of len nucleotides (calibrate.h states them), len + 1 rows each, back to back
 // from rows[0]: no nt buffer, no loads
 hipError_t dcp_launch_random_code_rows(int nseq, int len, uint64_t seed, uint32_t const t[3], DcpCodeRow *rows,
                                        hipStream_t stream);
+
+// ---- calibrate.hip ----
 // Gumbel location of nprof profiles by maximum likelihood at fixed lambda, one wavefront per profile: profile p's n score
-// pairs {null, alt} are out[2 n p ..); x = -2 * (null_loglik - alt_loglik) as dcp_lrt_filter_kernel forms it, non-finite
+// pairs {null, alt} are out[2 n p ..); x = dcp_lrt(-null, -alt) as dcp_lrt_filter_kernel forms it, non-finite
 // x left out and counted in excluded[p]; mu_bits[p] = the fp32 bits of
 //   m - (1 / lambda) * log((1 / n') * sum exp(-lambda * (x - m))),  m = min x,  over the n' kept scores, summed in fp64
 // (every term <= 1); NaN when n' = 0.

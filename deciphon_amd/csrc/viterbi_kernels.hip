@@ -446,85 +446,6 @@ __global__ __launch_bounds__(64 * W) void dcp_path_kernel(float const *__restric
   store_f32_lane0(out + pb.out, w.g.lane, T);
 }
 
-// Code rows of one encoded sequence: row r (1..n) holds the codes of the
-// 1..5-mers covering positions r-t..r-1 (imm_eseq_get, third-party imm;
-// off[t] + sum idx*4^(t-1-i), A,C,G,T = 0..3).
-__global__ void dcp_encode_kernel(unsigned char const *__restrict__ nt, int64_t const *__restrict__ seq_off,
-                                  int64_t const *__restrict__ row_off, int nseq, DcpCodeRow *__restrict__ rows)
-{
-  // gridDim.y is capped at 65535 (a batch of metagenomic reads is larger): stride over the sequences
-  for (int s = (int)blockIdx.y; s < nseq; s += (int)gridDim.y)
-  {
-    int64_t const n = seq_off[s + 1] - seq_off[s];
-    unsigned char const *x = nt + seq_off[s];
-    DcpCodeRow *out = rows + row_off[s];
-    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r <= n; r += (int64_t)gridDim.x * blockDim.x)
-    {
-      DcpCodeRow cr;
-      unsigned const off[5] = {0u, 4u, 20u, 84u, 340u};
-      unsigned idx = 0;
-#pragma unroll
-      for (int t = 1; t <= 5; ++t)
-      {
-        // extend the t-mer to the left: new symbol is the most significant digit
-        bool const ok = r - t >= 0;
-        unsigned const sym = ok ? x[r - t] : 0u;
-        idx += sym << (2 * (t - 1));
-        cr.c[t - 1] = ok ? off[t - 1] + idx : 0u;
-      }
-      cr.c[5] = cr.c[6] = cr.c[7] = 0;
-      out[r] = cr;
-    }
-  }
-}
-
-// Code rows of both strands of every read from one pass over its nucleotides (dcp_code_rows_of, include/deciphon_host.h,
-// states the rows): read s becomes sequence 2s as given and sequence 2s + 1, its reverse complement y[i] = 3 - x[n-1-i],
-// which is never materialised.  Row j of the reverse complement holds the t-mers y[j-t..j-1] = 3 - x[n-j+t-1..n-j]: the
-// thread of position r = n - j extends them to the RIGHT of r on the given strand as it extends the plus strand's to
-// the left, so it reads x[r-5..r+4], writes plus row r and minus row n - r, each as two 16-byte stores.
-// seq_off[nreads + 1]: the reads in nt; row_off[2 nreads + 1]: the rows in front of each of the 2 nreads sequences.
-__global__ void dcp_encode_strands_kernel(unsigned char const *__restrict__ nt, int64_t const *__restrict__ seq_off,
-                                          int64_t const *__restrict__ row_off, int nreads, DcpCodeRow *__restrict__ rows)
-{
-  // gridDim.y is capped at 65535: stride over the reads
-  for (int s = (int)blockIdx.y; s < nreads; s += (int)gridDim.y)
-  {
-    int64_t const n = seq_off[s + 1] - seq_off[s];
-    unsigned char const *x = nt + seq_off[s];
-    uint4 *plus = reinterpret_cast<uint4 *>(rows + row_off[2 * (int64_t)s]); // (rows are 32 bytes from a 256-byte base)
-    uint4 *minus = reinterpret_cast<uint4 *>(rows + row_off[2 * (int64_t)s + 1]);
-    if (n == 0) // an empty read: row 0 of either strand, and nothing to load
-    {
-      if (blockIdx.x == 0 && threadIdx.x == 0) plus[0] = plus[1] = minus[0] = minus[1] = make_uint4(0u, 0u, 0u, 0u);
-      continue;
-    }
-    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r <= n; r += (int64_t)gridDim.x * blockDim.x)
-    {
-      unsigned const off[5] = {0u, 4u, 20u, 84u, 340u};
-      unsigned cp[5], cm[5], ip = 0, im = 0;
-#pragma unroll
-      for (int t = 1; t <= 5; ++t)
-      {
-        // either strand's new symbol is its t-mer's leftmost, the most significant digit
-        // (a symbol beyond either end is read from the nearest position inside, n > 0, and dropped: ten loads in
-        // flight at once, none behind a branch)
-        bool const okp = r - t >= 0, okm = r + t <= n;
-        unsigned const lp = x[okp ? r - t : 0], lm = x[okm ? r + t - 1 : n - 1];
-        unsigned const sp = okp ? lp : 0u, sm = okm ? 3u - lm : 0u;
-        ip += sp << (2 * (t - 1));
-        im += sm << (2 * (t - 1));
-        cp[t - 1] = okp ? off[t - 1] + ip : 0u;
-        cm[t - 1] = okm ? off[t - 1] + im : 0u;
-      }
-      plus[2 * r] = make_uint4(cp[0], cp[1], cp[2], cp[3]);
-      plus[2 * r + 1] = make_uint4(cp[4], 0u, 0u, 0u);
-      minus[2 * (n - r)] = make_uint4(cm[0], cm[1], cm[2], cm[3]);
-      minus[2 * (n - r) + 1] = make_uint4(cm[4], 0u, 0u, 0u);
-    }
-  }
-}
-
 // trellis_unzip on the device (dcp_trellis_step, dcp_states.h): one thread walks one problem's trellis from T at stage L
 // back to S at stage 0 and writes the steps, packed as state_id | seqsize << 16, from
 // the END of its buffer backwards, so that they read forwards in path order.
@@ -566,8 +487,7 @@ __global__ void dcp_unzip_kernel(DcpProfileDev const *__restrict__ profiles, Dcp
   nsteps[pb.out] = bad ? -1 : (int32_t)n;
 }
 
-// The filter of process_window (c-core/thread.c:118-121) on the device: lrt = -2 * (null - alt) of every window
-// (c-core/lrt.h:6-9, the same fp32 operations), and the windows that go on to the path pass -- lrt finite and
+// The filter of process_window (c-core/thread.c:118-121) on the device: dcp_lrt of every window (dcp_types.h), and the windows that go on to the path pass -- lrt finite and
 // >= 0 -- appended to a list: hits[0] counts them, then (window, lrt bits) pairs, in no particular order (the
 // host sorts the few that there are).
 __global__ void dcp_lrt_filter_kernel(float const *__restrict__ out, int n, uint32_t *__restrict__ hits)
@@ -578,7 +498,7 @@ __global__ void dcp_lrt_filter_kernel(float const *__restrict__ out, int n, uint
   if (i < n)
   {
     float const null_loglik = -out[2 * (size_t)i], alt_loglik = -out[2 * (size_t)i + 1];
-    lrt = -2 * (null_loglik - alt_loglik);
+    lrt = dcp_lrt(null_loglik, alt_loglik);
     keep = lrt >= 0.0f && lrt < __builtin_inff(); // finite (not NaN, not +inf) and not negative
   }
   unsigned long long const mask = __ballot(keep);
@@ -950,28 +870,4 @@ hipError_t dcp_launch_path(int cls, DcpLaunch const &a)
                        a.profiles, a.problems, a.code_rows, a.xt_table, a.arena, a.out, a.nprob);
     return hipGetLastError();
   });
-}
-
-hipError_t dcp_launch_encode(unsigned char const *nt, int64_t const *seq_off, int64_t const *row_off, int nseq,
-                             int64_t max_len, DcpCodeRow *rows, hipStream_t stream)
-{
-  if (nseq <= 0) return hipSuccess;
-  unsigned bx = (unsigned)((max_len + 1 + 255) / 256);
-  if (bx < 1) bx = 1;
-  if (bx > 1024) bx = 1024;
-  hipLaunchKernelGGL(dcp_encode_kernel, dim3(bx, (unsigned)(nseq < 65535 ? nseq : 65535)), dim3(256), 0, stream, nt,
-                     seq_off, row_off, nseq, rows);
-  return hipGetLastError();
-}
-
-hipError_t dcp_launch_encode_strands(unsigned char const *nt, int64_t const *seq_off, int64_t const *row_off, int nreads,
-                                     int64_t max_len, DcpCodeRow *rows, hipStream_t stream)
-{
-  if (nreads <= 0) return hipSuccess;
-  unsigned bx = (unsigned)((max_len + 1 + 255) / 256);
-  if (bx < 1) bx = 1;
-  if (bx > 1024) bx = 1024;
-  hipLaunchKernelGGL(dcp_encode_strands_kernel, dim3(bx, (unsigned)(nreads < 65535 ? nreads : 65535)), dim3(256), 0,
-                     stream, nt, seq_off, row_off, nreads, rows);
-  return hipGetLastError();
 }

@@ -2,6 +2,7 @@
 // interface (c-core/viterbi.h) served by the GPU engine, one window per call.
 #include "../../include/dcp_viterbi.h"
 #include "../../include/deciphon_hip.h"
+#include "code_rows.h"
 #include "dcp_errors.h"
 #include "dcp_types.h"
 
@@ -28,7 +29,6 @@ namespace
 // evaluates the callback into nucleotide indices and checks that it describes a sequence
 bool sequence_of(int L, viterbi_code_fn fn, void *arg, std::vector<uint8_t> &nt)
 {
-  static int const off[6] = {0, 0, 4, 20, 84, 340};
   nt.resize((size_t)L);
   for (int pos = 0; pos < L; ++pos)
   {
@@ -36,13 +36,14 @@ bool sequence_of(int L, viterbi_code_fn fn, void *arg, std::vector<uint8_t> &nt)
     if (c < 0 || c > 3) return false;
     nt[(size_t)pos] = (uint8_t)c;
   }
-  for (int len = 2; len <= 5; ++len)
-    for (int pos = 0; pos + len <= L; ++pos)
-    {
-      int idx = 0;
-      for (int i = 0; i < len; ++i) idx = idx * 4 + nt[(size_t)(pos + i)];
-      if (fn(pos, len, arg) != off[len] + idx) return false;
-    }
+  // the 2..5-mers that end in front of row r, against the row those nucleotides have (code_rows.h)
+  for (int r = 2; r <= L; ++r)
+  {
+    uint32_t c[5];
+    dcp_code_row_words(r, [&](int t) { return nt[(size_t)(r - t)]; }, c);
+    for (int len = 2; len <= 5 && len <= r; ++len)
+      if (fn(r - len, len, arg) != (int)c[len - 1]) return false;
+  }
   return true;
 }
 

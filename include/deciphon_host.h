@@ -93,8 +93,8 @@ int64_t dcp_window_count(int64_t seq_size, int core_size);
  * off[t] + its base-4 value, the leftmost symbol the most significant digit, off = {0, 4, 20, 84, 340} -- and 0 where
  * r < t; words 5..7 are 0.  minus = 0: y = nt, what dcp_hip_set_sequences leaves.  minus != 0: y is the reverse
  * complement, y[i] = 3 - nt[n-1-i], what dcp_hip_set_sequences_strands leaves for the minus strand.  This function is
- * the statement the encode kernels are tested against.  0; DCP_EFUNCUSE for NULL or n < 0; DCP_ESEQABC for an index
- * above 3 (nothing of rows is then defined). */
+ * the statement (csrc/code_rows.h) the kernels of csrc/code_rows.hip are built from and tested against.
+ * 0; DCP_EFUNCUSE for NULL or n < 0; DCP_ESEQABC for an index above 3 (nothing of rows is then defined). */
 int dcp_code_rows_of(uint8_t const *nt, int64_t n, int minus, uint32_t *rows);
 /* The cost-order copy of the emission rows that the cost kernel of Q positions per lane and W wavefronts reads
  * (csrc/host_logic.h dcp_cost_order_col): cols[k] receives the column of position k, k < 64*Q*W, counted from the

@@ -112,6 +112,9 @@ say(f"{'seconds per scan (min..max)':28s}" + "".join(
 for ph in PHASES + ("windows", "path_passes", "rounds", "chunks"):
     fmt = "20.4f" if ph.endswith("_s") else "20.0f"
     say(f"{ph:28s}" + "".join(format(med([p[ph] for _, p in runs[k]]), fmt) for k in "abc"))
+# the upload + encode phase is a host-timed interval of a millisecond or two: its spread over the rounds beside its median
+h2d = {k: [p["reads_h2d_encode_s"] * 1e3 for _, p in runs[k]] for k in "abc"}
+say(f"{'reads_h2d_encode ms min/med/max':32s}" + "".join(f"{min(h2d[k]):8.3f}/{med(h2d[k]):.3f}/{max(h2d[k]):.3f}" for k in "abc"))
 a, b, c = (med([t for t, _ in runs[k]]) for k in "abc")
 say()
 say(f"(a) / (c) = {a / c:.2f}, (a) / (b) = {a / b:.2f}; cost pass (a) / (c) = "

@@ -1,5 +1,5 @@
 // host_sanitize.cpp -- TEST INFRASTRUCTURE: the host-side .dcp reader, windows, partitions, one short window walk, a
-// few memory plans of the path pass and a few hundred plans of window lists under ASan + UBSan, on the golden database, on truncated copies and on 200 randomly corrupted copies (must fail
+// few memory plans of the path pass, a few hundred plans of window lists and the code rows of short reads under ASan + UBSan, on the golden database, on truncated copies and on 200 randomly corrupted copies (must fail
 // cleanly, never fault).
 #include "deciphon_hip.h"
 #include "deciphon_host.h"
@@ -155,6 +155,27 @@ int main(int argc, char **argv)
     }
     if (!refusals || refusals == plans) { printf("stage: %ld refusals of %ld\n", refusals, plans); return 1; }
     printf("stage done: %ld plans\n", plans);
+  }
+  {
+    /* code rows (csrc/code_rows.h, the host's use of it) of reads of 0..7 nucleotides, every count of symbols below
+     * five to the left of a row, into buffers of exactly their size: the minus rows are the plus rows of the read
+     * reverse-complemented here, and word 0 of a plus row is the nucleotide in front of it */
+    srand(11);
+    for (int len = 0; len <= 7; ++len)
+    {
+      std::vector<uint8_t> nt((size_t)len), rev((size_t)len);
+      for (int i = 0; i < len; ++i) nt[(size_t)i] = (uint8_t)(rand() & 3);
+      for (int i = 0; i < len; ++i) rev[(size_t)i] = (uint8_t)(3 - nt[(size_t)(len - 1 - i)]);
+      std::vector<uint32_t> plus(((size_t)len + 1) * 8), minus(plus.size()), rev_plus(plus.size());
+      if (dcp_code_rows_of(nt.data(), len, 0, plus.data()) || dcp_code_rows_of(nt.data(), len, 1, minus.data()) ||
+          dcp_code_rows_of(rev.data(), len, 0, rev_plus.data()))
+      { printf("code rows: refused at length %d\n", len); return 1; }
+      if (minus != rev_plus) { printf("code rows: minus rows differ at length %d\n", len); return 1; }
+      for (int r = 0; r <= len; ++r)
+        if (plus[(size_t)r * 8] != (r ? nt[(size_t)r - 1] : 0u) || plus[(size_t)r * 8 + 5] || plus[(size_t)r * 8 + 7])
+        { printf("code rows: row %d of length %d\n", r, len); return 1; }
+    }
+    printf("code rows done: lengths 0..7\n");
   }
   /* truncated and corrupt files must fail cleanly */
   FILE *f = fopen(argv[1], "rb"); fseek(f, 0, SEEK_END); long sz = ftell(f); fseek(f, 0, SEEK_SET);

@@ -1,4 +1,4 @@
-"""GPU: both strands of every read (dcp_hip_set_sequences_strands, dcp_scan_set_strands; dcp_encode_strands_kernel).
+"""GPU: both strands of every read (dcp_hip_set_sequences_strands, dcp_scan_set_strands; the kernels of csrc/code_rows.hip).
 
 The minus strand exists only as code rows that the GPU writes from the one upload of the reads.  So: those rows, word
 for word, against the host statement (dcp_code_rows_of); the cost and path passes over a minus-strand window against the
@@ -76,6 +76,30 @@ def test_rows_of_more_reads_than_grid_rows():
             p, m = want[k]
             assert np.array_equal(eng.code_rows(2 * s), p), s
             assert np.array_equal(eng.code_rows(2 * s + 1), m), s
+        eng.set_sequences(reads)  # and the plain kernel strides there as well
+        assert eng.num_sequences == n
+        for s, x in enumerate(reads):
+            assert np.array_equal(eng.code_rows(s), want[x.tobytes()][0]), s
+
+
+def test_rows_of_a_read_longer_than_the_grid():
+    """A read of 262 151 rows, more than the 1024 blocks of 256 threads a grid has at the most in x: every kernel's loop
+    over the rows takes a second turn, and the short reads ride in a grid sized by the long one."""
+    rng = np.random.default_rng(9)
+    long = 262150
+    reads = [random_seq(rng, n) for n in (0, long, 1, 5)]
+    seed, freq = 20262, [0.1, 0.2, 0.3, 0.4]
+    with deciphon_amd.Engine(0) as eng:
+        eng.set_sequences(reads, "plus")
+        assert eng.num_sequences == len(reads)
+        for s, x in enumerate(reads):
+            assert np.array_equal(eng.code_rows(s), host.code_rows_of(x)), (s, "+")
+        eng.set_sequences(reads, "both")
+        check_rows(eng, reads)
+        eng.set_random_sequences(2, long, seed, freq)
+        assert eng.num_sequences == 2
+        for s in range(2):
+            assert np.array_equal(eng.code_rows(s), host.code_rows_of(host.random_nt(seed, long, s * long, freq))), s
 
 
 def test_refusals_leave_the_previous_reads_in_force():

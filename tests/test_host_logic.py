@@ -205,6 +205,7 @@ def test_host_reader_under_sanitizers(tmp_path):
     assert "walk done" in r.stdout  # one short window walk (csrc/scan_walk.h)
     assert "plan done: 720 plans" in r.stdout  # memory plans of the path pass (csrc/path_plan.h)
     assert "stage done: 400 plans" in r.stdout  # plans of window lists and their cost launches (csrc/stage_plan.h)
+    assert "code rows done: lengths 0..7" in r.stdout  # both strands at every short length (csrc/code_rows.h)
 
 
 def test_both_dcp_encodings_read_identically(tmp_path):

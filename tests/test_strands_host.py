@@ -1,6 +1,6 @@
 """CPU: the host half of scanning both strands -- the statement of a code row on either strand (dcp_code_rows_of,
-include/deciphon_host.h: what the encode kernels are held to), the scan's strand mode and its argument checks, which
-come before any device (dcp_scan_set_strands), the mapping of a row's hit back to the read as given (hit_on_read), and
+include/deciphon_host.h: csrc/code_rows.h, what the kernels of csrc/code_rows.hip are built from and held to), the
+scan's strand mode and its argument checks, which come before any device (dcp_scan_set_strands), the mapping of a row's hit back to the read as given (hit_on_read), and
 the chunk planner and the window walk fed the doubled, interleaved read lengths a scan of both strands hands them."""
 import numpy as np
 import pytest
