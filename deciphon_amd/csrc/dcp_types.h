@@ -57,7 +57,7 @@ struct DcpProfileDev
 #define DCP_HDI inline
 #endif
 // c-core/lrt.h:6-9, in its fp32 operations: the score of a window, for the host and for the kernels that filter and fit
-// by it (dcp_lrt_filter_kernel, dcp_gumbel_fit_kernel)
+// by it (dcp_lrt_filter_kernel, dcp_calib_gather_kernel)
 DCP_HDI float dcp_lrt(float null_loglik, float alt_loglik) { return -2 * (null_loglik - alt_loglik); }
 
 // where position k of a profile lies among the columns of a cost-order row of shape (Q, W) -- the map itself is

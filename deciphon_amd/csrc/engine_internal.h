@@ -402,13 +402,18 @@ struct dcp_hip
   bool staged_ran = false; // a dcp_hip_run_staged with reps > 0 has filled d_out since the dcp_hip_stage
   std::vector<CostLaunch> last_cost_launches; // the schedule launch_cost_all ran last (dcp_hip_last_cost_launches)
 
-  // Calibration (engine_calibrate.cpp): the Gumbel location of profiles [0, calib_mu.size()) from the last
-  // dcp_hip_calibrate and the scores it left out of each fit, at calib_lambda.  A profile beyond them has none (NaN); so
-  // has every profile once something a score depends on has changed (drop_calibration).
+  // Calibration (engine_calibrate.cpp): the ladder of read lengths of the last dcp_hip_calibrate / _calibrate_lengths
+  // (one rung for the first), and for profiles [0, calib_profile_lambda.size()) the Gumbel location at every rung, the
+  // scores each fit left out, [profile][calib_lens.size()], and lambda -- calib_lambda, the call's argument, or the
+  // profile's own fit when that was 0.  A profile beyond them has none (NaN); so has every profile once something a
+  // score depends on has changed (drop_calibration).
+  std::vector<int> calib_lens;
   std::vector<float> calib_mu;
   std::vector<int32_t> calib_excluded;
+  std::vector<float> calib_profile_lambda;
   float calib_lambda = NAN;
-  DevBuf<uint32_t> d_mu; // fp32 bits, as the fit kernel stores them
+  DevBuf<float> d_scores; // lrt of [profile][rung][read], gathered chunk by chunk for the one fit launch
+  DevBuf<uint32_t> d_mu, d_lambda; // fp32 bits, as the fit kernel stores them
   DevBuf<int32_t> d_excluded;
 
   // Input generation: moves with every accepted change of the profiles, sequences, mode or xtrans override.  The
@@ -527,8 +532,10 @@ int launch_cost_all(Pass const &ps, StagedPlan const &st, hipStream_t origin = n
 // _set_xtrans_table, _clear_profiles
 inline void drop_calibration(dcp_hip *x)
 {
+  x->calib_lens.clear();
   x->calib_mu.clear();
   x->calib_excluded.clear();
+  x->calib_profile_lambda.clear();
   x->calib_lambda = NAN;
 }
 

@@ -354,6 +354,37 @@ extern "C" int64_t dcp_window_count(int64_t seq_size, int core_size)
   return seq_size <= span ? 1 : 1 + (seq_size - span + step - 1) / step;
 }
 
+// mu of a profile at a window length from the rungs of its calibration (include/deciphon_host.h states the rule): the
+// line through the two usable rungs around len -- the nearest two beyond either end -- in ln len.
+extern "C" double dcp_calib_mu_at(int nlen, int const *lens, float const *mu, int64_t len)
+{
+  if (nlen < 1 || !lens || !mu || len < 1) return NAN;
+  for (int j = 0; j < nlen; ++j)
+    if (lens[j] < 1 || (j > 0 && lens[j] <= lens[j - 1])) return NAN;
+  // a: the last usable rung at or below len, or else the first usable one; b: the usable rung next to it, above when
+  // there is one
+  int a = -1, b = -1;
+  for (int j = 0; j < nlen; ++j)
+  {
+    if (isnan(mu[j])) continue;
+    if (a < 0 || lens[j] <= len)
+    {
+      b = a;
+      a = j;
+    }
+    else
+    {
+      b = j;
+      break;
+    }
+  }
+  if (a < 0) return NAN;
+  if (b < 0 || lens[a] == len) return (double)mu[a];
+  if (b < a) std::swap(a, b);
+  double const t = log((double)len / (double)lens[a]) / log((double)lens[b] / (double)lens[a]);
+  return (double)mu[a] + ((double)mu[b] - (double)mu[a]) * t;
+}
+
 // The code rows of one read, on either strand, by the statement the kernels are built from as well (code_rows.h;
 // code_rows.hip): the rows of the strand's sequence y = nt, or its reverse complement y[i] = 3 - nt[n-1-i].
 extern "C" int dcp_code_rows_of(uint8_t const *nt, int64_t n, int minus, uint32_t *rows)

@@ -452,6 +452,19 @@ int dcp_scan_set_evalue(struct dcp_scan *x, double z, double max)
 
 float dcp_scan_profile_mu(struct dcp_scan const *x, int i) { return x && x->eng ? dcp_hip_profile_mu(x->eng, i) : NAN; }
 
+int dcp_scan_calibrate_lengths(struct dcp_scan *x, int nseq, int nlen, int const *lens, uint64_t seed, float const freq[4], float lambda)
+{
+  if (!x) return raise(DCP_EFUNCUSE, __func__);
+  if (!x->eng) return raise(DCP_EFUNCUSE, __func__, "dcp_scan_setup has not succeeded");
+  if (int const rc = dcp_hip_calibrate_lengths(x->eng, nseq, nlen, lens, seed, freq, lambda))
+    return raise(rc, __func__, dcp_hip_strerror(x->eng));
+  return 0;
+}
+
+double dcp_scan_profile_mu_at(struct dcp_scan const *x, int i, int64_t len) { return x && x->eng ? dcp_hip_profile_mu_at(x->eng, i, len) : NAN; }
+
+float dcp_scan_profile_lambda(struct dcp_scan const *x, int i) { return x && x->eng ? dcp_hip_profile_lambda(x->eng, i) : NAN; }
+
 int dcp_scan_set_strands(struct dcp_scan *x, int strands)
 {
   // no engine is asked: the mode belongs to the scan and reaches the GPU with the reads of the next run

@@ -233,10 +233,11 @@ void DcpScanRows::format(std::vector<dcp_walk_hit> const &hits)
     copied.set_value();
     std::vector<DcpProductRuns::Row> out(jobs.size());
     std::vector<uint8_t> dropped(jobs.size(), 0); // rows at or beyond the E-value limit (DcpEvalueRule)
-    float const lambda = dcp_hip_calib_lambda(eng_);
     dcp_parallel_for(jobs.size(), 16, 8, 1, [&](size_t k) {
       Job const &j = jobs[k];
-      double const evalue = dcp_lrt_evalue(j.at.lrt, dcp_hip_profile_mu(eng_, j.at.profile), lambda, evalue_.z);
+      // mu of the profile at the window's length (dcp_calib_mu_at: one rung is a constant), and the profile's lambda
+      float const mu = (float)dcp_hip_profile_mu_at(eng_, j.at.profile, (int64_t)j.at.stop - (int64_t)j.at.start);
+      double const evalue = dcp_lrt_evalue(j.at.lrt, mu, dcp_hip_profile_lambda(eng_, j.at.profile), evalue_.z);
       if (evalue >= evalue_.max) // (never for NaN: a profile that is not calibrated keeps its rows)
       {
         dropped[k] = 1;

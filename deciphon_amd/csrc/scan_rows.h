@@ -69,8 +69,9 @@ private:
   size_t at_profile = 0, at_node = 0; // where the next entry of a dcp_scan_set_gencode goes
 };
 
-// The evalue column of a run and its row filter.  A row whose profile has a Gumbel location (dcp_hip_profile_mu is not
-// NaN) prints E = dcp_lrt_evalue(lrt, mu, the engine's lambda, z) with %.2g, as c-core/product_thread.c:60 prints
+// The evalue column of a run and its row filter.  A row whose profile has a Gumbel location at the length of the row's
+// window (dcp_hip_profile_mu_at of window_stop - window_start is not NaN) prints E = dcp_lrt_evalue(lrt, that mu as fp32,
+// dcp_hip_profile_lambda of the profile, z) with %.2g, as c-core/product_thread.c:60 prints
 // HMMER's, and is left out when E >= max (c-core/thread.c:192-201 drops E >= 1).  Any other row prints "nan" and stays.
 // The walk has moved on by then either way: last_hit_pos does not depend on it (thread.c:162 against thread.c:201).
 struct DcpEvalueRule

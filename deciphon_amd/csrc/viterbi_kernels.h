@@ -109,10 +109,18 @@ hipError_t dcp_launch_random_code_rows(int nseq, int len, uint64_t seed, uint32_
                                        hipStream_t stream);
 
 // ---- calibrate.hip ----
-// Gumbel location of nprof profiles by maximum likelihood at fixed lambda, one wavefront per profile: profile p's n score
-// pairs {null, alt} are out[2 n p ..); x = dcp_lrt(-null, -alt) as dcp_lrt_filter_kernel forms it, non-finite
-// x left out and counted in excluded[p]; mu_bits[p] = the fp32 bits of
-//   m - (1 / lambda) * log((1 / n') * sum exp(-lambda * (x - m))),  m = min x,  over the n' kept scores, summed in fp64
-// (every term <= 1); NaN when n' = 0.
-hipError_t dcp_launch_gumbel_fit(float const *out, int nprof, int n, float lambda, uint32_t *mu_bits, int32_t *excluded,
-                                 hipStream_t stream);
+// The scores of one chunk of a calibration's cost pass at one rung of its ladder: out holds the pairs {null, alt} of
+// nprof profiles x nseq reads, profile-major; x = dcp_lrt(-null, -alt), as dcp_lrt_filter_kernel forms it, goes to
+// scores[profile][nlen][nseq] at [.][rung][read] (scores: at the chunk's first profile).
+hipError_t dcp_launch_calib_gather(float const *out, int nprof, int nseq, int nlen, int rung, float *scores, hipStream_t stream);
+// Gumbel fit of nprof profiles by maximum likelihood, one wavefront per profile, over scores[nprof][nlen][n]; nlen in
+// 1 .. DCP_CALIB_MAX_LENS.  Per rung j the non-finite scores are left out and counted in excluded[p][j]; over the n' kept
+//   mu = m - (1 / lambda) * log((1 / n') * sum exp(-lambda * (x - m))),  m = min x,  summed in fp64 (every term <= 1),
+// whose fp32 bits are mu_bits[p][j]; NaN when n' = 0.  lambda > 0: that lambda.  lambda == 0: the one lambda per profile
+// that maximises the likelihood with a location of its own for every rung -- the root of
+//   g(lambda) = sum_j n'_j (1 / lambda - mean_j(y) + T1_j / T0_j),  y = x - m_j,  Tk_j = sum y^k exp(-lambda y),
+// over the rungs with n'_j >= 2 and not all scores equal, by Newton's method inside a bracket, to 1e-13 relative -- and
+// mu of every rung at it; a profile without such a rung gets NaN for lambda and every mu.  lambda_bits[p]: the fp32 bits
+// of the lambda used.  The order of every sum is fixed: the same scores give the same bits.
+hipError_t dcp_launch_gumbel_ladder_fit(float const *scores, int nprof, int nlen, int n, float lambda, uint32_t *mu_bits,
+                                        int32_t *excluded, uint32_t *lambda_bits, hipStream_t stream);

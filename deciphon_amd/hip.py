@@ -96,6 +96,16 @@ def load_library() -> C.CDLL:
     L.dcp_hip_profile_calib_excluded.argtypes = [vp, i32]
     L.dcp_hip_calib_lambda.argtypes = [vp]
     L.dcp_hip_calib_lambda.restype = C.c_float
+    L.dcp_hip_calibrate_lengths.argtypes = [vp, i32, i32, vp, C.c_uint64, vp, C.c_float]
+    L.dcp_hip_calib_num_lengths.argtypes = [vp]
+    L.dcp_hip_calib_length.argtypes = [vp, i32]
+    L.dcp_hip_profile_mu_rung.argtypes = [vp, i32, i32]
+    L.dcp_hip_profile_mu_rung.restype = C.c_float
+    L.dcp_hip_profile_calib_excluded_rung.argtypes = [vp, i32, i32]
+    L.dcp_hip_profile_lambda.argtypes = [vp, i32]
+    L.dcp_hip_profile_lambda.restype = C.c_float
+    L.dcp_hip_profile_mu_at.argtypes = [vp, i32, C.c_int64]
+    L.dcp_hip_profile_mu_at.restype = C.c_double
     L.dcp_hip_set_mode.argtypes = [vp, i32, i32]
     L.dcp_hip_set_xtrans_table.argtypes = [vp, i32, vp]
     L.dcp_hip_xtrans.argtypes = [i32, i32, i32, vp]
@@ -333,8 +343,38 @@ class Engine:
 
     @property
     def calib_lambda(self) -> float:
-        """lambda of the calibration in force; NaN without one."""
+        """lambda of the calibration in force as it was passed, 0 when it was fitted; NaN without one."""
         return float(self.lib.dcp_hip_calib_lambda(self.h))
+
+    def calibrate_lengths(self, nseq: int, lengths, seed: int, freq=None, lam: float = 0.5) -> None:
+        """calibrate() at every length of the increasing ladder `lengths` (dcp_hip_calibrate_lengths): rung j scores the
+        reads of set_random_sequences(nseq, lengths[j], seed + j, freq).  lam = 0 fits one lambda per profile, common
+        to its rungs, beside the locations.  The random sequences of the last rung stay resident: set yours again."""
+        keep, ptr = self._freq(freq)
+        lens = np.ascontiguousarray(lengths, np.int32).reshape(-1)
+        self._check(self.lib.dcp_hip_calibrate_lengths(self.h, int(nseq), len(lens), _p(lens), int(seed) & (2**64 - 1), ptr, float(lam)))
+        self._seq_lens = [int(lens[-1])] * int(nseq)
+
+    @property
+    def calib_lengths(self) -> tuple:
+        """The ladder of the calibration in force: one length after calibrate(), () without a calibration."""
+        return tuple(int(self.lib.dcp_hip_calib_length(self.h, j)) for j in range(self.lib.dcp_hip_calib_num_lengths(self.h)))
+
+    def profile_mu_rung(self, i: int, j: int) -> np.float32:
+        """The Gumbel location of profile i at rung j of calib_lengths; NaN when it has none."""
+        return np.float32(self.lib.dcp_hip_profile_mu_rung(self.h, int(i), int(j)))
+
+    def profile_calib_excluded_rung(self, i: int, j: int) -> int:
+        """Scores of profile i at rung j that the fit left out as not finite."""
+        return int(self.lib.dcp_hip_profile_calib_excluded_rung(self.h, int(i), int(j)))
+
+    def profile_lambda(self, i: int) -> np.float32:
+        """lambda of profile i: the one passed or, after lam = 0, the one fitted; NaN when it has none."""
+        return np.float32(self.lib.dcp_hip_profile_lambda(self.h, int(i)))
+
+    def profile_mu_at(self, i: int, length: int) -> float:
+        """The Gumbel location of profile i at a window of `length` nucleotides: host.calib_mu_at of its rungs."""
+        return float(self.lib.dcp_hip_profile_mu_at(self.h, int(i), int(length)))
 
     @property
     def num_sequences(self) -> int:

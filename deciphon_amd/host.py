@@ -100,6 +100,8 @@ def _lib():
     L.dcp_random_nt.argtypes = [C.c_uint64, vp, C.c_int64, C.c_int64, vp]
     L.dcp_lrt_evalue.argtypes = [C.c_float, C.c_float, C.c_float, C.c_double]
     L.dcp_lrt_evalue.restype = C.c_double
+    L.dcp_calib_mu_at.argtypes = [i32, vp, vp, C.c_int64]
+    L.dcp_calib_mu_at.restype = C.c_double
     L.dcp_hmm_open.argtypes = [C.c_char_p, i32, C.POINTER(vp)]
     L.dcp_hmm_close.argtypes = [vp]
     L.dcp_hmm_close.restype = None
@@ -743,6 +745,16 @@ def random_nt(seed: int, n: int, first_idx: int = 0, freq=None) -> np.ndarray:
 def lrt_evalue(lrt, mu, lam, z) -> float:
     """z * (1 - exp(-exp(-lam (lrt - mu)))), the Gumbel tail as dcp_lrt_evalue states it; NaN when mu is."""
     return float(_lib().dcp_lrt_evalue(float(lrt), float(mu), float(lam), float(z)))
+
+
+def calib_mu_at(lens, mu, length) -> float:
+    """mu at a window of `length` nucleotides from the rungs (lens[j], mu[j]) of a calibration over a ladder of read
+    lengths: linear in ln length between the rungs whose mu is not NaN and beyond them (dcp_calib_mu_at)."""
+    L = np.ascontiguousarray(lens, np.int32).reshape(-1)
+    m = np.ascontiguousarray(mu, np.float32).reshape(-1)
+    if len(L) != len(m):
+        raise ValueError("lens and mu differ in length")
+    return float(_lib().dcp_calib_mu_at(len(L), L.ctypes.data_as(C.c_void_p), m.ctypes.data_as(C.c_void_p), int(length)))
 
 
 def decode_quasi_codon(epsilon: float, nucltp, codonm, nt) -> np.ndarray:

@@ -35,6 +35,11 @@ def _lib():
     L.dcp_scan_set_evalue.argtypes = [vp, C.c_double, C.c_double]
     L.dcp_scan_profile_mu.argtypes = [vp, i32]
     L.dcp_scan_profile_mu.restype = C.c_float
+    L.dcp_scan_calibrate_lengths.argtypes = [vp, i32, i32, vp, C.c_uint64, vp, C.c_float]
+    L.dcp_scan_profile_mu_at.argtypes = [vp, i32, C.c_int64]
+    L.dcp_scan_profile_mu_at.restype = C.c_double
+    L.dcp_scan_profile_lambda.argtypes = [vp, i32]
+    L.dcp_scan_profile_lambda.restype = C.c_float
     L.dcp_scan_set_strands.argtypes = [vp, i32]
     L.dcp_scan_strands.argtypes = [vp]
     L.dcp_scan_partition_range.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
@@ -190,6 +195,25 @@ class Scan:
         ptr = None if f is None else f.ctypes.data_as(C.c_void_p)
         if rc := self._lib.dcp_scan_calibrate(self._cscan, int(nseq), int(length), int(seed) & (2**64 - 1), ptr, float(lam)):
             raise DeciphonError(rc)
+
+    def calibrate_lengths(self, nseq: int = 200, lengths=(300, 1000, 3000, 10000), seed: int = 42, freq=None, lam: float = 0.5):
+        """calibrate() at every length of the increasing ladder `lengths` (dcp_scan_calibrate_lengths): the E-value of a
+        row then takes mu at the length of the row's window, linear in its logarithm between the rungs and beyond them
+        (host.calib_mu_at).  lam = 0 fits one lambda per profile as well.  Not while run() is running."""
+        f = None if freq is None else np.ascontiguousarray(freq, np.float32).reshape(4)
+        ptr = None if f is None else f.ctypes.data_as(C.c_void_p)
+        lens = np.ascontiguousarray(lengths, np.int32).reshape(-1)
+        if rc := self._lib.dcp_scan_calibrate_lengths(self._cscan, int(nseq), len(lens), lens.ctypes.data_as(C.c_void_p),
+                                                      int(seed) & (2**64 - 1), ptr, float(lam)):
+            raise DeciphonError(rc)
+
+    def profile_mu_at(self, i: int, length: int) -> float:
+        """The Gumbel location of this scan's profile i at a window of `length` nucleotides; NaN when not calibrated."""
+        return float(self._lib.dcp_scan_profile_mu_at(self._cscan, int(i), int(length)))
+
+    def profile_lambda(self, i: int) -> np.float32:
+        """lambda of this scan's profile i, passed or fitted; NaN when the scan is not calibrated."""
+        return np.float32(self._lib.dcp_scan_profile_lambda(self._cscan, int(i)))
 
     def set_evalue(self, z: float = 0.0, max: float = float("inf")):
         """Z of the evalue column (<= 0: the sequences a run scans, reads x strands) and the limit of its rows: a

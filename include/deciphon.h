@@ -206,6 +206,19 @@ int dcp_scan_set_gencode(struct dcp_scan *, int gencode_id);
 int dcp_scan_calibrate(struct dcp_scan *, int nseq, int len, uint64_t seed, float const freq[4], float lambda);
 int dcp_scan_set_evalue(struct dcp_scan *, double z, double max);
 float dcp_scan_profile_mu(struct dcp_scan const *, int i);
+/* The same over a ladder of read lengths (dcp_hip_calibrate_lengths, include/deciphon_hip.h, whose arguments and error
+ * codes these are): a scan holds windows from a few hundred to 100 000 nucleotides and mu moves with the length, so
+ * every profile gets a mu per length of lens[nlen], and with lambda == 0 a lambda of its own, fitted.  The evalue column
+ * and the filter are then
+ *   dcp_lrt_evalue(lrt, (float)mu of the profile at window_stop - window_start, lambda of the profile, Z)
+ * with mu at a length by dcp_calib_mu_at (include/deciphon_host.h): linear in ln length between the rungs and beyond
+ * them.  After dcp_scan_calibrate that is what it has always been: one rung, a constant mu, the lambda passed.  The
+ * scan is uncalibrated again on the same events.  dcp_scan_profile_mu_at, dcp_scan_profile_lambda: of local profile i;
+ * NaN when it is not calibrated. */
+int dcp_scan_calibrate_lengths(struct dcp_scan *, int nseq, int nlen, int const *lens, uint64_t seed, float const freq[4],
+                               float lambda);
+double dcp_scan_profile_mu_at(struct dcp_scan const *, int i, int64_t len);
+float dcp_scan_profile_lambda(struct dcp_scan const *, int i);
 /* Not in the reference, which scans every read in the orientation it was given and no other (its GFF writer has
  * strand "+" for every hit): DCP_STRANDS_BOTH makes every later dcp_scan_run scan both strands of every read.  The reads
  * go to the GPU once; the code rows of the reverse complements are written there (dcp_hip_set_sequences_strands), and

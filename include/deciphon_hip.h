@@ -182,7 +182,7 @@ int dcp_hip_set_random_sequences(struct dcp_hip *, int nseq, int len, uint64_t s
  * DCP_EFUNCUSE, with nothing changed: batches outstanding, nseq < 1, len < 1, a bad freq, lambda <= 0, infinite or
  * NaN, profiles not committed, no dcp_hip_set_mode yet.  Without profiles it sets the sequences and returns 0.  The
  * random sequences stay resident: the caller sets its reads again.  DECIPHON_HIP_TIMING prints one line
- * "dcp_hip_calibrate:" with profiles, windows, cells and the seconds of generation, cost pass and fit.
+ * "dcp_hip_calibrate:" with profiles, rungs (one), windows, cells and the seconds of generation, cost pass, gather and fit.
  * dcp_hip_profile_mu: NaN for a profile never calibrated, a bad index or NULL.  mu of every profile goes back to NaN on
  * whatever changes a score: dcp_hip_set_epsilon, _set_gencode, _set_mode, _set_xtrans_table, _clear_profiles; profiles
  * added after a calibration have none.  dcp_hip_calib_lambda: the lambda of the calibration in force, NaN without. */
@@ -190,6 +190,47 @@ int dcp_hip_calibrate(struct dcp_hip *, int nseq, int len, uint64_t seed, float 
 float dcp_hip_profile_mu(struct dcp_hip const *, int i);
 int dcp_hip_profile_calib_excluded(struct dcp_hip const *, int i);
 float dcp_hip_calib_lambda(struct dcp_hip const *);
+
+/* ---- calibration over a ladder of read lengths, and lambda fitted ------------------------------------------------
+ * mu moves with the length of what is scored, and one scan holds windows of many lengths.  So:
+ * the calibration above at every length of lens[nlen], 1 <= nlen <= DCP_CALIB_MAX_LENS, every length >= 1 and larger
+ * than the one before.  Rung j scores every profile against exactly the reads of
+ *   dcp_hip_set_random_sequences(nseq, lens[j], seed + j (mod 2^64), freq),
+ * which dcp_random_nt(seed + j, ...) (include/deciphon_host.h) reproduces on the host -- part of the interface, like the
+ * generator -- through the same cost pass in the same chunks; the reads of the last rung stay resident.  A kernel keeps
+ * lrt of every profile x rung x read on the device, and one launch fits all profiles, one wavefront each, every sum in
+ * fp64 in a fixed order (the same arguments give the same bits):
+ *   lambda > 0   that lambda; mu of rung j is the formula above over the rung's finite scores and has the bits
+ *                dcp_hip_calibrate(nseq, lens[j], seed + j, freq, lambda) gives -- which is this call with one rung.
+ *   lambda == 0  one lambda per profile, common to its rungs, by maximum likelihood with a location per rung: with
+ *                y = x - m_j and Tk_j = sum y^k exp(-lambda y) over the n'_j finite scores of rung j, the root of
+ *                  g(lambda) = sum_j n'_j (1 / lambda - mean_j(y) + T1_j / T0_j)
+ *                over the rungs with n'_j >= 2 and not all scores equal (g falls strictly from +inf to a negative
+ *                limit: one root), by Newton's method inside a bracket until |step| <= 1e-13 lambda; then
+ *                mu_j = m_j - log(T0_j / n'_j) / lambda for every rung with a finite score.  A profile without a rung
+ *                that carries scale gets NaN for lambda and every mu: not calibrated.
+ * lambda and mu are kept as fp32; a rung without a finite score has mu NaN; the scores left out are counted per rung.
+ * DCP_EFUNCUSE, with nothing changed -- not the sequences, the calibration in force or any query: whatever
+ * dcp_hip_calibrate refuses, for any rung; nlen or lens as they must not be; lambda negative, NaN or infinite;
+ * lambda == 0 with nseq < 2.  DCP_ENOMEM, with nothing changed, when the scores find no room.  Without profiles it sets
+ * the sequences of the last rung and returns 0.  The calibration goes when dcp_hip_calibrate's does.
+ * DECIPHON_HIP_TIMING prints one line "dcp_hip_calibrate_lengths:" with profiles, rungs, windows, cells and the seconds
+ * of generation, cost pass, gather and fit.
+ * dcp_hip_calib_num_lengths: the rungs of the calibration in force, 0 without one (1 after dcp_hip_calibrate);
+ * dcp_hip_calib_length: of rung j (0 for a bad j).  dcp_hip_profile_mu_rung, _calib_excluded_rung: profile i at rung j,
+ * NaN and 0 for what is not calibrated; dcp_hip_profile_mu and dcp_hip_profile_calib_excluded answer for rung 0.
+ * dcp_hip_profile_lambda: the fixed lambda or the profile's fitted one, NaN when it has none; dcp_hip_calib_lambda is
+ * the `lambda` argument of the calibration in force: 0 when it was fitted.  dcp_hip_profile_mu_at: mu of profile i at a
+ * window of len nucleotides, dcp_calib_mu_at (include/deciphon_host.h) of its rungs. */
+#define DCP_CALIB_MAX_LENS 16
+int dcp_hip_calibrate_lengths(struct dcp_hip *, int nseq, int nlen, int const *lens, uint64_t seed, float const freq[4],
+                              float lambda);
+int dcp_hip_calib_num_lengths(struct dcp_hip const *);
+int dcp_hip_calib_length(struct dcp_hip const *, int j);
+float dcp_hip_profile_mu_rung(struct dcp_hip const *, int i, int j);
+int dcp_hip_profile_calib_excluded_rung(struct dcp_hip const *, int i, int j);
+float dcp_hip_profile_lambda(struct dcp_hip const *, int i);
+double dcp_hip_profile_mu_at(struct dcp_hip const *, int i, int64_t len);
 
 /* ---- special transitions (replaces work_reset -> xtrans_setup, c-core/work.c:47-51) ---- */
 int dcp_hip_set_mode(struct dcp_hip *, int multi_hits, int hmmer3_compat);
@@ -208,7 +249,7 @@ void dcp_hip_xtrans(int seq_size, int multi_hits, int hmmer3_compat, float xt[DC
  *
  * The inputs: every accepted call of dcp_hip_add_profile, _add_protein, _load_dcp, _load_hmm, _set_epsilon and
  * _set_gencode (with profiles resident), _commit_profiles,
- * _clear_profiles, _set_sequences, _set_random_sequences, _calibrate, _set_mode or _set_xtrans_table changes them, even one that sets what was
+ * _clear_profiles, _set_sequences, _set_random_sequences, _calibrate, _calibrate_lengths, _set_mode or _set_xtrans_table changes them, even one that sets what was
  * there already (a call refused for outstanding batches or for its arguments changes nothing).  Two things
  * outlive a call and are tied to the inputs they were made from: the staged window list (dcp_hip_stage) and the
  * trellis of the last dcp_hip_path, which is computed only when asked for.  Once the inputs have changed,

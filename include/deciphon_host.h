@@ -278,6 +278,15 @@ int dcp_random_nt(uint64_t seed, uint32_t const t[3], int64_t first_idx, int64_t
  *   z * (-expm1(-exp(-(double)lambda * ((double)lrt - mu))))
  * -- the one place the tail is stated.  NaN when mu is NaN. */
 double dcp_lrt_evalue(float lrt, float mu, float lambda, double z);
+/* mu of a profile at a window of len nucleotides, from the nlen rungs (lens[j], mu[j]) of a calibration over a ladder of
+ * read lengths (dcp_hip_calibrate_lengths, include/deciphon_hip.h) -- the one statement of the rule; dcp_hip_profile_mu_at
+ * and the scan call it.  Piecewise linear in ln len through the points (ln lens[j], mu[j]) of the rungs whose mu is not
+ * NaN: between the usable rungs a < b around len
+ *   mu[a] + (mu[b] - mu[a]) * (log(len / lens[a]) / log(lens[b] / lens[a]))      in double,
+ * and beyond either end the line of the end segment goes on (in theory mu is linear in ln L; clamping would freeze the
+ * error a ladder is there to remove).  At len == lens[j] of a usable rung exactly (double)mu[j].  One usable rung: that
+ * mu, a constant.  None: NaN.  NaN as well for nlen < 1, NULL, len < 1, a length below 1 or lens that do not increase. */
+double dcp_calib_mu_at(int nlen, int const *lens, float const *mu, int64_t len);
 
 #ifdef __cplusplus
 }
